@@ -86,16 +86,18 @@ def _usable_cores(cap=16):
 CPU_BASELINE_THREADS = _usable_cores()
 
 
-REFERENCE_RSL_RL = "/root/reference/rsl_rl"     # exists in the build container only (never on the GPU box)
+REFERENCE_RSL_RL = os.environ.get("WBC_REFERENCE_RSL_RL", "")  # a checkout of the reference's rsl_rl package, when one is at hand (opt-in)
 
 
 def _cpu_learner_classes(kind="port"):
-    """(kind, PPO, ActorCritic) of the CPU baseline. "port" (what every bench line on a GPU box reports: /root/reference does not
-    exist there): this package's eager torch path -- the same op sequence as the reference's rsl_rl, pinned to it seed for seed by
-    tests/test_ppo_parity.py. "reference": the reference's own rsl_rl classes, importable in the build container only -- used by
+    """(kind, PPO, ActorCritic) of the CPU baseline. "port" (what every bench line on a GPU box reports: the reference tree does
+    not travel there): this package's eager torch path -- the same op sequence as the reference's rsl_rl, pinned to it seed for seed by
+    tests/test_ppo_parity.py. "reference": the reference's own rsl_rl classes, imported from $WBC_REFERENCE_RSL_RL -- used by
     `bench.py --cpu-baseline-only`, which times BOTH on one box so that the port's cost is shown next to the reference's
     (profiles/r05_cpu_baseline_reference_vs_port.json)."""
     if kind == "reference":
+        if not os.path.isdir(REFERENCE_RSL_RL):
+            raise RuntimeError("the reference learner needs WBC_REFERENCE_RSL_RL: a checkout of the reference's rsl_rl package")
         import contextlib
         import io
         sys.dont_write_bytecode = True              # the reference tree is read-only
@@ -235,6 +237,40 @@ def _self_launch(args):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
+DUMP_SAMPLE_ENVS = 256         # per-env arrays are dumped for a fixed, seeded sample of envs (keeps the dump near 40 MB)
+DUMP_SIM_TENSORS = ("ROOT_STATES", "DOF_STATE", "OBS_BUF", "REW_BUF", "ARM_REW_BUF", "RESET_BUF", "EPISODE_LENGTH", "TORQUES")
+
+
+def dump_outputs(runner, env, out_dir):
+    """`--dump-outputs DIR`: what the timed path computed in its last iteration, as DIR/<name>.npy (float32 / float64):
+    the policy's parameters after the update (param.<name>), the iteration's loss statistics (stat.<key>), the rollout
+    storage (storage.<field>: T x sampled envs x ...) and the sim's end state (sim.<TENSOR>: sampled envs x ...). The env
+    sample is a seeded choice of DUMP_SAMPLE_ENVS indices (env_index.npy), the same for every run at the same env count."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def save(name, t):
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        a = a.astype(np.float64 if a.dtype in (np.float64, np.int64, np.int32) else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    n = env.num_envs
+    idx = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_SAMPLE_ENVS), replace=False))
+    save("env_index", idx.astype(np.int64))
+    tidx = torch.as_tensor(idx, device=runner.alg.storage.rewards.device)
+    for k, v in runner.alg.actor_critic.state_dict().items():
+        save("param." + k, v)
+    for k, v in runner.history[-1].items():
+        if k not in ("collection_time", "learn_time", "fps"):
+            save("stat." + k, np.float64(v))
+    st = runner.alg.storage
+    for k in ("observations", "actions", "rewards", "dones", "values", "actions_log_prob", "returns", "advantages", "mu", "sigma"):
+        save("storage." + k, getattr(st, k).index_select(1, tidx))
+    for k in DUMP_SIM_TENSORS:
+        save("sim." + k, env.sim.tensor(k).index_select(0, tidx.to(env.sim.tensor(k).device)))
+
+
 def _phase(hist, pred):
     sel = [h for h in hist if pred(h)]
     if not sel:
@@ -278,9 +314,13 @@ def main():
                     help="with --terrain trimesh: terrain.curriculum=True on the Perlin field (grid always has it)")
     ap.add_argument("--cpu-baseline-only", action="store_true",
                     help="no GPU needed: time the rsl_rl PPO-update path on this box's host cores over a synthetic 4096 x 40 rollout -- the "
-                         "REFERENCE's own classes where /root/reference/rsl_rl exists (kind 'reference') and this package's eager port "
+                         "REFERENCE's own classes where $WBC_REFERENCE_RSL_RL names a checkout of them (kind 'reference') and this package's eager port "
                          "(kind 'port'), both on the same storage contents")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed iteration computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if not args.cpu_baseline_only and args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1 (the number of timed PPO iterations)")
 
     if args.cpu_baseline_only:
         r = _synthetic_runner(args.envs_per_gpu, T_STEPS)
@@ -585,6 +625,8 @@ def main():
                                       "traffic": counter_file("ppo_update_traffic.json") if rows == 40960 else None,
                                       "launch_ms": upd_ms, "algorithmic_flops_per_launch": flops, "rows_per_launch": rows,
                                       "launches_timed": len(upd_events), "timed": "inside the timed region, every 10th minibatch call"}
+        if args.dump_outputs:
+            dump_outputs(runner, env, args.dump_outputs)
         if world == 1 and not args.no_cpu_baseline:
             note("cpu baseline ...")
             out["cpu_baseline"] = cpu_baseline(runner)

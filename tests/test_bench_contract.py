@@ -43,21 +43,42 @@ def test_cpu_baseline_leg_reports_the_contract_fields():
 def test_cpu_baseline_never_imports_the_reference_tree():
     before = set(sys.modules)
     bench.cpu_baseline(_stand_in_runner(16, 4), sim_sample_envs=8)
-    new = [m for m in set(sys.modules) - before if getattr(sys.modules[m], "__file__", None) and "/root/reference" in (sys.modules[m].__file__ or "")]
-    assert not new and not any("/root/reference" in p for p in sys.path)
+    new = [m for m in set(sys.modules) - before if m == "rsl_rl" or m.startswith("rsl_rl.")]     # the reference's package (the port is wbc_amd.rsl_rl)
+    assert not new and not (bench.REFERENCE_RSL_RL and bench.REFERENCE_RSL_RL in sys.path)
 
 
-@pytest.mark.skipif(not os.path.isdir(bench.REFERENCE_RSL_RL), reason="the reference tree exists in the build container only")
-def test_cpu_baseline_can_time_the_reference_classes_in_the_build_container():
-    """`bench.py --cpu-baseline-only`: kind 'reference' = the reference's own rsl_rl PPO / ActorCritic on the same storage contents
-    (profiles/r05_cpu_baseline_reference_vs_port.json holds both lines from one box)."""
+def _rsl_rl_checkout(root):
+    """A stand-in for a checkout of the reference's rsl_rl: a package `rsl_rl` with the two entry points the reference leg imports
+    (rsl_rl.algorithms.PPO, rsl_rl.modules.ActorCritic), here re-exporting this package's port so that the test needs nothing
+    outside the repository."""
+    for sub, name in (("algorithms", "PPO"), ("modules", "ActorCritic")):
+        d = root / "rsl_rl" / sub
+        d.mkdir(parents=True)
+        (d / "__init__.py").write_text(f"from wbc_amd.rsl_rl.{sub} import {name}  # noqa: F401\n")
+    (root / "rsl_rl" / "__init__.py").write_text("")
+    return str(root)
+
+
+def test_cpu_baseline_can_time_the_reference_classes_in_the_build_container(tmp_path, monkeypatch):
+    """`bench.py --cpu-baseline-only`: kind 'reference' = the rsl_rl PPO / ActorCritic of the checkout $WBC_REFERENCE_RSL_RL names, on
+    the same storage contents as the port (profiles/r05_cpu_baseline_reference_vs_port.json holds both lines from one box). The
+    checkout is a stand-in built under tmp_path: what is checked is that the leg imports its classes from that location and times them."""
+    ref = _rsl_rl_checkout(tmp_path)
+    monkeypatch.setattr(bench, "REFERENCE_RSL_RL", ref)
+    monkeypatch.setattr(sys, "dont_write_bytecode", sys.dont_write_bytecode)
+    stale = {m: sys.modules.pop(m) for m in list(sys.modules) if m == "rsl_rl" or m.startswith("rsl_rl.")}
     r = bench._synthetic_runner(32, 4)
     try:
         out = bench.cpu_baseline(r, sim_sample_envs=8, learner="reference")
+        origin = sys.modules["rsl_rl"].__file__
     finally:
-        while bench.REFERENCE_RSL_RL in sys.path:
-            sys.path.remove(bench.REFERENCE_RSL_RL)
-    assert out["kind"] == "reference" and bench.REFERENCE_RSL_RL in out["sample"] and out["value"] > 0
+        while ref in sys.path:
+            sys.path.remove(ref)
+        for m in [m for m in sys.modules if m == "rsl_rl" or m.startswith("rsl_rl.")]:
+            del sys.modules[m]
+        sys.modules.update(stale)
+    assert os.path.dirname(os.path.dirname(origin)) == ref
+    assert out["kind"] == "reference" and ref in out["sample"] and out["value"] > 0
     port = bench.cpu_baseline(r, sim_sample_envs=8, learner="port")
     assert port["kind"] == "port" and port["value"] > 0
 
@@ -66,3 +87,8 @@ def test_world_size_mismatch_is_an_error_message_not_an_assert():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and "WORLD_SIZE=2" in (p.stderr + p.stdout)
+
+
+def test_steps_below_one_is_refused_before_any_gpu_work():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--steps must be at least 1" in (p.stderr + p.stdout)
