@@ -199,3 +199,265 @@ extern "C" int wbc_sim_arm_dynamics(wbc_sim* s, const int* link_rb9, const float
   hipLaunchKernelGGL(wbc_arm_dynamics_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, A, root, dofs, bp, mp, n, mm, jac, gtorque);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+
+// ---- whole-body Jacobian and mass matrix (Isaac Gym's acquire_jacobian_tensor / acquire_mass_matrix_tensor, WG:509-510, 550-558) --
+// Coordinates nu = (v_root, omega_root, qd[0..WBC_NDOF-1]) (include/wbc_sim.h). One 64-lane workgroup per env: forward kinematics,
+// spatial inertias and composites into LDS, then two sweeps in which consecutive lanes store consecutive 16-byte pieces of the env's
+// J [27,6,26] and M [26,26] rows (structural zeros included), so every store instruction writes 1 KB of one contiguous range.
+// J is assembled in LDS a chunk of rigid bodies at a time (one lane per rigid body and column) and copied out.
+#define BD_NCOL WBC_NCOL                        // 26 generalised coordinates
+#define BD_JROW (6 * BD_NCOL)                  // 156 floats of J per rigid body
+#define BD_JENV (WBC_NRB * BD_JROW)            // 4212 floats of J per env
+#define BD_MENV (BD_NCOL * BD_NCOL)            // 676 floats of M per env
+#define BD_JCHUNK 9                            // rigid bodies per LDS chunk of J (5.6 KB)
+static_assert(WBC_NRB % BD_JCHUNK == 0 && (BD_JCHUNK * BD_JROW) % 4 == 0, "J chunks");
+
+struct BodyConst {
+  int32_t parent[WBC_NB], axis[WBC_NB], dof[WBC_NB];
+  uint32_t anc[WBC_NB];                        // bit a: moving body a is on the path root..b (b included)
+  int32_t col_body[WBC_NDOF];                  // moving body DoF d drives; -1: none (the locked fingers)
+  int32_t rb_body[WBC_NRB];
+  int32_t gripper_body;
+  float rb_offset[WBC_NRB][3];
+  float joint_xyz[WBC_NB][3], mass[WBC_NB], com[WBC_NB][3], inertia[WBC_NB][6];
+};
+
+extern "C" __global__ void __launch_bounds__(64) wbc_body_dynamics_kernel(BodyConst B, const float* __restrict__ root,
+                                                                         const float* __restrict__ dofs,
+                                                                         const float* __restrict__ body_params, int n,
+                                                                         float* __restrict__ jac, float* __restrict__ mm) {
+  __shared__ float sE[WBC_NB][9], sP[WBC_NB][3];   // body rotation (columns = body axes) and origin in F
+  __shared__ float sI[WBC_NB][10];                 // spatial inertia about F's origin, in F: m, m c (3), rotational xx yy zz xy xz yz
+  __shared__ float sIc[WBC_NB][10];                // the same, composite of the subtree
+  __shared__ float sAw[WBC_NB][3], sOw[WBC_NB][3]; // joint axis and body origin, world axes, relative to the root origin
+  __shared__ float sDw[WBC_NRB][3];                // rigid-body origin, world axes, relative to the root origin
+  __shared__ uint32_t sAnc[WBC_NB], sRbAnc[WBC_NRB];
+  __shared__ int32_t sColBody[BD_NCOL];            // 0 for the six root columns, the driven body, or -1
+  __shared__ float sS[BD_NCOL][6], sF[BD_NCOL][6]; // per column: motion subspace (omega; v at F's origin) in F, and Ic S
+  extern __shared__ float4 sJ4[];                  // dynamic, only when jac is written: BD_JCHUNK rigid bodies' rows of J, as stored
+  const int env = blockIdx.x, lane = threadIdx.x;
+  if (env >= n) return;
+  float R[9];
+  quat_to_mat(root + (size_t)env * 26 + 3, R);
+
+  // 1) forward kinematics in F, lane b = moving body b: compose the joint transforms from b up to the root
+  if (lane < WBC_NB) {
+    const int b = lane;
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    f3 p = mk3(0.f, 0.f, 0.f);
+    int a = b;
+    for (int it = 0; it < WBC_MAX_DEPTH && a > 0; ++it) {      // (E, p) <- (Rot_a E, xyz_a + Rot_a p)
+      const int ax = B.axis[a];
+      const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
+      float s, c;
+      sincosf(dofs[(size_t)env * (2 * WBC_NDOF) + 2 * B.dof[a]], &s, &c);
+      const float t = 1.f - c;
+      const float Q[9] = {c + t * ux * ux, t * ux * uy - s * uz, t * ux * uz + s * uy,
+                          t * uy * ux + s * uz, c + t * uy * uy, t * uy * uz - s * ux,
+                          t * uz * ux - s * uy, t * uz * uy + s * ux, c + t * uz * uz};
+      float En[9];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) En[r * 3 + k] = Q[r * 3] * E[k] + Q[r * 3 + 1] * E[3 + k] + Q[r * 3 + 2] * E[6 + k];
+#pragma unroll
+      for (int e = 0; e < 9; ++e) E[e] = En[e];
+      p = mk3(B.joint_xyz[a][0], B.joint_xyz[a][1], B.joint_xyz[a][2]) + mat_mul(Q, p);
+      a = B.parent[a];
+    }
+#pragma unroll
+    for (int e = 0; e < 9; ++e) sE[b][e] = E[e];
+    st3(sP[b], p);
+    // spatial inertia about F's origin: the per-env root composite and gripper body (body_params), the model's otherwise
+    float m = B.mass[b], com[3] = {B.com[b][0], B.com[b][1], B.com[b][2]}, I6[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) I6[j] = B.inertia[b][j];
+    const int slot = b == 0 ? 0 : (b == B.gripper_body ? 10 : -1);
+    if (slot >= 0) {
+      const float* bp = body_params + (size_t)env * 20 + slot;
+      m = bp[0];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) I6[j] = bp[4 + j];
+    }
+    const f3 C = p + mat_mul(E, mk3(com[0], com[1], com[2]));
+    const float Ib[9] = {I6[0], I6[3], I6[4], I6[3], I6[1], I6[5], I6[4], I6[5], I6[2]};
+    float EI[9], Ibar[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) EI[r * 3 + k] = E[r * 3] * Ib[k] + E[r * 3 + 1] * Ib[3 + k] + E[r * 3 + 2] * Ib[6 + k];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) Ibar[r * 3 + k] = EI[r * 3] * E[k * 3] + EI[r * 3 + 1] * E[k * 3 + 1] + EI[r * 3 + 2] * E[k * 3 + 2];
+    const float CC = dot(C, C);
+    sI[b][0] = m; sI[b][1] = m * C.x; sI[b][2] = m * C.y; sI[b][3] = m * C.z;
+    sI[b][4] = Ibar[0] + m * (CC - C.x * C.x);
+    sI[b][5] = Ibar[4] + m * (CC - C.y * C.y);
+    sI[b][6] = Ibar[8] + m * (CC - C.z * C.z);
+    sI[b][7] = Ibar[1] - m * C.x * C.y;
+    sI[b][8] = Ibar[2] - m * C.x * C.z;
+    sI[b][9] = Ibar[5] - m * C.y * C.z;
+    const int ax = B.axis[b];                                  // -1 for the root: no joint axis
+    const f3 axF = mk3(ax == 0 ? E[0] : ax == 1 ? E[1] : ax == 2 ? E[2] : 0.f,
+                       ax == 0 ? E[3] : ax == 1 ? E[4] : ax == 2 ? E[5] : 0.f,
+                       ax == 0 ? E[6] : ax == 1 ? E[7] : ax == 2 ? E[8] : 0.f);
+    st3(sAw[b], mat_mul(R, axF));
+    st3(sOw[b], mat_mul(R, p));
+    sAnc[b] = B.anc[b];
+  }
+  __syncthreads();
+
+  // 2) composite inertias (a plain sum: every body's inertia is already about F's origin) and the rigid-body levers
+  if (lane < WBC_NB) {
+    float acc[10];
+#pragma unroll
+    for (int j = 0; j < 10; ++j) acc[j] = 0.f;
+    for (int d = 0; d < WBC_NB; ++d)
+      if ((sAnc[d] >> lane) & 1u) {
+#pragma unroll
+        for (int j = 0; j < 10; ++j) acc[j] += sI[d][j];
+      }
+#pragma unroll
+    for (int j = 0; j < 10; ++j) sIc[lane][j] = acc[j];
+  } else if (lane >= 32 && lane < 32 + WBC_NRB) {
+    const int r = lane - 32, b = B.rb_body[r];
+    const f3 pF = ld3(sP[b]) + mat_mul(sE[b], mk3(B.rb_offset[r][0], B.rb_offset[r][1], B.rb_offset[r][2]));
+    st3(sDw[r], mat_mul(R, pF));
+    sRbAnc[r] = sAnc[b];
+  }
+  __syncthreads();
+
+  // 3) per generalised coordinate c: its motion subspace S_c in F and F_c = Ic S_c of the subtree it moves. The root columns are
+  //    those of the world-frame coordinates (v_F = R^T v_root, omega_F = R^T omega_root), i.e. M = T^T M_F T with T = diag(R^T, R^T, 1).
+  if (lane < BD_NCOL) {
+    const int c = lane;
+    int b = 0;
+    float S[6];
+    if (c < 6) {
+      const int j = c < 3 ? c : c - 3;
+      const f3 row = matT_mul(R, mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f));
+      const bool lin = c < 3;
+      S[0] = lin ? 0.f : row.x; S[1] = lin ? 0.f : row.y; S[2] = lin ? 0.f : row.z;
+      S[3] = lin ? row.x : 0.f; S[4] = lin ? row.y : 0.f; S[5] = lin ? row.z : 0.f;
+    } else {
+      b = B.col_body[c - 6];
+      if (b >= 0) {
+        const int ax = B.axis[b];
+        const f3 a = mk3(sE[b][ax], sE[b][3 + ax], sE[b][6 + ax]), l = cross(ld3(sP[b]), a);
+        S[0] = a.x; S[1] = a.y; S[2] = a.z; S[3] = l.x; S[4] = l.y; S[5] = l.z;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) S[j] = 0.f;
+      }
+    }
+    float Fv[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (b >= 0) {
+      const float* I = sIc[b];
+      const f3 w = mk3(S[0], S[1], S[2]), v = mk3(S[3], S[4], S[5]), h = mk3(I[1], I[2], I[3]);
+      const f3 top = mk3(I[4] * w.x + I[7] * w.y + I[8] * w.z, I[7] * w.x + I[5] * w.y + I[9] * w.z,
+                         I[8] * w.x + I[9] * w.y + I[6] * w.z) + cross(h, v);
+      const f3 bot = cross(w, h) + I[0] * v;
+      Fv[0] = top.x; Fv[1] = top.y; Fv[2] = top.z; Fv[3] = bot.x; Fv[4] = bot.y; Fv[5] = bot.z;
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) { sS[c][j] = S[j]; sF[c][j] = Fv[j]; }
+    sColBody[c] = b;
+  }
+  __syncthreads();
+
+  // 4) M: M_ij = S_i . (Ic S_j) with j's body in the subtree of i's (and symmetrically), 0 where neither moves the other
+  if (mm) {
+    float4* out = reinterpret_cast<float4*>(mm + (size_t)env * BD_MENV);
+    for (int t = lane; t < BD_MENV / 4; t += 64) {
+      float v[4];
+      int i = (4 * t) / BD_NCOL, j = 4 * t - i * BD_NCOL;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int bi = sColBody[i], bj = sColBody[j];
+        float x = 0.f;
+        if (bi >= 0 && bj >= 0) {
+          if ((sAnc[bj] >> bi) & 1u) x = dot6(sS[i], sF[j]);
+          else if ((sAnc[bi] >> bj) & 1u) x = dot6(sS[j], sF[i]);
+        }
+        v[u] = x;
+        if (++j == BD_NCOL) { j = 0; ++i; }
+      }
+      out[t] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+  }
+
+  // 5) J, BD_JCHUNK rigid bodies at a time: one lane per (rigid body, column) writes that column's six rows into an LDS copy of the
+  //    output rows, which the wave then stores 16 bytes per lane. Levers from world-axis vectors relative to the root origin.
+  if (jac) {
+    float* sJ = reinterpret_cast<float*>(sJ4);
+    float4* out = reinterpret_cast<float4*>(jac + (size_t)env * BD_JENV);
+    for (int r0 = 0; r0 < WBC_NRB; r0 += BD_JCHUNK) {
+      for (int it = lane; it < BD_JCHUNK * BD_NCOL; it += 64) {
+        const int rr = it / BD_NCOL, c = it - rr * BD_NCOL, r = r0 + rr;
+        const f3 d = ld3(sDw[r]);
+        f3 lin = mk3(0.f, 0.f, 0.f), ang = mk3(0.f, 0.f, 0.f);
+        if (c < 6) {
+          const int j = c < 3 ? c : c - 3;
+          const f3 e = mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f);
+          if (c < 3) lin = e;                                  // v_root: identity on the linear rows
+          else { lin = cross(e, d); ang = e; }                 // omega_root: e_j x d_r, identity on the angular rows
+        } else {
+          const int b = sColBody[c];
+          if (b >= 0 && ((sRbAnc[r] >> b) & 1u)) {
+            ang = ld3(sAw[b]);
+            lin = cross(ang, d - ld3(sOw[b]));
+          }
+        }
+        float* o = sJ + rr * BD_JROW + c;
+        o[0] = lin.x; o[BD_NCOL] = lin.y; o[2 * BD_NCOL] = lin.z;
+        o[3 * BD_NCOL] = ang.x; o[4 * BD_NCOL] = ang.y; o[5 * BD_NCOL] = ang.z;
+      }
+      __syncthreads();
+      for (int t = lane; t < BD_JCHUNK * BD_JROW / 4; t += 64) out[r0 * (BD_JROW / 4) + t] = sJ4[t];
+      __syncthreads();
+    }
+  }
+}
+
+extern "C" int wbc_sim_internal_fail(int code, const char* msg);
+
+// Outputs (device, caller-owned, 16-byte aligned, either may be NULL): jac f32 [N,27,6,26], mm f32 [N,26,26] (include/wbc_sim.h).
+extern "C" int wbc_sim_body_dynamics(wbc_sim* s, float* jac, float* mm, void* stream) {
+  StreamDeviceGuard sdg(stream);
+  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: sim is NULL");
+  if (!jac && !mm) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: jac and mm are both NULL");
+  if (((uintptr_t)jac | (uintptr_t)mm) & 15u) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: jac / mm must be 16-byte aligned");
+  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: no sim state");
+  const wbc_model& m = hc->model;
+  BodyConst B;
+  for (int d = 0; d < WBC_NDOF; ++d) B.col_body[d] = -1;
+  for (int b = 0; b < WBC_NB; ++b) {
+    B.parent[b] = m.parent[b]; B.axis[b] = m.axis[b]; B.dof[b] = m.dof[b]; B.mass[b] = m.mass[b];
+    for (int j = 0; j < 3; ++j) { B.joint_xyz[b][j] = m.joint_xyz[b][j]; B.com[b][j] = m.com[b][j]; }
+    for (int j = 0; j < 6; ++j) B.inertia[b][j] = m.inertia[b][j];
+    // the kernel walks at most WBC_MAX_DEPTH joints from a body to the root and indexes 32-bit ancestor masks
+    uint32_t anc = 1u << b;
+    int depth = 0;
+    for (int a = b; a > 0; a = m.parent[a]) {
+      if (m.parent[a] < 0 || m.parent[a] >= a || ++depth > WBC_MAX_DEPTH || m.axis[a] < 0 || m.axis[a] > 2 || m.dof[a] < 0 || m.dof[a] >= WBC_NDOF)
+        return wbc_sim_internal_fail(-3, "wbc_sim_body_dynamics: the model's tree is not one the kernel walks");
+      anc |= 1u << m.parent[a];
+    }
+    B.anc[b] = anc;
+    if (b > 0) B.col_body[m.dof[b]] = b;
+  }
+  for (int r = 0; r < WBC_NRB; ++r) {
+    if (m.rb_body[r] < 0 || m.rb_body[r] >= WBC_NB) return wbc_sim_internal_fail(-3, "wbc_sim_body_dynamics: bad rb_body");
+    B.rb_body[r] = m.rb_body[r];
+    for (int j = 0; j < 3; ++j) B.rb_offset[r][j] = m.rb_offset[r][j];
+  }
+  B.gripper_body = m.gripper_body;
+  // the J chunk is dynamic LDS: a mass-matrix-only refresh keeps the small footprint (twice the resident envs per CU)
+  const size_t jbytes = jac ? BD_JCHUNK * BD_JROW * sizeof(float) : 0;
+  hipLaunchKernelGGL(wbc_body_dynamics_kernel, dim3(n), dim3(64), jbytes, (hipStream_t)stream, B, root, dofs, bp, n, jac, mm);
+  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_body_dynamics: launch failed");
+}

@@ -629,6 +629,8 @@ extern "C" int wbc_sim_internal_arm_inputs(wbc_sim* s, const DevConst** hc, cons
   *hc = &s->hc; *root = s->T.root; *dofs = s->T.dof; *body_params = s->T.body_params; *mass_params = s->T.mass_params; *n = s->n;
   return 0;
 }
+// wbc_last_error() for the entry points that live in other translation units
+extern "C" int wbc_sim_internal_fail(int code, const char* msg) { return fail(code, msg); }
 
 extern "C" int wbc_sim_get_step_counter(wbc_sim* s, int64_t* out) { if (!s || !out) return fail(-1, "null"); *out = s->step_counter; return 0; }
 extern "C" int wbc_sim_set_step_counter(wbc_sim* s, int64_t v) { if (!s) return fail(-1, "null"); s->step_counter = v; return 0; }

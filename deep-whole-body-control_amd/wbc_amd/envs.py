@@ -462,6 +462,23 @@ class WidowGo1(LeggedRobot):
             else:
                 self.extras["time_outs"] = self.time_out_buf
 
+    # ---- whole-body Jacobian / mass matrix (WG:509-510, 517-518, 550-558): created on first use, refreshed only on request ------
+    @property
+    def jacobian_whole(self) -> torch.Tensor:
+        """f32 [N, 27, 6, 26], persistent: views taken of it (the reference's ee_j_eef) follow refresh_jacobian_tensors()."""
+        return self.sim.acquire_jacobian_tensor()
+
+    @property
+    def mm_whole(self) -> torch.Tensor:
+        """f32 [N, 26, 26], persistent: views taken of it (the reference's mm) follow refresh_mass_matrix_tensors()."""
+        return self.sim.acquire_mass_matrix_tensor()
+
+    def refresh_jacobian_tensors(self):
+        self.sim.refresh_jacobian_tensors()
+
+    def refresh_mass_matrix_tensors(self):
+        self.sim.refresh_mass_matrix_tensors()
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])

@@ -160,6 +160,37 @@ class WbcSim:
         check(self.L.wbc_sim_arm_dynamics(self.h, rb, ms, mm.data_ptr(), jac.data_ptr(), gt.data_ptr(), self._stream()), "wbc_sim_arm_dynamics")
         return mm, jac, gt
 
+    # ---- whole-body Jacobian / mass matrix (gym.acquire_jacobian_tensor / acquire_mass_matrix_tensor, WG:509-510, 550-558) ----
+    def acquire_jacobian_tensor(self) -> torch.Tensor:
+        """The persistent f32 [N, 27, 6, 26] Jacobian of every robot rigid body's origin w.r.t. (v_root, omega_root, qd), world
+        frame (include/wbc_sim.h: wbc_sim_body_dynamics). The same tensor on every call; refresh_jacobian_tensors() fills it."""
+        if self.__dict__.get("_jacobian") is None:
+            self._jacobian = torch.zeros(self.num_envs, abi.NRB, 6, 6 + abi.NDOF, dtype=torch.float32, device=self.device)
+        return self._jacobian
+
+    def acquire_mass_matrix_tensor(self) -> torch.Tensor:
+        """The persistent f32 [N, 26, 26] mass matrix in the same coordinates; refresh_mass_matrix_tensors() fills it."""
+        if self.__dict__.get("_mass_matrix") is None:
+            self._mass_matrix = torch.zeros(self.num_envs, 6 + abi.NDOF, 6 + abi.NDOF, dtype=torch.float32, device=self.device)
+        return self._mass_matrix
+
+    def body_dynamics(self, jac: Optional[torch.Tensor] = None, mm: Optional[torch.Tensor] = None) -> None:
+        """One wbc_sim_body_dynamics launch on the current stream into caller-owned buffers (either may be None)."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        for t, shape in ((jac, (n, abi.NRB, 6, ncol)), (mm, (n, ncol, ncol))):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+        check(self.L.wbc_sim_body_dynamics(self.h, jac.data_ptr() if jac is not None else None,
+                                           mm.data_ptr() if mm is not None else None, self._stream()), "wbc_sim_body_dynamics")
+
+    def refresh_jacobian_tensors(self) -> None:
+        """Recompute the acquired Jacobian in place from the current root / DoF state (views of it see the new values)."""
+        self.body_dynamics(jac=self.acquire_jacobian_tensor())
+
+    def refresh_mass_matrix_tensors(self) -> None:
+        """Recompute the acquired mass matrix in place from the current state and per-env body parameters."""
+        self.body_dynamics(mm=self.acquire_mass_matrix_tensor())
+
     def episode_stats(self, scale: float, track_state: torch.Tensor = None, track_cap: int = 0) -> torch.Tensor:
         """Means over the envs that reset in the last step of their finished episode's reward sums [NREW] and metric
         sums [NMETRIC], times `scale`, as one fresh device tensor (WG:743-754 without a host sync). With `track_state`

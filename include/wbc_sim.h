@@ -534,6 +534,23 @@ size_t wbc_ppo_workspace_floats(int B);
 int wbc_sim_arm_dynamics(wbc_sim* sim, const int* link_rb9, const float* link_mass9, float* mm, float* jac,
                          float* gtorque, void* stream);
 
+/* Isaac Gym's whole-body tensors of the robot actor (acquire_jacobian_tensor / acquire_mass_matrix_tensor, widowGo1.py:509-510,
+ * 517-518, 550-558), from the sim's current root / DoF state and per-env body parameters (WBC_T_BODY_PARAMS).
+ * Generalised velocity nu = (v_root, omega_root, qd[0..WBC_NDOF-1]), WBC_NCOL = 6 + WBC_NDOF = 26 columns:
+ *   v_root, omega_root  the root origin's linear and the root's angular velocity, world frame (WBC_T_ROOT_STATES[:, 0, 7:13]);
+ *   qd                  simulator DoF order (WBC_T_DOF_STATE[..., 1]); column 6 + d is DoF d.
+ * jac f32 [N, WBC_NRB, 6, 26]: rows 0:3 the world-frame linear velocity of rigid body r's ORIGIN (rb_offset), rows 3:6 its
+ *   angular velocity, as linear maps of nu: J[e, r] @ nu_e == rigid_body_state[e, r, 7:13] (wbc_sim_refresh_rigid_body_state).
+ *   A DoF column is non-zero only where that joint is an ancestor of r's moving body.
+ * mm f32 [N, 26, 26]: kinetic energy 1/2 nu^T M nu = sum over moving bodies of 1/2 (m |v_com|^2 + omega^T I_world omega) with the
+ *   per-env root composite and gripper body of WBC_T_BODY_PARAMS (the inertias the step kernel integrates with).
+ * Locked fingers (DoFs 18, 19: prismatic joints the dynamics treats as rigid, see urdf_model.build_model): their columns of J
+ * and their rows and columns of M are exactly zero; M restricted to the other 24 coordinates is symmetric positive definite.
+ * jac / mm: caller-owned device memory, 16-byte aligned; either may be NULL (that tensor is not written), not both.
+ * -1 with a message in wbc_last_error() for a NULL sim, both outputs NULL or a misaligned output. */
+#define WBC_NCOL (6 + WBC_NDOF)
+int wbc_sim_body_dynamics(wbc_sim* sim, float* jac, float* mm, void* stream);
+
 /* extras["episode"] of reset_idx (widowGo1.py:743-754): out[0:WBC_NREW] = mean over the envs that reset in the last
  * step of their finished episode's reward sums, out[WBC_NREW:+WBC_NMETRIC] the same for the metric sums, both
  * times `scale` (1 / max_episode_length_s). `out`: device, WBC_NREW + WBC_NMETRIC floats. On a step in which no env reset
