@@ -7,12 +7,14 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "wbc_device.h"
 #include "wbc_stats.h"
 #include "wbc_stream_guard.h"
+#include "wbc_urdf.h"
 
 extern "C" __global__ void wbc_step_kernel(const DevTensors* __restrict__ Tp, const DevConst* __restrict__ C, const float* __restrict__ actions, int num_envs,
                                            uint64_t seed, uint64_t step, StepOut so, uint32_t deal);
@@ -642,6 +644,8 @@ struct wbc_asset {
   wbc_curriculum cur[2];
   int ndof = 0, nrb = 0;
   std::vector<std::string> dof_names, rb_names;
+  bool has_cfg = true;                  // false: loaded from a URDF without a template
+  std::vector<wbc_dof_props> props;     // URDF assets only
 };
 static const char kAssetMagic[10] = "WBCASSET1";
 extern "C" int wbc_asset_load(const char* path, wbc_asset** out) {
@@ -689,8 +693,82 @@ extern "C" int wbc_asset_dof_properties(const wbc_asset* a, float* lower, float*
   return 0;
 }
 extern "C" const wbc_model* wbc_asset_model(const wbc_asset* a) { return a ? &a->model : nullptr; }
-extern "C" const wbc_task_cfg* wbc_asset_task_cfg(const wbc_asset* a) { return a ? &a->cfg : nullptr; }
-extern "C" const wbc_curriculum* wbc_asset_curriculum(const wbc_asset* a, int which) { return (a && (which == 0 || which == 1)) ? &a->cur[which] : nullptr; }
+extern "C" const wbc_task_cfg* wbc_asset_task_cfg(const wbc_asset* a) { return (a && a->has_cfg) ? &a->cfg : nullptr; }
+extern "C" const wbc_curriculum* wbc_asset_curriculum(const wbc_asset* a, int which) {
+  return (a && a->has_cfg && (which == 0 || which == 1)) ? &a->cur[which] : nullptr;
+}
+
+// ---- asset from a URDF (wbc_urdf.h), see include/wbc_sim.h -------------------------------------------------------------------------
+extern "C" void wbc_asset_opts_default(wbc_asset_opts* o) { if (o) wbc_urdf::default_opts(o); }
+extern "C" int wbc_asset_load_urdf(const char* path, const wbc_asset_opts* opts, const wbc_asset* tmpl, wbc_asset** out) {
+  if (!path || !out) return fail(-1, "wbc_asset_load_urdf: bad arguments");
+  try {
+    wbc_asset_opts dflt;
+    wbc_urdf::default_opts(&dflt);
+    const wbc_asset_opts& o = opts ? *opts : dflt;
+    wbc_urdf::Result r;
+    std::string err;
+    int rc = wbc_urdf::load(path, o, r, err);
+    if (rc) return fail(rc, "wbc_asset_load_urdf: " + err);
+    std::unique_ptr<wbc_asset> a(new wbc_asset());
+    a->model = r.model;
+    a->ndof = (int)r.dof_names.size();
+    a->nrb = (int)r.rb_names.size();
+    a->dof_names = r.dof_names;
+    a->rb_names = r.rb_names;
+    a->props = r.props;
+    a->has_cfg = false;
+    memset(&a->cfg, 0, sizeof(a->cfg));
+    memset(a->cur, 0, sizeof(a->cur));
+    if (tmpl) {
+      if (!tmpl->has_cfg) return fail(-1, "wbc_asset_load_urdf: the template carries no task configuration");
+      for (int i = 0; i < a->ndof || i < tmpl->ndof; ++i) {
+        const char* mine = i < a->ndof ? a->dof_names[i].c_str() : "(none)";
+        const char* theirs = i < tmpl->ndof ? tmpl->dof_names[i].c_str() : "(none)";
+        if (strcmp(mine, theirs) != 0)
+          return fail(-4, std::string("wbc_asset_load_urdf: DoF ") + std::to_string(i) + " of the template is " + theirs + ", the URDF's is " + mine);
+      }
+      for (int i = 0; i < a->nrb || i < tmpl->nrb; ++i) {
+        const char* mine = i < a->nrb ? a->rb_names[i].c_str() : "(none)";
+        const char* theirs = i < tmpl->nrb ? tmpl->rb_names[i].c_str() : "(none)";
+        if (strcmp(mine, theirs) != 0)
+          return fail(-4, std::string("wbc_asset_load_urdf: rigid body ") + std::to_string(i) + " of the template is " + theirs + ", the URDF's is " + mine);
+      }
+      a->cfg = tmpl->cfg;
+      a->cur[0] = tmpl->cur[0];
+      a->cur[1] = tmpl->cur[1];
+      wbc_urdf::set_model_limits(a->cfg, r, o);
+      a->has_cfg = true;
+    }
+    *out = a.release();
+    return 0;
+  } catch (const std::exception& e) {
+    return fail(-2, std::string("wbc_asset_load_urdf: ") + e.what());
+  }
+}
+extern "C" int wbc_asset_dof_properties_ex(const wbc_asset* a, wbc_dof_props* out) {
+  if (!a || !out) return fail(-1, "wbc_asset_dof_properties_ex: bad arguments");
+  if (a->props.empty()) return fail(-5, "wbc_asset_dof_properties_ex: no URDF property table (a .wbcasset file stores the limits only)");
+  for (int i = 0; i < a->ndof; ++i) out[i] = a->props[i];
+  return 0;
+}
+extern "C" int wbc_asset_find_rigid_body(const wbc_asset* a, const char* name) {
+  if (!a || !name) return -1;
+  for (int i = 0; i < a->nrb; ++i)
+    if (a->rb_names[i] == name) return i;
+  return -1;
+}
+extern "C" int wbc_asset_find_dof(const wbc_asset* a, const char* name) {
+  if (!a || !name) return -1;
+  for (int i = 0; i < a->ndof; ++i)
+    if (a->dof_names[i] == name) return i;
+  return -1;
+}
+extern "C" int wbc_asset_force_sensor_bodies(const wbc_asset* a, int32_t out[4]) {
+  if (!a || !out) return fail(-1, "wbc_asset_force_sensor_bodies: bad arguments");
+  for (int i = 0; i < WBC_NFEET; ++i) out[i] = a->model.feet_rb[i];
+  return 0;
+}
 
 // sizes of the ABI structs, checked against the ctypes mirrors by the CPU tests
 extern "C" void wbc_abi_sizes(int* out) { out[0] = (int)sizeof(wbc_model); out[1] = (int)sizeof(wbc_task_cfg); out[2] = (int)sizeof(wbc_curriculum); }

@@ -661,3 +661,78 @@ def asset_bytes(m: RobotModel, cfg) -> bytes:
         assert len(b) < 64
         parts.append(b.ljust(64, b"\0"))
     return b"".join(parts)
+
+
+class WbcAssetOpts(C.Structure):
+    """wbc_asset_opts (include/wbc_sim.h): gymapi.AssetOptions (WG:268-282) plus what this framework's model needs."""
+    _fields_ = [("struct_size", C.c_uint32), ("default_dof_drive_mode", i32), ("collapse_fixed_joints", i32),
+                ("replace_cylinder_with_capsule", i32), ("flip_visual_attachments", i32), ("fix_base_link", i32), ("disable_gravity", i32),
+                ("density", C.c_double), ("angular_damping", C.c_double), ("linear_damping", C.c_double),
+                ("max_angular_velocity", C.c_double), ("max_linear_velocity", C.c_double), ("armature", C.c_double),
+                ("thickness", C.c_double), ("self_collisions", i32), ("root_link", C.c_char * 64), ("foot_name", C.c_char * 64),
+                ("gripper_name", C.c_char * 64), ("lock_friction_above", C.c_double), ("box_size", C.c_double), ("rest_offset", C.c_double),
+                ("arm_limb_fit", (C.c_double * 3) * 3), ("soft_dof_pos_limit", C.c_double), ("soft_dof_vel_limit", C.c_double),
+                ("soft_torque_limit", C.c_double)]
+
+
+class WbcDofProps(C.Structure):
+    """wbc_dof_props: one entry of wbc_asset_dof_properties_ex (Isaac Gym's DofProperties + locked)."""
+    _fields_ = [("has_limits", i32), ("lower", f32), ("upper", f32), ("drive_mode", i32), ("velocity", f32), ("effort", f32),
+                ("stiffness", f32), ("damping", f32), ("friction", f32), ("armature", f32), ("locked", i32)]
+
+
+class UrdfAsset:
+    """What wbc_asset_load_urdf loaded, copied out of the library (the C handle is freed before this is returned): `model`
+    (WbcModel), `task_cfg` / `curricula` (None without a template), `dof_names`, `rb_names`, `dof_props` (WbcDofProps list) and
+    `force_sensor_bodies` (the feet, WG:310-315)."""
+
+    def __init__(self, model, task_cfg, curricula, dof_names, rb_names, dof_props, force_sensor_bodies):
+        self.model, self.task_cfg, self.curricula = model, task_cfg, curricula
+        self.dof_names, self.rb_names, self.dof_props, self.force_sensor_bodies = dof_names, rb_names, dof_props, force_sensor_bodies
+
+
+def load_urdf_asset(path: str, template: Optional[str] = None, **opts) -> UrdfAsset:
+    """Thin ctypes wrapper of wbc_asset_load_urdf. `template`: a .wbcasset file (e.g. DEFAULT_ASSET) whose task cfg and curricula are
+    copied, with the model-derived limits recomputed from the URDF. `opts`: wbc_asset_opts fields over wbc_asset_opts_default
+    (names as str, arm_limb_fit as {limb: (radius, cap0, cap1)} like ARM_LIMB_FIT or a 3x3 sequence). Raises native.WbcError."""
+    from .native import WbcError, lib
+    L = lib()
+    o = WbcAssetOpts()
+    L.wbc_asset_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k == "arm_limb_fit":
+            v = [v[n] for n in ("upper_arm", "forearm", "hand")] if isinstance(v, dict) else v
+            _set(o.arm_limb_fit, v)
+        elif k in ("root_link", "foot_name", "gripper_name"):
+            setattr(o, k, v.encode())
+        elif k in dict(WbcAssetOpts._fields_) and k != "struct_size":
+            setattr(o, k, v)
+        else:
+            raise TypeError(f"load_urdf_asset: unknown option {k!r}")
+    tmpl = C.c_void_p()
+    if template is not None:
+        rc = L.wbc_asset_load(os.fsencode(template), C.byref(tmpl))
+        if rc:
+            raise WbcError(f"wbc_asset_load failed ({rc}): {L.wbc_last_error().decode()}")
+    a = C.c_void_p()
+    try:
+        rc = L.wbc_asset_load_urdf(os.fsencode(path), C.byref(o), tmpl, C.byref(a))
+        if rc:
+            raise WbcError(f"wbc_asset_load_urdf failed ({rc}): {L.wbc_last_error().decode()}")
+        model = WbcModel.from_buffer_copy(L.wbc_asset_model(a).contents)
+        p = L.wbc_asset_task_cfg(a)
+        task_cfg = WbcTaskCfg.from_buffer_copy(p.contents) if p else None
+        curricula = tuple(WbcCurriculum.from_buffer_copy(L.wbc_asset_curriculum(a, w).contents) for w in (0, 1)) if p else None
+        ndof, nrb = L.wbc_asset_dof_count(a), L.wbc_asset_rigid_body_count(a)
+        props = (WbcDofProps * ndof)()
+        if L.wbc_asset_dof_properties_ex(a, props):
+            raise WbcError(f"wbc_asset_dof_properties_ex: {L.wbc_last_error().decode()}")
+        feet = (i32 * NFEET)()
+        L.wbc_asset_force_sensor_bodies(a, feet)
+        return UrdfAsset(model, task_cfg, curricula, [L.wbc_asset_dof_name(a, i).decode() for i in range(ndof)],
+                         [L.wbc_asset_rigid_body_name(a, i).decode() for i in range(nrb)], list(props), list(feet))
+    finally:
+        if a:
+            L.wbc_asset_free(a)
+        if tmpl:
+            L.wbc_asset_free(tmpl)

@@ -92,6 +92,12 @@ def lib():
         L.wbc_asset_task_cfg.restype = C.POINTER(abi.WbcTaskCfg)
         L.wbc_asset_curriculum.argtypes = [c_void, c_int]
         L.wbc_asset_curriculum.restype = C.POINTER(abi.WbcCurriculum)
+        L.wbc_asset_opts_default.argtypes = [C.POINTER(abi.WbcAssetOpts)]
+        L.wbc_asset_opts_default.restype = None
+        L.wbc_asset_load_urdf.argtypes = [C.c_char_p, C.POINTER(abi.WbcAssetOpts), c_void, C.POINTER(c_void)]
+        L.wbc_asset_dof_properties_ex.argtypes = [c_void, C.POINTER(abi.WbcDofProps)]
+        L.wbc_asset_find_rigid_body.argtypes = L.wbc_asset_find_dof.argtypes = [c_void, C.c_char_p]
+        L.wbc_asset_force_sensor_bodies.argtypes = [c_void, C.POINTER(C.c_int32)]
         L.wbc_ppo_sq_partials_offset.argtypes = [c_int]
         L.wbc_ppo_sq_partials_offset.restype = C.c_size_t
         L.wbc_ppo_clip_adam.argtypes = [c_void] * 4 + [C.c_float] * 7 + [c_void, c_void, c_void]
@@ -117,7 +123,9 @@ EXPORTED_SYMBOLS = [
     "wbc_ppo_num_splits", "wbc_ppo_workspace_floats", "wbc_ppo_sq_partials_offset", "wbc_hist_train_grad", "wbc_hist_train_grad_floats",
     "wbc_hist_train_workspace_floats", "wbc_hist_clip_adam", "wbc_priv_latent", "wbc_runner_track_episodes", "wbc_sim_episode_stats_track", "wbc_tensor_spec", "wbc_policy_act_job", "wbc_sim_episode_stats_job", "wbc_side_job_run",
     "wbc_runner_track_state_floats", "wbc_asset_load", "wbc_asset_free", "wbc_asset_dof_count", "wbc_asset_rigid_body_count", "wbc_asset_dof_name",
-    "wbc_asset_rigid_body_name", "wbc_asset_dof_properties", "wbc_asset_model", "wbc_asset_task_cfg", "wbc_asset_curriculum"]
+    "wbc_asset_rigid_body_name", "wbc_asset_dof_properties", "wbc_asset_model", "wbc_asset_task_cfg", "wbc_asset_curriculum",
+    "wbc_asset_opts_default", "wbc_asset_load_urdf", "wbc_asset_dof_properties_ex", "wbc_asset_find_rigid_body", "wbc_asset_find_dof",
+    "wbc_asset_force_sensor_bodies"]
 
 
 def check(rc: int, what: str = "") -> None:
