@@ -77,7 +77,7 @@ struct TrainSmem {
   __attribute__((aligned(8))) float w_c2[H_C3][H_C2 * 2 + 2];
   float w_lin[H_OUT][H_C1];
   float b_enc[H_C1], b_c1[H_C2], b_c2[H_C3], b_lin[H_OUT];
-  long long ridx[G_ROWS];               // gathered row of obs / target, -1 past the end of the minibatch
+  long long ridx[G_ROWS];               // gathered row of obs / target; past the end of the minibatch ~(the minibatch's last row): negative, and still a row idx names
   // conv1 / conv2 weight gradients of the whole launch (every element owned by one lane of one wave: plain read-add-write per group;
   // as register tiles they were 20 more VGPRs held across the forward pass, which sits at the 256-register limit)
   float gW1[H_C2][4][H_C1];             // [co][tap][ci]
@@ -123,7 +123,7 @@ hist_train_kernel(HistParams P, const float* __restrict__ obs, const float* __re
 #pragma unroll 1
   for (int group = blockIdx.x; group < ngroups; group += gridDim.x) {
     const int row0 = group * G_ROWS;
-    if (tid < G_ROWS) s.ridx[tid] = (row0 + tid < rows) ? idx[row0 + tid] : -1;
+    if (tid < G_ROWS) s.ridx[tid] = (row0 + tid < rows) ? idx[row0 + tid] : ~idx[rows - 1];
     int opaque = 0;
     asm volatile("" : "+v"(opaque));                    // keeps the weight fetches inside the loop (no hoisting)
     int tl = tid;
@@ -428,7 +428,7 @@ hist_train_kernel(HistParams P, const float* __restrict__ obs, const float* __re
         for (int i = 0; i < CH; ++i) {
           const int q = 4 * (c0 + i) + g, rr = q / H_T, t = q - rr * H_T;
           const long long gi = s.ridx[rr];
-          const float* xr = obs + (size_t)(gi < 0 ? 0 : gi) * H_OBS + H_OFF + t * H_NP;
+          const float* xr = obs + (size_t)(gi < 0 ? ~gi : gi) * H_OBS + H_OFF + t * H_NP;   // (a padding row's dz1 is 0: it must meet a finite x, so a row of the minibatch, not row 0 of obs)
           bxv[i] = xr[jt0 * 16 + p];
           b4v[i] = (third && b4ok) ? xr[64 + p] : 0.f;
         }

@@ -1,10 +1,13 @@
 """Pins tests/learner_reference.py (the float64 restatements the GPU learner-kernel tests compare against) to the modules
 and optimiser it restates, on the CPU: the history and privileged encoders against the ActorCritic modules cast to
 float64, GAE against the reference's known-answer fixture and the CPU port's recurrence, clip + Adam against
-nn.utils.clip_grad_norm_ + torch.optim.Adam in float64."""
+nn.utils.clip_grad_norm_ + torch.optim.Adam in float64; policy_act, ppo_minibatch and hist_train against the ActorCritic
+modules cast to float64 and oracle/ppo_oracle.py evaluated in float64 (float64 autograd for the gradients), and the
+margins kink_free_batch promises at every minibatch size of the GPU tests' case list."""
 import copy
 import math
 import os
+import unittest.mock as mock
 
 import numpy as np
 import pytest
@@ -12,6 +15,7 @@ import torch
 
 import golden_procedure as gp
 import learner_reference as lr
+import ppo_oracle as po
 from wbc_amd.rsl_rl.modules import ActorCritic
 from wbc_amd.rsl_rl.storage import RolloutStorage
 
@@ -120,3 +124,142 @@ def test_clip_adam_without_clip_keeps_the_scaled_gradient():
     for max_norm in (0.0, -1.0):
         _, g_out, _, _, norm = lr.clip_adam(np.zeros(101), g, np.zeros(101), np.zeros(101), 1, 1e-3, max_norm, grad_scale=0.5)
         assert np.array_equal(g_out, 0.5 * g) and norm == pytest.approx(0.5 * math.sqrt((g * g).sum()), rel=1e-15)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# policy_act, ppo_minibatch, hist_train, kink_free_batch
+@pytest.fixture(scope="module")
+def pol64():
+    """The policy of test_fused_act_matches_torch_modules (initialisation + 0.05 N(0, 1), std in [0.3, 1.3]: no zero bias)."""
+    torch.manual_seed(3)
+    ac = ActorCritic(76, 76, 18, **gp.POLICY_KW)
+    with torch.no_grad():
+        for p in ac.parameters():
+            p.add_(0.05 * torch.randn_like(p))
+        ac.std.copy_(0.3 + torch.rand_like(ac.std))
+    ac = ac.double()
+    w, std = lr.policy_weights(ac)
+    return dict(ac=ac, w=w, std=std, sd={k: v.detach() for k, v in ac.state_dict().items()})
+
+
+def _obs(rows, seed, scale=1.0):
+    return scale * torch.randn(rows, 860, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+
+
+@pytest.mark.parametrize("scale,with_eps,student", [(1.0, True, False), (3.0, True, False), (1.0, False, False), (1.0, True, True)])
+def test_policy_act_matches_the_modules_and_the_oracle(pol64, scale, with_eps, student):
+    ac, w, std, sd = pol64["ac"], pol64["w"], pol64["std"], pol64["sd"]
+    obs = _obs(257, 5, scale)
+    eps = torch.randn(257, 18, generator=torch.Generator().manual_seed(6), dtype=torch.float64) if with_eps else None
+    with torch.no_grad():
+        latent = ac.actor.infer_hist_latent(obs) if student else None
+        (mean, actions, logp, values), E = lr.policy_act(w, std, obs, eps, latent=latent)
+        ac.update_distribution(obs, student)
+        m_mod, v_mod = ac.action_mean, ac.evaluate(obs)
+        a_mod = m_mod + ac.std * eps if with_eps else m_mod
+        lp_mod = ac.get_actions_log_prob(a_mod)
+        m_or, v_or = po.actor_mean(sd, obs, student), po.critic_value(sd, obs)
+        lp_or = po.log_prob2(m_or, m_or * 0. + sd["std"], a_mod)
+    for got, mod, orc in ((mean, m_mod, m_or), (values, v_mod, v_or), (logp, lp_mod, lp_or), (actions, a_mod, a_mod)):
+        assert got.dtype == torch.float64 and got.shape == mod.shape
+        assert (got - mod).abs().max().item() <= 1e-12 * (1 + mod.abs().max().item())
+        assert (got - orc).abs().max().item() <= 1e-12 * (1 + orc.abs().max().item())
+    if not with_eps:
+        assert torch.equal(actions, mean)
+    assert mean.abs().max().item() <= 1.0 and (scale < 3 or mean.abs().max().item() > 0.99)       # the 3 x case reaches tanh's saturation
+    # E is the first-order float32 bound up to its factor: with fan-in + 2 = 130 in front it holds for ANY evaluation
+    # order, so the float32 modules must satisfy it. (It is a worst-case scale: |W| row sums of ~8 per layer compound to
+    # ~1e-3 at the outputs, a thousand times the error a float32 pass actually makes; the GPU tests use it with a measured factor.)
+    ac32 = copy.deepcopy(ac).float()
+    with torch.no_grad():
+        o32 = obs.float()
+        ac32.update_distribution(o32, student)
+        m32, v32 = ac32.action_mean, ac32.evaluate(o32)
+        a32 = m32 + ac32.std * eps.float() if with_eps else m32
+        lp32 = ac32.get_actions_log_prob(a32)
+        (mean, actions, logp, values), E = lr.policy_act(*lr.policy_weights(ac32), o32, eps.float() if with_eps else None,
+                                                         latent=ac32.actor.infer_hist_latent(o32) if student else None)
+    for got, ref, e in zip((m32, a32, lp32, v32), (mean, actions, logp, values), E):
+        assert ((got.double() - ref).abs() <= 130 * e).all()
+        assert 0 < e.min().item() and e.max().item() < 0.1
+
+
+def _poisoned(obs, fields, TN, seed):
+    """The rows scattered to random places of TN-row tensors whose other rows are NaN; returns (batch, idx)."""
+    B = obs.shape[0]
+    idx = torch.randperm(TN, generator=torch.Generator().manual_seed(seed))[:B]
+    out = {}
+    for k, v in dict(fields, obs=obs).items():
+        full = torch.full((TN,) + tuple(v.shape[1:]), float("nan"), dtype=v.dtype)
+        full[idx] = v
+        out[k] = full
+    return out, idx
+
+
+PPO_OPTS = dict(clip=0.2, value_coef=1.0, mixing=0.5, roa_coef=0.1, use_clipped_value_loss=True)
+
+
+@pytest.mark.parametrize("B,change", [(300, {}), (1, {}), (300, {"use_clipped_value_loss": False}), (300, {"mixing": 0.0}), (300, {"roa_coef": 0.0}),
+                                      (300, {"value_coef": 0.5, "mixing": 1.0})])
+def test_ppo_minibatch_matches_float64_autograd_over_the_modules(pol64, B, change):
+    ac, w, std = pol64["ac"], pol64["w"], pol64["std"]
+    obs = _obs(B, 20 + B)
+    fields, _ = lr.kink_free_batch(w, std, obs, seed=B)
+    batch, idx = _poisoned(obs.float(), fields, B + 41, 3)
+    opts = dict(PPO_OPTS, **change)
+    flat, S = lr.ppo_minibatch(w, std, batch, idx, **opts)
+    assert flat.dtype == S.dtype == torch.float64 and flat.shape == S.shape == (lr.policy_grad_floats(w),)
+    ref = lr.eager_ppo_grad(ac, {k: v.double() for k, v in batch.items()}, idx, **opts)
+    assert torch.isfinite(flat).all() and torch.isfinite(S).all()
+    assert ((flat - ref).abs() <= 1e-12 * S).all(), ((flat - ref).abs() / S.clamp_min(1e-300)).max().item()
+    assert (S >= flat.abs()).all()
+    assert (S[:-3] > 0).all() and flat[:-3].abs().max().item() > 1e-3        # every weight and bias receives a gradient
+    if not change and B > 1:                                                   # and the oracle's own loss function, default options
+        sd = {k: v.detach().clone().requires_grad_(True) for k, v in pol64["sd"].items()}
+        o = batch["obs"][idx].double()
+        # ppo_losses evaluates the history encoder itself: hand the reference that latent as the given one
+        with torch.no_grad():
+            batch["hist_latent"][idx] = po.hist_latent(sd, o).float()
+        flat, S = lr.ppo_minibatch(w, std, batch, idx, **opts)
+        b64 = {k: v[idx].double() for k, v in batch.items()}
+        with mock.patch.object(po, "hist_latent", lambda sd_, obs_: b64["hist_latent"]):
+            s_, v_, r_ = po.ppo_losses(sd, o, b64["actions"], b64["old_values"], b64["advantages"], b64["returns"], b64["old_logp"], 0.5, 0.2)
+        (s_ + v_ + 0.1 * r_).backward()
+        ref = torch.cat([sd[n + k].grad.reshape(-1) for n in lr.POLICY_LAYERS for k in (".weight", ".bias")] + [sd["std"].grad.reshape(-1)])
+        assert ((flat[:-3] - ref).abs() <= 1e-12 * S[:-3]).all()
+        sums = torch.stack([s_ * 2 * B, v_ * 2 * B, r_ * B]).detach()
+        assert ((flat[-3:] - sums).abs() <= 1e-12 * S[-3:]).all()
+
+
+@pytest.mark.parametrize("rows", [1, 25, 333])
+def test_hist_train_matches_float64_autograd_over_the_module(ac64, rows):
+    g = torch.Generator().manual_seed(rows)
+    TN = rows + 17
+    idx = torch.randperm(TN, generator=g)[:rows]
+    obs = torch.full((TN, 860), float("nan"))
+    target = torch.full((TN, 20), float("nan"))
+    obs[idx] = torch.randn(rows, 860, generator=g)
+    target[idx] = torch.randn(rows, 20, generator=g)
+    flat, S = lr.hist_train(lr.hist_weights(ac64), obs, target, idx)
+    ref = lr.eager_hist_grad(ac64, obs.double(), target.double(), idx)
+    assert flat.shape == S.shape == ref.shape and torch.isfinite(flat).all()
+    assert ((flat - ref).abs() <= 1e-12 * S).all()
+    assert (S >= flat.abs()).all() and (S > 0).all()
+    per_row = (target[idx].double() - lr.hist_latent(lr.hist_weights(ac64), obs[idx])).norm(p=2, dim=1)
+    assert per_row.min().item() >= 0.1                                          # away from the norm's kink at 0
+
+
+# the minibatch sizes of tests/test_gpu_policy_ppo_fp64.py
+@pytest.mark.parametrize("B", [1, 15, 16, 17, 33, 1000, 12288, 12289, 40960])
+def test_kink_free_batch_keeps_its_margins(pol64, B):
+    """kink_free_batch asserts its margins itself; here also that they are the ones its construction gives (ratio bands
+    end 1e-2 from the clip, |v - v_old| 0.11 or 0.10 from it, |l1 - l2| >= 0.1 x 0.1 on clipped rows), far above the
+    ~1e-5 a float32 forward pass can move these quantities, and that the fields are float32."""
+    obs = _obs(B, B)
+    fields, m = lr.kink_free_batch(pol64["w"], pol64["std"], obs, seed=B)
+    assert all(v.dtype == torch.float32 and v.shape[0] == B and torch.isfinite(v).all() for v in fields.values())
+    assert m["ratio"] >= 9.9e-3 and m["value_clip"] >= 0.099 and m["l1_l2"] >= 9.9e-3 and m["latent"] >= 1.0
+    if B >= 1000:
+        sh = m["shares"]
+        assert abs(sh["clipped"] - 0.5) < 0.05 and min(sh["ratio_low"], sh["ratio_in"], sh["ratio_high"]) > 0.3
+        assert min(sh["l1_gt_l2"], sh["l1_lt_l2"]) > 0.2
