@@ -424,6 +424,33 @@ extern "C" __global__ void __launch_bounds__(64) wbc_body_dynamics_kernel(BodyCo
 
 extern "C" int wbc_sim_internal_fail(int code, const char* msg);
 
+// Fills B from the model. 0, or 1: a tree the kernels cannot walk, 2: a rigid body that rides on no moving body.
+static int body_const_fill(const wbc_model& m, BodyConst& B) {
+  for (int d = 0; d < WBC_NDOF; ++d) B.col_body[d] = -1;
+  for (int b = 0; b < WBC_NB; ++b) {
+    B.parent[b] = m.parent[b]; B.axis[b] = m.axis[b]; B.dof[b] = m.dof[b]; B.mass[b] = m.mass[b];
+    for (int j = 0; j < 3; ++j) { B.joint_xyz[b][j] = m.joint_xyz[b][j]; B.com[b][j] = m.com[b][j]; }
+    for (int j = 0; j < 6; ++j) B.inertia[b][j] = m.inertia[b][j];
+    // the kernels walk at most WBC_MAX_DEPTH joints between a body and the root and index 32-bit ancestor masks
+    uint32_t anc = 1u << b;
+    int depth = 0;
+    for (int a = b; a > 0; a = m.parent[a]) {
+      if (m.parent[a] < 0 || m.parent[a] >= a || ++depth > WBC_MAX_DEPTH || m.axis[a] < 0 || m.axis[a] > 2 || m.dof[a] < 0 || m.dof[a] >= WBC_NDOF)
+        return 1;
+      anc |= 1u << m.parent[a];
+    }
+    B.anc[b] = anc;
+    if (b > 0) B.col_body[m.dof[b]] = b;
+  }
+  for (int r = 0; r < WBC_NRB; ++r) {
+    if (m.rb_body[r] < 0 || m.rb_body[r] >= WBC_NB) return 2;
+    B.rb_body[r] = m.rb_body[r];
+    for (int j = 0; j < 3; ++j) B.rb_offset[r][j] = m.rb_offset[r][j];
+  }
+  B.gripper_body = m.gripper_body;
+  return 0;
+}
+
 // Outputs (device, caller-owned, 16-byte aligned, either may be NULL): jac f32 [N,27,6,26], mm f32 [N,26,26] (include/wbc_sim.h).
 extern "C" int wbc_sim_body_dynamics(wbc_sim* s, float* jac, float* mm, void* stream) {
   StreamDeviceGuard sdg(stream);
@@ -432,32 +459,210 @@ extern "C" int wbc_sim_body_dynamics(wbc_sim* s, float* jac, float* mm, void* st
   if (!jac && !mm) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: jac and mm are both NULL");
   if (((uintptr_t)jac | (uintptr_t)mm) & 15u) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: jac / mm must be 16-byte aligned");
   if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: no sim state");
-  const wbc_model& m = hc->model;
   BodyConst B;
-  for (int d = 0; d < WBC_NDOF; ++d) B.col_body[d] = -1;
-  for (int b = 0; b < WBC_NB; ++b) {
-    B.parent[b] = m.parent[b]; B.axis[b] = m.axis[b]; B.dof[b] = m.dof[b]; B.mass[b] = m.mass[b];
-    for (int j = 0; j < 3; ++j) { B.joint_xyz[b][j] = m.joint_xyz[b][j]; B.com[b][j] = m.com[b][j]; }
-    for (int j = 0; j < 6; ++j) B.inertia[b][j] = m.inertia[b][j];
-    // the kernel walks at most WBC_MAX_DEPTH joints from a body to the root and indexes 32-bit ancestor masks
-    uint32_t anc = 1u << b;
-    int depth = 0;
-    for (int a = b; a > 0; a = m.parent[a]) {
-      if (m.parent[a] < 0 || m.parent[a] >= a || ++depth > WBC_MAX_DEPTH || m.axis[a] < 0 || m.axis[a] > 2 || m.dof[a] < 0 || m.dof[a] >= WBC_NDOF)
-        return wbc_sim_internal_fail(-3, "wbc_sim_body_dynamics: the model's tree is not one the kernel walks");
-      anc |= 1u << m.parent[a];
-    }
-    B.anc[b] = anc;
-    if (b > 0) B.col_body[m.dof[b]] = b;
+  switch (body_const_fill(hc->model, B)) {
+    case 1: return wbc_sim_internal_fail(-3, "wbc_sim_body_dynamics: the model's tree is not one the kernel walks");
+    case 2: return wbc_sim_internal_fail(-3, "wbc_sim_body_dynamics: bad rb_body");
   }
-  for (int r = 0; r < WBC_NRB; ++r) {
-    if (m.rb_body[r] < 0 || m.rb_body[r] >= WBC_NB) return wbc_sim_internal_fail(-3, "wbc_sim_body_dynamics: bad rb_body");
-    B.rb_body[r] = m.rb_body[r];
-    for (int j = 0; j < 3; ++j) B.rb_offset[r][j] = m.rb_offset[r][j];
-  }
-  B.gripper_body = m.gripper_body;
   // the J chunk is dynamic LDS: a mass-matrix-only refresh keeps the small footprint (twice the resident envs per CU)
   const size_t jbytes = jac ? BD_JCHUNK * BD_JROW * sizeof(float) : 0;
   hipLaunchKernelGGL(wbc_body_dynamics_kernel, dim3(n), dim3(64), jbytes, (hipStream_t)stream, B, root, dofs, bp, n, jac, mm);
   return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_body_dynamics: launch failed");
+}
+
+// ---- whole-body inverse dynamics: tau = M nudot + C nu + g in the coordinates of wbc_sim_body_dynamics (include/wbc_sim.h) ---------
+// Recursive Newton-Euler with every spatial vector about F's origin in F's axes, so neither pass needs a parent-child transform.
+// Two envs per 64-lane workgroup, one per 32-lane half (19 bodies / 26 columns fit in 32 lanes); two phases, ONE LDS hand-over:
+//  1) lane b = moving body b walks its ancestor path from the root DOWN (IdConst::path) and carries in registers the frame (E, p),
+//     the spatial velocity and the spatial acceleration. The depth-sequential velocity-product term v x S qd is thereby a
+//     loop-carried register dependence of at most WBC_MAX_DEPTH steps (each lane redoes its ancestors' joints) instead of an LDS
+//     round trip per tree level. Then the body's force m a_com and its moment about F's origin (from I_b alpha + omega x I_b omega
+//     about the centre of mass, in body axes) go to LDS with (m, m c), and with the torque of the body's own force and weight
+//     about its OWN joint, formed in body axes.
+//  2) lane c = generalised coordinate c sums the forces of the subtree it moves (ancestor masks; a joint's own body through its
+//     own-joint torque) and projects on S_c; the root columns carry T = diag(R^T, R^T, 1) as in the mass matrix. g(q) comes from
+//     the subtree's (m, m c) and is added at the end (equivalent to a_0 -= g, more accurate: see phase 2).
+// The root position is never read.
+#ifndef ID_EPW
+#define ID_EPW 2                                // envs per workgroup: 2, or 1 (-DID_EPW=1, the variant DESIGN.md compares with)
+#endif
+static_assert(ID_EPW == 1 || ID_EPW == 2, "one env per 64 lanes or one per 32-lane half");
+struct IdConst {
+  int32_t axis[WBC_NB], dof[WBC_NB];
+  int32_t path[WBC_NB][WBC_MAX_DEPTH];         // moving bodies on the way root -> b (root excluded, b last), padded with -1
+  uint32_t anc[WBC_NB];                        // as BodyConst::anc
+  int32_t col_body[WBC_NDOF];
+  int32_t gripper_body;
+  float joint_xyz[WBC_NB][3], mass[WBC_NB], com[WBC_NB][3], inertia[WBC_NB][6];
+  float gravity[3];
+};
+
+extern "C" __global__ void __launch_bounds__(64) wbc_inverse_dynamics_kernel(IdConst K, const float* __restrict__ root,
+                                                                            const float* __restrict__ dofs,
+                                                                            const float* __restrict__ body_params,
+                                                                            const float* __restrict__ nudot, int n,
+                                                                            float* __restrict__ tau, float* __restrict__ grav) {
+  __shared__ __align__(16) float sF[ID_EPW][WBC_NB][12];   // per body: force (moment about F's origin; force) in F at 0..5, own-joint torques at 6, 7, (m, m c) at 8..11
+  __shared__ float sS[ID_EPW][WBC_NB][6];          // the body's joint in F: axis, origin
+  const int half = ID_EPW == 2 ? threadIdx.x >> 5 : 0, lane = ID_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
+  const int env = blockIdx.x * ID_EPW + half;
+  const bool live = env < n, dyn = tau != nullptr;
+  const size_t e = live ? env : n - 1;             // the idle half of the last workgroup recomputes the last env and stores nothing
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+  const f3 gF = matT_mul(R, mk3(K.gravity[0], K.gravity[1], K.gravity[2]));
+
+  if (lane < WBC_NB) {
+    const int b = lane;
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    f3 p = mk3(0.f, 0.f, 0.f), Sw = p, Sv = p;
+    // spatial velocity (vw; vv) and acceleration (aw; av) of the root in F. nudot[0:3] is the CLASSICAL acceleration of the
+    // root origin: a spatial acceleration's linear part is R^T a - omega x v.
+    f3 vw = p, vv = p, aw = p, av = p;
+    if (dyn) {
+      vv = matT_mul(R, ld3(root + e * 26 + 7));
+      vw = matT_mul(R, ld3(root + e * 26 + 10));
+      if (nudot) { av = matT_mul(R, ld3(nudot + e * BD_NCOL)); aw = matT_mul(R, ld3(nudot + e * BD_NCOL + 3)); }
+      av = av - cross(vw, vv);
+    }
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
+      const int a = K.path[b][k];
+      if (a < 0) break;
+      const int ax = K.axis[a], d = K.dof[a];
+      const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
+      float s, c;
+      sincosf(dofs[e * (2 * WBC_NDOF) + 2 * d], &s, &c);
+      const float t = 1.f - c;
+      const float Q[9] = {c + t * ux * ux, t * ux * uy - s * uz, t * ux * uz + s * uy,
+                          t * uy * ux + s * uz, c + t * uy * uy, t * uy * uz - s * ux,
+                          t * uz * ux - s * uy, t * uz * uy + s * ux, c + t * uz * uz};
+      p = p + mat_mul(E, mk3(K.joint_xyz[a][0], K.joint_xyz[a][1], K.joint_xyz[a][2]));     // (E, p) <- (E Rot_a, p + E xyz_a)
+      float En[9];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) En[r * 3 + j] = E[r * 3] * Q[j] + E[r * 3 + 1] * Q[3 + j] + E[r * 3 + 2] * Q[6 + j];
+#pragma unroll
+      for (int j = 0; j < 9; ++j) E[j] = En[j];
+      Sw = mat_mul(E, mk3(ux, uy, uz));
+      Sv = cross(p, Sw);
+      if (dyn) {
+        const float qd = dofs[e * (2 * WBC_NDOF) + 2 * d + 1], qdd = nudot ? nudot[e * BD_NCOL + 6 + d] : 0.f;
+        const f3 jw = Sw * qd, jv = Sv * qd;                   // a += S qdd + v x (S qd), then v += S qd
+        aw = aw + Sw * qdd + cross(vw, jw);
+        av = av + Sv * qdd + cross(vw, jv) + cross(vv, jw);
+        vw = vw + jw; vv = vv + jv;
+      }
+    }
+    // spatial inertia about F's origin: the per-env root composite and gripper body (body_params), the model's otherwise
+    float m = K.mass[b], com[3] = {K.com[b][0], K.com[b][1], K.com[b][2]}, I6[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) I6[j] = K.inertia[b][j];
+    const int slot = b == 0 ? 0 : (b == K.gripper_body ? 10 : -1);
+    if (slot >= 0) {
+      const float* bp = body_params + e * 20 + slot;
+      m = bp[0];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) I6[j] = bp[4 + j];
+    }
+    // The body's own joint sees the body's own force through the lever (com x axis) in BODY axes, where the axis is a unit vector
+    // and the lever is the model's: a force that (nearly) passes through the axis then yields its small torque to fp32 accuracy,
+    // which the difference of two moments about the far base origin would not. Descendants reach the joint through F (phase 2).
+    const int axb = K.axis[b];                                 // -1 for the root: no joint axis
+    const f3 cm = mk3(com[0], com[1], com[2]), ub = mk3(axb == 0 ? 1.f : 0.f, axb == 1 ? 1.f : 0.f, axb == 2 ? 1.f : 0.f);
+    const f3 C = p + mat_mul(E, cm), h = m * C, lev = cross(cm, ub);
+    float* o = sF[half][b];
+    if (dyn) {
+      // classical acceleration of the centre of mass from the spatial one, force m a_com in F, moment about the centre of mass in
+      // body axes (I_b alpha + omega x I_b omega with the model's inertia as it stands)
+      const f3 acom = av + cross(aw, C) + cross(vw, vv + cross(vw, C)), fl = m * acom;
+      const f3 wl = matT_mul(E, vw), al = matT_mul(E, aw);
+      const float Ib[9] = {I6[0], I6[3], I6[4], I6[3], I6[1], I6[5], I6[4], I6[5], I6[2]};
+      const f3 ncl = mat_mul(Ib, al) + cross(wl, mat_mul(Ib, wl));
+      st3(o, mat_mul(E, ncl) + cross(C, fl)); st3(o + 3, fl);  // about F's origin, in F: what the ancestors' joints see
+      o[6] = dot(ub, ncl) - dot(lev, matT_mul(E, fl));         // u . (n_c + com x f) = u . n_c - (com x u) . f, body axes
+    }
+    o[7] = m * dot(matT_mul(E, gF), lev);                      // the same for the body's weight -m g: m g . (com x u)
+    o[8] = m; st3(o + 9, h);
+    st3(sS[half][b], Sw); st3(sS[half][b] + 3, p);
+  }
+  __syncthreads();
+
+  if (lane < BD_NCOL) {
+    const int c = lane, b = c < 6 ? 0 : K.col_body[c - 6], bb = b < 0 ? 0 : b;
+    const int j = c < 3 ? c : c - 3;
+    float S[6];                                                // motion subspace (omega; v at F's origin) in F
+    f3 po = mk3(0.f, 0.f, 0.f);                                // joint origin in F
+    if (c < 6) {                                               // world-frame root coordinates: rows of R
+      const f3 row = matT_mul(R, mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f));
+      const bool lin = c < 3;
+      S[0] = lin ? 0.f : row.x; S[1] = lin ? 0.f : row.y; S[2] = lin ? 0.f : row.z;
+      S[3] = lin ? row.x : 0.f; S[4] = lin ? row.y : 0.f; S[5] = lin ? row.z : 0.f;
+    } else {
+      const f3 a = ld3(sS[half][bb]);
+      po = ld3(sS[half][bb] + 3);
+      const f3 l = cross(po, a);
+      S[0] = a.x; S[1] = a.y; S[2] = a.z; S[3] = l.x; S[4] = l.y; S[5] = l.z;
+    }
+    float acc[12];
+#pragma unroll
+    for (int j = 0; j < 12; ++j) acc[j] = 0.f;
+    for (int d = 0; d < WBC_NB; ++d) {                         // subtree sums: every force is already about F's origin
+      const bool in = ((K.anc[d] >> bb) & 1u) && (c < 6 || d != bb);   // a joint's own body comes in through slots 6, 7
+      const float4* f4 = reinterpret_cast<const float4*>(sF[half][d]);
+      if (dyn) {
+        const float4 u = f4[0];
+        const float2 w = *reinterpret_cast<const float2*>(sF[half][d] + 4);
+        acc[0] += in ? u.x : 0.f; acc[1] += in ? u.y : 0.f; acc[2] += in ? u.z : 0.f; acc[3] += in ? u.w : 0.f;
+        acc[4] += in ? w.x : 0.f; acc[5] += in ? w.y : 0.f;
+      }
+      const float4 u = f4[2];
+      acc[8] += in ? u.x : 0.f; acc[9] += in ? u.y : 0.f; acc[10] += in ? u.z : 0.f; acc[11] += in ? u.w : 0.f;
+    }
+    // g(q) from the subtree's (m, m c): the net force is -m g in WORLD axes as it stands, the root moment is formed in world axes
+    // and a joint's torque takes the lever about the joint's own origin, so that the weight (the largest term of most rows) meets
+    // no rotation there and back and no moment about the far base origin. tau = (Newton-Euler without gravity) + g(q).
+    float gv = 0.f;
+    if (b >= 0) {
+      const f3 gw = mk3(K.gravity[0], K.gravity[1], K.gravity[2]), hs = mk3(acc[9], acc[10], acc[11]);
+      if (c < 3) gv = -acc[8] * (j == 0 ? gw.x : j == 1 ? gw.y : gw.z);
+      else if (c < 6) { const f3 nw = cross(gw, mat_mul(R, hs)); gv = j == 0 ? nw.x : j == 1 ? nw.y : nw.z; }
+      else gv = sF[half][bb][7] + dot(mk3(S[0], S[1], S[2]), cross(gF, hs - acc[8] * po));
+    }
+    if (live) {
+      if (tau) tau[e * BD_NCOL + c] = b >= 0 ? ((c < 6 ? 0.f : sF[half][bb][6]) + dot6(S, acc)) + gv : 0.f;
+      if (grav) grav[e * BD_NCOL + c] = gv;
+    }
+  }
+}
+
+// nudot (device f32 [N,26] or NULL = zeros), tau / grav (device f32 [N,26], caller-owned, either may be NULL): include/wbc_sim.h.
+extern "C" int wbc_sim_inverse_dynamics(wbc_sim* s, const float* nudot, float* tau, float* grav, void* stream) {
+  StreamDeviceGuard sdg(stream);
+  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: sim is NULL");
+  if (!tau && !grav) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: tau and grav are both NULL");
+  if (((uintptr_t)nudot | (uintptr_t)tau | (uintptr_t)grav) & 3u)
+    return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: nudot / tau / grav must be 4-byte aligned");
+  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: no sim state");
+  if (n <= 0) return 0;
+  BodyConst B;
+  if (body_const_fill(hc->model, B) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_inverse_dynamics: the model's tree is not one the kernel walks");
+  IdConst K;
+  for (int d = 0; d < WBC_NDOF; ++d) K.col_body[d] = B.col_body[d];
+  for (int b = 0; b < WBC_NB; ++b) {
+    K.axis[b] = B.axis[b]; K.dof[b] = B.dof[b]; K.anc[b] = B.anc[b]; K.mass[b] = B.mass[b];
+    for (int j = 0; j < 3; ++j) { K.joint_xyz[b][j] = B.joint_xyz[b][j]; K.com[b][j] = B.com[b][j]; }
+    for (int j = 0; j < 6; ++j) K.inertia[b][j] = B.inertia[b][j];
+    int up[WBC_MAX_DEPTH], depth = 0;                          // body_const_fill bounded the depth
+    for (int a = b; a > 0; a = B.parent[a]) up[depth++] = a;
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k) K.path[b][k] = k < depth ? up[depth - 1 - k] : -1;
+  }
+  K.gripper_body = B.gripper_body;
+  for (int j = 0; j < 3; ++j) K.gravity[j] = hc->cfg.gravity[j];
+  hipLaunchKernelGGL(wbc_inverse_dynamics_kernel, dim3((n + ID_EPW - 1) / ID_EPW), dim3(64), 0, (hipStream_t)stream, K, root, dofs, bp, nudot, n,
+                     tau, grav);
+  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_inverse_dynamics: launch failed");
 }

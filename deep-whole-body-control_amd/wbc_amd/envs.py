@@ -479,6 +479,28 @@ class WidowGo1(LeggedRobot):
     def refresh_mass_matrix_tensors(self):
         self.sim.refresh_mass_matrix_tensors()
 
+    # ---- whole-body inverse dynamics (no counterpart in the reference, whose get_g_torques covers nine arm links' weight only) ----
+    @property
+    def bias_forces(self) -> torch.Tensor:
+        """f32 [N, 26], persistent: h = C(q, nu) nu + g(q) in the coordinates of mm_whole; follows refresh_bias_force_tensors()."""
+        return self.sim.acquire_bias_force_tensor()
+
+    def refresh_bias_force_tensors(self):
+        self.sim.refresh_bias_force_tensors()
+
+    def inverse_dynamics(self, nudot: torch.Tensor = None) -> torch.Tensor:
+        """A fresh f32 [N, 26] tau = M nudot + C nu + g of the current state (nudot None: h): rows 0:3 net external force, 3:6 net
+        external moment about the root origin (world axes), 6: joint torques (include/wbc_sim.h: wbc_sim_inverse_dynamics)."""
+        tau = torch.empty(self.num_envs, 6 + self.num_dofs, dtype=torch.float32, device=self.device)
+        self.sim.inverse_dynamics(nudot=nudot, tau=tau)
+        return tau
+
+    def gravity_forces(self) -> torch.Tensor:
+        """A fresh f32 [N, 26] g(q): what holds the current pose still against sim.gravity."""
+        grav = torch.empty(self.num_envs, 6 + self.num_dofs, dtype=torch.float32, device=self.device)
+        self.sim.inverse_dynamics(grav=grav)
+        return grav
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])

@@ -191,6 +191,30 @@ class WbcSim:
         """Recompute the acquired mass matrix in place from the current state and per-env body parameters."""
         self.body_dynamics(mm=self.acquire_mass_matrix_tensor())
 
+    # ---- whole-body inverse dynamics / bias forces: the h of M nudot + h = S^T tau + sum J_c^T f_c, same coordinates ----------
+    def acquire_bias_force_tensor(self) -> torch.Tensor:
+        """The persistent f32 [N, 26] bias vector h = C nu + g (include/wbc_sim.h: wbc_sim_inverse_dynamics with nudot = NULL).
+        The same tensor on every call; refresh_bias_force_tensors() fills it."""
+        if self.__dict__.get("_bias_force") is None:
+            self._bias_force = torch.zeros(self.num_envs, 6 + abi.NDOF, dtype=torch.float32, device=self.device)
+        return self._bias_force
+
+    def inverse_dynamics(self, nudot: Optional[torch.Tensor] = None, tau: Optional[torch.Tensor] = None,
+                         grav: Optional[torch.Tensor] = None) -> None:
+        """One wbc_sim_inverse_dynamics launch on the current stream into caller-owned [N, 26] buffers: tau = M nudot + C nu + g
+        (nudot None: zeros, i.e. tau = h) and / or grav = g(q); either output may be None, not both."""
+        shape = (self.num_envs, 6 + abi.NDOF)
+        for t in (nudot, tau, grav):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+        check(self.L.wbc_sim_inverse_dynamics(self.h, nudot.data_ptr() if nudot is not None else None,
+                                              tau.data_ptr() if tau is not None else None,
+                                              grav.data_ptr() if grav is not None else None, self._stream()), "wbc_sim_inverse_dynamics")
+
+    def refresh_bias_force_tensors(self) -> None:
+        """Recompute the acquired bias vector in place from the current state and per-env body parameters."""
+        self.inverse_dynamics(tau=self.acquire_bias_force_tensor())
+
     def episode_stats(self, scale: float, track_state: torch.Tensor = None, track_cap: int = 0) -> torch.Tensor:
         """Means over the envs that reset in the last step of their finished episode's reward sums [NREW] and metric
         sums [NMETRIC], times `scale`, as one fresh device tensor (WG:743-754 without a host sync). With `track_state`

@@ -614,6 +614,25 @@ int wbc_sim_arm_dynamics(wbc_sim* sim, const int* link_rb9, const float* link_ma
 #define WBC_NCOL (6 + WBC_NDOF)
 int wbc_sim_body_dynamics(wbc_sim* sim, float* jac, float* mm, void* stream);
 
+/* Whole-body inverse dynamics in the coordinates of wbc_sim_body_dynamics: the third term of the equations of motion
+ *     M(q) nudot + h(q, nu) = S^T tau_joint + sum J_c^T f_c ,     h = C(q, nu) nu + g(q) ,
+ * i.e. tau = M nudot + C nu + g, from the sim's current WBC_T_ROOT_STATES (orientation and nu[0:6]), WBC_T_DOF_STATE (q, qd),
+ * per-env WBC_T_BODY_PARAMS (root composite and gripper body, as wbc_sim_body_dynamics uses them) and all three components of
+ * wbc_task_cfg.gravity. One launch of a recursive Newton-Euler kernel.
+ * nudot  device f32 [N, 26] or NULL (= zeros): d/dt of the WORLD components of nu -- the classical linear acceleration of the root
+ *        origin, the angular acceleration of the root, the joint accelerations in simulator DoF order.
+ * tau    device f32 [N, 26] or NULL: rows 0:3 the net external force on the robot (world axes), rows 3:6 the net external moment
+ *        about the ROOT ORIGIN (world axes), rows 6: the joint torques, such that (q, nu, nudot) is the motion the rigid-body
+ *        dynamics produce. With nudot == NULL this is the bias vector h. tau(nudot) - tau(0) == mm @ nudot by definition.
+ * grav   device f32 [N, 26] or NULL: g(q) alone (tau at nu = 0, nudot = 0); h - g is the velocity-product term C nu.
+ * At least one of tau / grav is non-NULL; all three pointers need 4-byte alignment only.
+ * Locked fingers (DoFs 18, 19): their entries of nudot and of qd are ignored, their rows of tau / grav are exactly 0.
+ * The root POSITION is never read: the result is bit-identical under a translation of the robot.
+ * This is RIGID-BODY dynamics: wbc_task_cfg.joint_armature, the joint-limit stop torques and contacts are not part of it.
+ * -1 with a message in wbc_last_error() for a NULL sim, both outputs NULL or a misaligned pointer; -3 for a model whose tree the
+ * kernel cannot walk; -2 if the launch fails. Stream / device handling as wbc_sim_body_dynamics. */
+int wbc_sim_inverse_dynamics(wbc_sim* sim, const float* nudot, float* tau, float* grav, void* stream);
+
 /* extras["episode"] of reset_idx (widowGo1.py:743-754): out[0:WBC_NREW] = mean over the envs that reset in the last
  * step of their finished episode's reward sums, out[WBC_NREW:+WBC_NMETRIC] the same for the metric sums, both
  * times `scale` (1 / max_episode_length_s). `out`: device, WBC_NREW + WBC_NMETRIC floats. On a step in which no env reset
