@@ -21,9 +21,10 @@ NCOL = wb.NCOL
 GRAVITY = (0.0, 0.0, -9.81)
 
 
-def inverse_dynamics(model, root_pos, root_quat, q, nu, nudot=None, body_params=None, gravity=GRAVITY):
+def inverse_dynamics(model, root_pos, root_quat, q, nu, nudot=None, body_params=None, gravity=GRAVITY, forces=None):
     """(tau [26], mag [26]). mag = sum over bodies of |J_v|^T |F| + |J_w|^T |T|, the component-wise absolute values of the sum
-    that gives tau: the scale the rounding error of an fp32 evaluation is proportional to."""
+    that gives tau: the scale the rounding error of an fp32 evaluation is proportional to. forces: a list that receives every
+    body's inertia force F (world axes, at its centre of mass)."""
     q, nu = np.asarray(q, dtype=np.float64), np.asarray(nu, dtype=np.float64)
     nudot = np.zeros(NCOL) if nudot is None else np.asarray(nudot, dtype=np.float64)
     g = np.asarray(gravity, dtype=np.float64)
@@ -36,15 +37,17 @@ def inverse_dynamics(model, root_pos, root_quat, q, nu, nudot=None, body_params=
         ax = R[b][:, model.axis[b]]
         r = p[b] - p[par]
         om[b] = om[par] + ax * nu[6 + d]
-        al[b] = al[par] + ax * nudot[6 + d] + np.cross(om[par], ax * nu[6 + d])
-        acc[b] = acc[par] + np.cross(al[par], r) + np.cross(om[par], np.cross(om[par], r))
+        al[b] = al[par] + ax * nudot[6 + d] + wb.cross3(om[par], ax * nu[6 + d])
+        acc[b] = acc[par] + wb.cross3(al[par], r) + wb.cross3(om[par], wb.cross3(om[par], r))
     tau, mag = np.zeros(NCOL), np.zeros(NCOL)
     for b, (m, com, I6) in enumerate(wb.body_inertias(model, body_params)):
         rc = R[b] @ com
-        a_com = acc[b] + np.cross(al[b], rc) + np.cross(om[b], np.cross(om[b], rc))
+        a_com = acc[b] + wb.cross3(al[b], rc) + wb.cross3(om[b], wb.cross3(om[b], rc))
         Iw = R[b] @ wb._sym(I6) @ R[b].T
         F = m * (a_com - g)
-        T = Iw @ al[b] + np.cross(om[b], Iw @ om[b])
+        T = Iw @ al[b] + wb.cross3(om[b], Iw @ om[b])
+        if forces is not None:
+            forces.append(F)
         J = wb.point_jacobian(model, R, p, b, p[b] + rc)
         tau += J[0:3].T @ F + J[3:6].T @ T
         mag += np.abs(J[0:3]).T @ np.abs(F) + np.abs(J[3:6]).T @ np.abs(T)

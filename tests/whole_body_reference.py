@@ -49,21 +49,26 @@ def dof_body(model):
     return out
 
 
+def cross3(a, b):
+    """a x b of two 3-vectors (np.cross spends most of its time on axis bookkeeping; the references call this a few hundred times
+    per state)."""
+    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]])
+
+
 def point_jacobian(model, R, p, body, point):
     """[6, 26] Jacobian (linear velocity of the world point `point` riding on moving body `body`; the body's angular velocity)."""
     J = np.zeros((6, NCOL))
     J[0:3, 0:3] = np.eye(3)
     d = point - p[0]
-    for j in range(3):
-        J[0:3, 3 + j] = np.cross(np.eye(3)[j], d)
-        J[3 + j, 3 + j] = 1.0
-    anc = ancestors(model, body)
-    for dof, b in enumerate(dof_body(model)):
-        if b < 0 or b not in anc:
-            continue
+    J[0:3, 3:6] = [[0.0, d[2], -d[1]], [-d[2], 0.0, d[0]], [d[1], -d[0], 0.0]]        # column j: e_j x d
+    J[3:6, 3:6] = np.eye(3)
+    b = body
+    while b > 0:                                                                       # the joints on the path root..body
         a = R[b][:, model.axis[b]]
-        J[0:3, 6 + dof] = np.cross(a, point - p[b])
+        dof = model.body_dof[b]
+        J[0:3, 6 + dof] = cross3(a, point - p[b])
         J[3:6, 6 + dof] = a
+        b = model.parent[b]
     return J
 
 
