@@ -6,6 +6,8 @@
 // in get_arm_ee_control_torques (WG:1217-1242). Here they come from the same state tensors the step kernel keeps:
 // one thread per env walks the 6-joint arm chain (forward kinematics in the base frame F, composite spatial inertias
 // from the tip inwards, M_ij = S_i^T Ic_j S_j) -- an optional, once-per-step pre-pass (torque_supervision=False as shipped).
+#include <cstdio>
+
 #include "wbc_device.h"
 #include "wbc_stream_guard.h"
 
@@ -638,19 +640,10 @@ extern "C" __global__ void __launch_bounds__(64) wbc_inverse_dynamics_kernel(IdC
   }
 }
 
-// nudot (device f32 [N,26] or NULL = zeros), tau / grav (device f32 [N,26], caller-owned, either may be NULL): include/wbc_sim.h.
-extern "C" int wbc_sim_inverse_dynamics(wbc_sim* s, const float* nudot, float* tau, float* grav, void* stream) {
-  StreamDeviceGuard sdg(stream);
-  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: sim is NULL");
-  if (!tau && !grav) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: tau and grav are both NULL");
-  if (((uintptr_t)nudot | (uintptr_t)tau | (uintptr_t)grav) & 3u)
-    return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: nudot / tau / grav must be 4-byte aligned");
-  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: no sim state");
-  if (n <= 0) return 0;
+// Fills K from the model. 0, or 1: a tree the kernels cannot walk.
+static int id_const_fill(const DevConst* hc, IdConst& K) {
   BodyConst B;
-  if (body_const_fill(hc->model, B) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_inverse_dynamics: the model's tree is not one the kernel walks");
-  IdConst K;
+  if (body_const_fill(hc->model, B) != 0) return 1;
   for (int d = 0; d < WBC_NDOF; ++d) K.col_body[d] = B.col_body[d];
   for (int b = 0; b < WBC_NB; ++b) {
     K.axis[b] = B.axis[b]; K.dof[b] = B.dof[b]; K.anc[b] = B.anc[b]; K.mass[b] = B.mass[b];
@@ -662,7 +655,315 @@ extern "C" int wbc_sim_inverse_dynamics(wbc_sim* s, const float* nudot, float* t
   }
   K.gripper_body = B.gripper_body;
   for (int j = 0; j < 3; ++j) K.gravity[j] = hc->cfg.gravity[j];
+  return 0;
+}
+
+// nudot (device f32 [N,26] or NULL = zeros), tau / grav (device f32 [N,26], caller-owned, either may be NULL): include/wbc_sim.h.
+extern "C" int wbc_sim_inverse_dynamics(wbc_sim* s, const float* nudot, float* tau, float* grav, void* stream) {
+  StreamDeviceGuard sdg(stream);
+  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: sim is NULL");
+  if (!tau && !grav) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: tau and grav are both NULL");
+  if (((uintptr_t)nudot | (uintptr_t)tau | (uintptr_t)grav) & 3u)
+    return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: nudot / tau / grav must be 4-byte aligned");
+  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: no sim state");
+  if (n <= 0) return 0;
+  IdConst K;
+  if (id_const_fill(hc, K) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_inverse_dynamics: the model's tree is not one the kernel walks");
   hipLaunchKernelGGL(wbc_inverse_dynamics_kernel, dim3((n + ID_EPW - 1) / ID_EPW), dim3(64), 0, (hipStream_t)stream, K, root, dofs, bp, nudot, n,
                      tau, grav);
   return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_inverse_dynamics: launch failed");
+}
+
+// ---- mass-matrix solves: out = M^-1 rhs in the coordinates of wbc_sim_body_dynamics (include/wbc_sim.h) ------------------------------
+// M never leaves the launch. Live coordinates s (the 24 that are not locked fingers) are ordered root 0..5, then chain by chain from
+// the root outwards, so every coordinate's ancestors precede it: the six root coordinates (a "chain" of six) and the joints between the
+// root and its own. Row s of M is kept in LDS as [the root columns | its chain's columns up to itself]: position u of a row is the same
+// coordinate in the rows of all its ancestors, and nothing outside these rows is ever non-zero -- Featherstone's L^T D L factorisation
+// (leaves first) has no fill-in. MS_EPW envs per 64-lane workgroup, one per lane group:
+//  1) lane b = moving body b: forward kinematics root -> b in registers (as wbc_inverse_dynamics_kernel), centre of mass and
+//     rotational inertia about it in F to LDS;
+//  2) lane s = coordinate s: composite of the subtree it moves ABOUT ITS OWN JOINT ORIGIN (the root: F's origin), so that the light
+//     wrist joints' entries are not the difference of two moments about the far base origin, and F_s = Ic_s S_s;
+//  3) M[s][i] = S_i . F_s for every ancestor-or-self i of s, the force moved to i's origin (a chain-local lever), one entry per lane;
+//  4) elimination k = last .. first: the ancestors' rows lose row_k^T row_k / D_k, one entry pair per lane, one LDS round per k;
+//  5) lane r = right-hand side r: x = L^-1 D^-1 L^-T b with the root's six values and one chain's values in registers.
+// A single-wavefront workgroup: the __syncthreads() below order the LDS traffic and cost no barrier instruction.
+// The root position is never read.
+#ifndef MS_EPW
+#define MS_EPW 2                                // envs per workgroup: 2, or 1 (-DMS_EPW=1, the variant DESIGN.md compares with)
+#endif
+static_assert(MS_EPW == 1 || MS_EPW == 2, "one env per 64 lanes or one per 32-lane half");
+#define MS_NS (6 + WBC_NB - 1)                  // live coordinates at most: the root's six and one per joint
+#define MS_W (6 + WBC_MAX_DEPTH)                // a row: the root columns, the chain's, the diagonal at position (number of ancestors)
+#define MS_LPE (64 / MS_EPW)                    // lanes per env
+#define MS_BT 16                                // floats per body / per coordinate in the tables of phases 1-3
+#define MS_TN ((WBC_NB + MS_NS) * MS_BT)        // those tables; the solve's hand-over between its two passes reuses them
+static_assert(WBC_SOLVE_MAX_RHS <= MS_LPE && (MS_NS - 6) * WBC_SOLVE_MAX_RHS <= MS_TN && WBC_NB <= MS_LPE && MS_NS <= MS_LPE, "lanes / LDS reuse");
+struct MsConst {
+  IdConst K;                                   // tree walk and inertias (gravity unused)
+  int32_t ns;                                  // live coordinates
+  int32_t co_body[MS_NS], co_col[MS_NS];       // moving body and column (of 26) of coordinate s
+  int32_t co_na[MS_NS], co_anc0[MS_NS];        // number of ancestors; the coordinate at row position 6 (its chain's first joint)
+  int32_t nchain, ch_base[WBC_NCHAIN], ch_len[WBC_NCHAIN];
+  float arm[MS_NS];                            // wbc_task_cfg.joint_armature of coordinate s (0 for the root's)
+};
+
+extern "C" __global__ void __launch_bounds__(64) wbc_mass_solve_kernel(MsConst C, const float* __restrict__ root,
+                                                                      const float* __restrict__ dofs,
+                                                                      const float* __restrict__ body_params,
+                                                                      const float* __restrict__ rhs, int64_t rhs_stride, int nrhs,
+                                                                      const float* __restrict__ sub, int n, float* __restrict__ out,
+                                                                      int armature) {
+  __shared__ float sH[MS_EPW][MS_NS][MS_W];        // rows of M, then of L (unit lower, M = L^T D L)
+  __shared__ float sID[MS_EPW][MS_NS];             // 1 / D
+  __shared__ float sT[MS_EPW][MS_TN];
+  const IdConst& K = C.K;
+  const int half = MS_EPW == 2 ? threadIdx.x >> 5 : 0, lane = MS_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
+  const int env = blockIdx.x * MS_EPW + half;
+  const bool live = env < n;
+  const size_t e = live ? env : n - 1;             // the idle half of the last workgroup recomputes the last env and stores nothing
+  float* sB = sT[half];                            // per body: origin 0..2, joint axis 3..5, m 6, centre of mass 7..9, inertia about it 10..15, all in F
+  float* sC = sT[half] + WBC_NB * MS_BT;           // per coordinate: S = (w 0..2; v 3..5) about P 6..8, F = Ic S = (n 9..11; f 12..14) about P
+  float (*H)[MS_W] = sH[half];
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+
+  if (lane < WBC_NB) {
+    const int b = lane;
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    f3 p = mk3(0.f, 0.f, 0.f), Sw = p;
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
+      const int a = K.path[b][k];
+      if (a < 0) break;
+      const int ax = K.axis[a];
+      const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
+      float s, c;
+      sincosf(dofs[e * (2 * WBC_NDOF) + 2 * K.dof[a]], &s, &c);
+      const float t = 1.f - c;
+      const float Q[9] = {c + t * ux * ux, t * ux * uy - s * uz, t * ux * uz + s * uy,
+                          t * uy * ux + s * uz, c + t * uy * uy, t * uy * uz - s * ux,
+                          t * uz * ux - s * uy, t * uz * uy + s * ux, c + t * uz * uz};
+      p = p + mat_mul(E, mk3(K.joint_xyz[a][0], K.joint_xyz[a][1], K.joint_xyz[a][2]));     // (E, p) <- (E Rot_a, p + E xyz_a)
+      float En[9];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) En[r * 3 + j] = E[r * 3] * Q[j] + E[r * 3 + 1] * Q[3 + j] + E[r * 3 + 2] * Q[6 + j];
+#pragma unroll
+      for (int j = 0; j < 9; ++j) E[j] = En[j];
+      Sw = mat_mul(E, mk3(ux, uy, uz));
+    }
+    // the per-env root composite and gripper body (body_params), the model's otherwise
+    float m = K.mass[b], com[3] = {K.com[b][0], K.com[b][1], K.com[b][2]}, I6[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) I6[j] = K.inertia[b][j];
+    const int slot = b == 0 ? 0 : (b == K.gripper_body ? 10 : -1);
+    if (slot >= 0) {
+      const float* bp = body_params + e * 20 + slot;
+      m = bp[0];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) I6[j] = bp[4 + j];
+    }
+    const float Ib[9] = {I6[0], I6[3], I6[4], I6[3], I6[1], I6[5], I6[4], I6[5], I6[2]};
+    float EI[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) EI[r * 3 + k] = E[r * 3] * Ib[k] + E[r * 3 + 1] * Ib[3 + k] + E[r * 3 + 2] * Ib[6 + k];
+    auto ibar = [&](int r, int k) { return EI[r * 3] * E[k * 3] + EI[r * 3 + 1] * E[k * 3 + 1] + EI[r * 3 + 2] * E[k * 3 + 2]; };
+    float* o = sB + b * MS_BT;
+    st3(o, p); st3(o + 3, Sw); o[6] = m; st3(o + 7, p + mat_mul(E, mk3(com[0], com[1], com[2])));
+    o[10] = ibar(0, 0); o[11] = ibar(1, 1); o[12] = ibar(2, 2); o[13] = ibar(0, 1); o[14] = ibar(0, 2); o[15] = ibar(1, 2);
+  }
+  __syncthreads();
+
+  if (lane < C.ns) {
+    const int s = lane, b = C.co_body[s];
+    const f3 P = ld3(sB + b * MS_BT);              // the root's origin is F's: (0, 0, 0)
+    float m = 0.f, xx = 0.f, yy = 0.f, zz = 0.f, xy = 0.f, xz = 0.f, yz = 0.f;
+    f3 h = mk3(0.f, 0.f, 0.f);
+    for (int d = 0; d < WBC_NB; ++d)
+      if ((K.anc[d] >> b) & 1u) {
+        const float* q = sB + d * MS_BT;
+        const float md = q[6];
+        const f3 r = ld3(q + 7) - P;
+        const float rr = dot(r, r);
+        m += md; h = h + md * r;
+        xx += q[10] + md * (rr - r.x * r.x); yy += q[11] + md * (rr - r.y * r.y); zz += q[12] + md * (rr - r.z * r.z);
+        xy += q[13] - md * r.x * r.y; xz += q[14] - md * r.x * r.z; yz += q[15] - md * r.y * r.z;
+      }
+    f3 w = mk3(0.f, 0.f, 0.f), v = w;
+    if (s < 6) {                                   // world-frame root coordinates: rows of R
+      const int j = s < 3 ? s : s - 3;
+      const f3 row = matT_mul(R, mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f));
+      if (s < 3) v = row; else w = row;
+    } else {
+      w = ld3(sB + b * MS_BT + 3);
+    }
+    const f3 nn = mk3(xx * w.x + xy * w.y + xz * w.z, xy * w.x + yy * w.y + yz * w.z, xz * w.x + yz * w.y + zz * w.z) + cross(h, v);
+    const f3 ff = cross(w, h) + m * v;
+    float* o = sC + s * MS_BT;
+    st3(o, w); st3(o + 3, v); st3(o + 6, P); st3(o + 9, nn); st3(o + 12, ff);
+  }
+  __syncthreads();
+
+  for (int t = lane; t < C.ns * MS_W; t += MS_LPE) {
+    const int s = t / MS_W, u = t - s * MS_W, na = C.co_na[s];
+    if (u > na) continue;
+    const int i = u == na ? s : (u < 6 ? u : C.co_anc0[s] + u - 6);
+    const float *ci = sC + i * MS_BT, *cs = sC + s * MS_BT;
+    const f3 f = ld3(cs + 12);
+    float x = dot(ld3(ci), ld3(cs + 9) + cross(ld3(cs + 6) - ld3(ci + 6), f)) + dot(ld3(ci + 3), f);
+    if (i == s && armature) x += C.arm[s];
+    H[s][u] = x;
+  }
+  __syncthreads();
+
+  for (int k = C.ns - 1; k > 0; --k) {
+    const int na = C.co_na[k], a0 = C.co_anc0[k];
+    const float id = 1.f / H[k][na];
+    for (int t = lane; t < na * (na + 1) / 2; t += MS_LPE) {
+      int u = (int)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);          // t = u (u + 1) / 2 + v, v <= u
+      u = u * (u + 1) / 2 > t ? u - 1 : ((u + 1) * (u + 2) / 2 <= t ? u + 1 : u);
+      const int v = t - u * (u + 1) / 2;
+      H[u < 6 ? u : a0 + u - 6][v] -= H[k][u] * id * H[k][v];
+    }
+    __syncthreads();
+  }
+  for (int t = lane; t < C.ns * MS_W; t += MS_LPE) {
+    const int s = t / MS_W, u = t - s * MS_W, na = C.co_na[s];
+    const float id = 1.f / H[s][na];
+    if (u < na) H[s][u] *= id;
+    if (u == MS_W - 1) sID[half][s] = id;
+  }
+  __syncthreads();                                 // (also: the tables of phases 1-3 are dead from here on)
+
+  if (lane >= nrhs || !live) return;
+  const float* bp = rhs ? rhs + e * rhs_stride + (size_t)lane * BD_NCOL : nullptr;
+  const float* hp = sub ? sub + e * BD_NCOL : nullptr;
+  float* op = out + (e * nrhs + lane) * BD_NCOL;
+  float* stash = sT[half] + lane;                  // [coordinate - 6][right-hand side]
+  auto ld = [&](int s) { const int c = C.co_col[s]; return (bp ? bp[c] : 0.f) - (hp ? hp[c] : 0.f); };
+  float xr[6];
+#pragma unroll
+  for (int j = 0; j < 6; ++j) xr[j] = ld(j);
+  for (int c = 0; c < C.nchain; ++c) {             // x <- L^-T b, leaves first; D^-1 on the way out
+    const int base = C.ch_base[c], len = C.ch_len[c];
+    float xc[WBC_MAX_DEPTH];
+#pragma unroll
+    for (int d = 0; d < WBC_MAX_DEPTH; ++d) xc[d] = d < len ? ld(base + d) : 0.f;
+#pragma unroll
+    for (int d = WBC_MAX_DEPTH - 1; d >= 0; --d)
+      if (d < len) {
+        const float* row = H[base + d];
+        const float xk = xc[d];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) xr[j] -= row[j] * xk;
+#pragma unroll
+        for (int q = 0; q < d; ++q) xc[q] -= row[6 + q] * xk;
+        stash[(base + d - 6) * WBC_SOLVE_MAX_RHS] = xk * sID[half][base + d];
+      }
+  }
+#pragma unroll
+  for (int k = 5; k > 0; --k)
+#pragma unroll
+    for (int j = 0; j < k; ++j) xr[j] -= H[k][j] * xr[k];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {                    // x <- L^-1 x, the root first
+    float a = xr[k] * sID[half][k];
+#pragma unroll
+    for (int j = 0; j < k; ++j) a -= H[k][j] * xr[j];
+    xr[k] = a;
+    op[C.co_col[k]] = a;
+  }
+  for (int c = 0; c < C.nchain; ++c) {
+    const int base = C.ch_base[c], len = C.ch_len[c];
+    float xc[WBC_MAX_DEPTH];
+#pragma unroll
+    for (int d = 0; d < WBC_MAX_DEPTH; ++d)
+      if (d < len) {
+        const float* row = H[base + d];
+        float a = stash[(base + d - 6) * WBC_SOLVE_MAX_RHS];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) a -= row[j] * xr[j];
+#pragma unroll
+        for (int q = 0; q < d; ++q) a -= row[6 + q] * xc[q];
+        xc[d] = a;
+        op[C.co_col[base + d]] = a;
+      }
+  }
+  for (int d = 0; d < WBC_NDOF; ++d)               // the locked fingers: exactly 0
+    if (K.col_body[d] < 0) op[6 + d] = 0.f;
+}
+
+extern "C" int wbc_sim_internal_fd_scratch(wbc_sim* s, float** h);
+
+// Fills C from the model and the chains. 0, or 1: a tree the kernel cannot walk.
+static int ms_const_fill(const DevConst* hc, MsConst& C) {
+  if (id_const_fill(hc, C.K) != 0) return 1;
+  const wbc_model& m = hc->model;
+  for (int s = 0; s < MS_NS; ++s) { C.co_body[s] = 0; C.co_col[s] = s < 6 ? s : 0; C.co_na[s] = s < 6 ? s : 0; C.co_anc0[s] = 6; C.arm[s] = 0.f; }
+  int s = 6;
+  C.nchain = 0;
+  for (int c = 0; c < WBC_NCHAIN; ++c) {
+    const int len = hc->chain_len[c];
+    if (len <= 0) continue;
+    if (len > WBC_MAX_DEPTH || s + len > MS_NS) return 1;
+    C.ch_base[C.nchain] = s; C.ch_len[C.nchain] = len; ++C.nchain;
+    for (int d = 0; d < len; ++d, ++s) {
+      const int b = hc->chain_body[c][d];
+      // every chain hangs off the root and is serial: the rows' layout and the solve's register passes rely on it
+      if (b <= 0 || b >= WBC_NB || m.parent[b] != (d == 0 ? 0 : hc->chain_body[c][d - 1])) return 1;
+      C.co_body[s] = b; C.co_col[s] = 6 + m.dof[b]; C.co_na[s] = 6 + d; C.co_anc0[s] = s - d;
+      C.arm[s] = m.dof[b] < WBC_NACT ? hc->cfg.joint_armature[m.dof[b]] : 0.f;
+    }
+  }
+  for (int c = C.nchain; c < WBC_NCHAIN; ++c) { C.ch_base[c] = 6; C.ch_len[c] = 0; }
+  if (s != 6 + WBC_NB - 1) return 1;                // a moving body on no chain
+  C.ns = s;
+  return 0;
+}
+
+static int mass_solve_launch(wbc_sim* s, const char* who, const float* rhs, int64_t rhs_env_stride, int nrhs, const float* sub, float* out,
+                             int flags, void* stream) {
+  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
+  char msg[160];
+  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) { snprintf(msg, sizeof msg, "%s: no sim state", who); return wbc_sim_internal_fail(-1, msg); }
+  if (n <= 0) return 0;
+  MsConst C;
+  if (ms_const_fill(hc, C) != 0) { snprintf(msg, sizeof msg, "%s: the model's tree is not one the kernel walks", who); return wbc_sim_internal_fail(-3, msg); }
+  hipLaunchKernelGGL(wbc_mass_solve_kernel, dim3((n + MS_EPW - 1) / MS_EPW), dim3(64), 0, (hipStream_t)stream, C, root, dofs, bp, rhs, rhs_env_stride,
+                     nrhs, sub, n, out, (flags & WBC_SOLVE_ARMATURE) ? 1 : 0);
+  if (hipGetLastError() == hipSuccess) return 0;
+  snprintf(msg, sizeof msg, "%s: launch failed", who);
+  return wbc_sim_internal_fail(-2, msg);
+}
+
+// rhs (device f32, right-hand side k of env e at rhs + e * rhs_env_stride + 26 k), out (device f32 [N, nrhs, 26]): include/wbc_sim.h.
+extern "C" int wbc_sim_mass_solve(wbc_sim* s, const float* rhs, int64_t rhs_env_stride, int nrhs, float* out, int flags, void* stream) {
+  StreamDeviceGuard sdg(stream);
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: sim is NULL");
+  if (!rhs || !out) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: rhs / out is NULL");
+  if (nrhs < 1 || nrhs > WBC_SOLVE_MAX_RHS) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: nrhs must be 1..WBC_SOLVE_MAX_RHS");
+  if (rhs_env_stride < (int64_t)BD_NCOL * nrhs) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: rhs_env_stride is below 26 * nrhs");
+  if (flags & ~WBC_SOLVE_ARMATURE) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: unknown flag bits");
+  if (((uintptr_t)rhs | (uintptr_t)out) & 3u) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: rhs / out must be 4-byte aligned");
+  return mass_solve_launch(s, "wbc_sim_mass_solve", rhs, rhs_env_stride, nrhs, nullptr, out, flags, stream);
+}
+
+// nudot = M^-1 (tau - h): wbc_inverse_dynamics_kernel writes h into the sim's [N, 26] scratch, the solve subtracts it as it loads.
+extern "C" int wbc_sim_forward_dynamics(wbc_sim* s, const float* tau, float* nudot, int flags, void* stream) {
+  StreamDeviceGuard sdg(stream);
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics: sim is NULL");
+  if (!nudot) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics: nudot is NULL");
+  if (flags & ~WBC_SOLVE_ARMATURE) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics: unknown flag bits");
+  if (((uintptr_t)tau | (uintptr_t)nudot) & 3u) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics: tau / nudot must be 4-byte aligned");
+  float* h = nullptr;
+  if (wbc_sim_internal_fd_scratch(s, &h) != 0) return -1;
+  const int rc = wbc_sim_inverse_dynamics(s, nullptr, h, nullptr, stream);
+  if (rc != 0) return rc;
+  return mass_solve_launch(s, "wbc_sim_forward_dynamics", tau, BD_NCOL, 1, h, nudot, flags, stream);
 }

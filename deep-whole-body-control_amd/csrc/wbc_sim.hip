@@ -78,6 +78,7 @@ struct wbc_sim {
   char* deal_mem = nullptr;
   bool deal_on = false;
   int64_t step_launches = 0;
+  float* fd_scratch = nullptr;   // [N,26]: the bias forces between the two launches of wbc_sim_forward_dynamics (wbc_sim_create)
 };
 
 extern "C" const char* wbc_last_error(void) { return g_err.c_str(); }
@@ -381,6 +382,7 @@ extern "C" int wbc_sim_create(const wbc_model* model, const wbc_task_cfg* cfg, i
   HIP_OK(hipMemcpy(s->dT, &s->T, sizeof(DevTensors), hipMemcpyHostToDevice));
   HIP_OK(hipMalloc((void**)&s->dc, sizeof(DevConst)));
   HIP_OK(hipMemcpy(s->dc, &s->hc, sizeof(DevConst), hipMemcpyHostToDevice));
+  HIP_OK(hipMalloc((void**)&s->fd_scratch, (size_t)num_envs * WBC_NCOL * sizeof(float)));
   *out = s;
   return 0;
 }
@@ -393,6 +395,7 @@ extern "C" int wbc_sim_destroy(wbc_sim* s) {
   if (s->deal_mem) (void)hipFree(s->deal_mem);
   if (s->dT) (void)hipFree(s->dT);
   if (s->hf_dev) (void)hipFree(s->hf_dev);
+  if (s->fd_scratch) (void)hipFree(s->fd_scratch);
   delete s;
   return 0;
 }
@@ -629,6 +632,12 @@ extern "C" int wbc_sim_internal_arm_inputs(wbc_sim* s, const DevConst** hc, cons
                                            const float** mass_params, int* n) {
   if (!s) return -1;
   *hc = &s->hc; *root = s->T.root; *dofs = s->T.dof; *body_params = s->T.body_params; *mass_params = s->T.mass_params; *n = s->n;
+  return 0;
+}
+// internal (wbc_arm_kernel.hip): the sim's [N,26] scratch of wbc_sim_forward_dynamics
+extern "C" int wbc_sim_internal_fd_scratch(wbc_sim* s, float** h) {
+  if (!s || !h || !s->fd_scratch) return fail(-1, "wbc_sim_forward_dynamics: the sim has no bias-force scratch");
+  *h = s->fd_scratch;
   return 0;
 }
 // wbc_last_error() for the entry points that live in other translation units

@@ -501,6 +501,27 @@ class WidowGo1(LeggedRobot):
         self.sim.inverse_dynamics(grav=grav)
         return grav
 
+    # ---- M^-1 (no counterpart in the reference, which calls pinv on the gathered arm block): one launch, M never leaves the device ----
+    def mass_matrix_solve(self, rhs: torch.Tensor, armature: bool = False) -> torch.Tensor:
+        """A fresh f32 M^-1 rhs of the current state, rhs [N, 26] or [N, K, 26] (K <= 32; a strided view such as
+        jacobian_whole[:, r] is taken as it stands). armature: with the implicit-PD joint armature on the diagonal, the matrix a
+        substep integrates with (include/wbc_sim.h: wbc_sim_mass_solve). Fingers: exactly 0."""
+        return self.sim.mass_solve(rhs, armature=armature)
+
+    def forward_dynamics(self, tau: torch.Tensor = None, armature: bool = False) -> torch.Tensor:
+        """A fresh f32 [N, 26] nudot = M^-1 (tau - h), the inverse of inverse_dynamics: tau rows 0:3 net external force, 3:6 net
+        external moment about the root origin (world axes), 6: joint torques; None: zeros (include/wbc_sim.h:
+        wbc_sim_forward_dynamics). Contacts enter as J^T f added to tau by the caller."""
+        return self.sim.forward_dynamics(tau, armature=armature)
+
+    def operational_space_inverse_inertia(self, rigid_body: int, armature: bool = False) -> torch.Tensor:
+        """f32 [N, 6, 6] inverse operational-space inertia J_r M^-1 J_r^T of rigid body r's origin (rows linear, angular; world
+        frame). Refreshes jacobian_whole. It is NOT inverted here: it can be near-singular, and whether and how to invert it is the
+        caller's decision."""
+        self.sim.refresh_jacobian_tensors()
+        J = self.jacobian_whole[:, int(rigid_body)]                                   # [N, 6, 26], env stride 27 * 156
+        return torch.bmm(self.sim.mass_solve(J, armature=armature), J.transpose(1, 2))
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])

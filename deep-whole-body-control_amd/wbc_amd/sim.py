@@ -215,6 +215,44 @@ class WbcSim:
         """Recompute the acquired bias vector in place from the current state and per-env body parameters."""
         self.inverse_dynamics(tau=self.acquire_bias_force_tensor())
 
+    # ---- M^-1: mass-matrix solves and forward dynamics, same coordinates (include/wbc_sim.h: wbc_sim_mass_solve) ------------------
+    def mass_solve(self, rhs: torch.Tensor, out: Optional[torch.Tensor] = None, armature: bool = False) -> torch.Tensor:
+        """One wbc_sim_mass_solve launch on the current stream: out[e, k] = M_e^-1 rhs[e, k] at the current state. rhs f32 [N, 26]
+        or [N, K, 26] (K <= 32) whose last two dims are contiguous, with any env stride (a view such as jacobian[:, r] is passed as
+        it stands); returns (or fills) [N, K, 26], [N, 26] for a [N, 26] rhs. armature: solve with M + diag(0_6, joint_armature)."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        flat = rhs.dim() == 2
+        r3 = rhs.unsqueeze(1) if flat else rhs
+        assert r3.dim() == 3 and r3.shape[0] == n and r3.shape[2] == ncol and 1 <= r3.shape[1] <= 32, tuple(rhs.shape)
+        assert rhs.device == self.arena.device and rhs.dtype == torch.float32
+        k = r3.shape[1]
+        assert r3.stride(2) == 1 and (k == 1 or r3.stride(1) == ncol), "the last two dims of rhs must be contiguous"
+        stride = r3.stride(0) if n > 1 else k * ncol
+        assert stride >= k * ncol, "rhs rows of different envs overlap"
+        if out is None:
+            out = torch.empty((n, ncol) if flat else (n, k, ncol), dtype=torch.float32, device=self.device)
+        assert out.device == self.arena.device and out.dtype == torch.float32 and out.is_contiguous()
+        assert tuple(out.shape) == ((n, ncol) if flat else (n, k, ncol))
+        r0, o0 = rhs.data_ptr(), out.data_ptr()
+        assert r0 + 4 * ((n - 1) * stride + k * ncol) <= o0 or o0 + 4 * n * k * ncol <= r0, "out overlaps rhs"
+        check(self.L.wbc_sim_mass_solve(self.h, rhs.data_ptr(), stride, k, out.data_ptr(), 1 if armature else 0, self._stream()),
+              "wbc_sim_mass_solve")
+        return out
+
+    def forward_dynamics(self, tau: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                         armature: bool = False) -> torch.Tensor:
+        """wbc_sim_forward_dynamics on the current stream: nudot = M^-1 (tau - h), f32 [N, 26] (tau None: zeros)."""
+        shape = (self.num_envs, 6 + abi.NDOF)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        for t in (tau, out):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape
+        assert tau is None or abs(tau.data_ptr() - out.data_ptr()) >= 4 * out.numel(), "out overlaps tau"
+        check(self.L.wbc_sim_forward_dynamics(self.h, tau.data_ptr() if tau is not None else None, out.data_ptr(),
+                                              1 if armature else 0, self._stream()), "wbc_sim_forward_dynamics")
+        return out
+
     def episode_stats(self, scale: float, track_state: torch.Tensor = None, track_cap: int = 0) -> torch.Tensor:
         """Means over the envs that reset in the last step of their finished episode's reward sums [NREW] and metric
         sums [NMETRIC], times `scale`, as one fresh device tensor (WG:743-754 without a host sync). With `track_state`

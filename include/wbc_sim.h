@@ -633,6 +633,36 @@ int wbc_sim_body_dynamics(wbc_sim* sim, float* jac, float* mm, void* stream);
  * kernel cannot walk; -2 if the launch fails. Stream / device handling as wbc_sim_body_dynamics. */
 int wbc_sim_inverse_dynamics(wbc_sim* sim, const float* nudot, float* tau, float* grav, void* stream);
 
+/* M^-1 in the coordinates of wbc_sim_body_dynamics, M formed from the sim's CURRENT state inside the launch and factorised as
+ * L^T D L over the kinematic tree (leaves first: no fill-in); it never goes through memory.
+ *     out[e, k, :] = M_e^-1 rhs[e, k, :]   for k < nrhs.
+ * rhs    device f32: right-hand side k of env e is the 26 contiguous floats at rhs + e * rhs_env_stride + 26 k.
+ *        rhs_env_stride is in floats and >= 26 nrhs, so that the view jac[:, r] of one rigid body's six Jacobian rows (env stride
+ *        27 * 156) can be passed as it stands: M is symmetric, the result is then (M^-1 J_r^T)^T and out @ J_r^T the inverse
+ *        operational-space inertia J_r M^-1 J_r^T.
+ * out    device f32 [N, nrhs, 26], contiguous, not overlapping rhs. Both pointers need 4-byte alignment only.
+ * flags  0, or WBC_SOLVE_ARMATURE: solve with M + diag(0_6, wbc_task_cfg.joint_armature[0..]) -- the matrix one airborne substep
+ *        of the step kernel integrates with (the implicit-PD armature).
+ * Locked fingers (coordinates 24, 25): their entries of rhs are ignored, their entries of out are exactly 0; the other 24
+ * coordinates are solved as a symmetric positive definite system. The root POSITION is never read: the result is bit-identical
+ * under a translation of the robot.
+ * -1 with a message in wbc_last_error() for a NULL sim / rhs / out, nrhs outside 1..WBC_SOLVE_MAX_RHS, a stride below 26 nrhs,
+ * unknown flag bits or a misaligned pointer (nothing is written); -3 for a model whose tree the kernel cannot walk; -2 if the
+ * launch fails. Stream / device handling as wbc_sim_body_dynamics. */
+#define WBC_SOLVE_ARMATURE 1
+#define WBC_SOLVE_MAX_RHS 32
+int wbc_sim_mass_solve(wbc_sim* sim, const float* rhs, int64_t rhs_env_stride, int nrhs, float* out, int flags, void* stream);
+
+/* Forward dynamics nudot = M^-1 (tau - h), the inverse of wbc_sim_inverse_dynamics: tau device f32 [N, 26] or NULL (= zeros) in
+ * that function's conventions (rows 0:3 the net external force, rows 3:6 the net external moment about the root origin, world
+ * axes; rows 6: the joint torques; a caller adds J^T f of contacts itself), nudot device f32 [N, 26]. Two launches on `stream`:
+ * the inverse-dynamics kernel writes h into a [N, 26] buffer the sim owns (allocated by wbc_sim_create, so the call is safe under stream capture), the solve subtracts it. That buffer
+ * is one per sim: calls for the same sim on DIFFERENT streams must be ordered by the caller (events), or they race on h.
+ * Without flags this is rigid-body dynamics: wbc_sim_inverse_dynamics(nudot) returns tau up to rounding. With
+ * WBC_SOLVE_ARMATURE it is the acceleration one airborne substep of the step kernel applies for the applied torques tau[6:]
+ * away from the joint limits. Fingers, translation, alignment and error codes as wbc_sim_mass_solve (NULL nudot: -1). */
+int wbc_sim_forward_dynamics(wbc_sim* sim, const float* tau, float* nudot, int flags, void* stream);
+
 /* extras["episode"] of reset_idx (widowGo1.py:743-754): out[0:WBC_NREW] = mean over the envs that reset in the last
  * step of their finished episode's reward sums, out[WBC_NREW:+WBC_NMETRIC] the same for the metric sums, both
  * times `scale` (1 / max_episode_length_s). `out`: device, WBC_NREW + WBC_NMETRIC floats. On a step in which no env reset
