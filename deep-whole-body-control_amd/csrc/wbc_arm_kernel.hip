@@ -967,3 +967,319 @@ extern "C" int wbc_sim_forward_dynamics(wbc_sim* s, const float* tau, float* nud
   if (rc != 0) return rc;
   return mass_solve_launch(s, "wbc_sim_forward_dynamics", tau, BD_NCOL, 1, h, nudot, flags, stream);
 }
+
+// ---- rigid-body accelerations and contact-constrained forward dynamics (include/wbc_sim.h) ---------------------------------------------
+// acc = J nudot + Jdot nu for every rigid-body origin, and the solve of
+//     M nudot + h = tau + sum_r J_r^T lambda_r,    J_r nudot + (Jdot nu)_r = a_des_r - damping lambda_r
+// for up to WBC_CONSTR_MAX_BODIES bodies whose origins' linear accelerations are prescribed. Both start from a walk in the shape of phase 1 of
+// wbc_inverse_dynamics_kernel (a copy: that kernel's code generation is left alone): a lane follows IdConst-style path[] from the root
+// DOWN and carries the frame (E, p), the angular velocity w, the angular acceleration a_w and the classical acceleration a_o of the
+// body's origin in F's axes in registers. With x a point of the body relative to that origin, its classical acceleration is
+// R (a_o + a_w x x + w x (w x x)) and the angular one R a_w. The root position is never read.
+#ifndef BA_EPW
+#define BA_EPW 2                                // envs per workgroup of the three kernels below: 2, or 1 (-DBA_EPW=1, the variant DESIGN.md compares with)
+#endif
+static_assert(BA_EPW == 1 || BA_EPW == 2, "one env per 64 lanes or one per 32-lane half");
+#define BA_LPE (64 / BA_EPW)                    // lanes per env
+#define CD_MAXROWS (3 * WBC_CONSTR_MAX_BODIES)  // 15 constraint rows at most
+#define CD_GSTRIDE 16                           // floats of gamma per env in the workspace
+#define CD_LD 27                                // LDS row pitch of the 26-column blocks (odd: rows land in different banks)
+static_assert(WBC_NRB <= BA_LPE && WBC_NB + WBC_CONSTR_MAX_BODIES <= BA_LPE && CD_MAXROWS + 1 <= WBC_SOLVE_MAX_RHS && CD_MAXROWS <= CD_GSTRIDE, "lanes");
+struct BaConst {
+  int32_t axis[WBC_NB], dof[WBC_NB];
+  int32_t path[WBC_NB][WBC_MAX_DEPTH];         // as IdConst::path
+  int32_t rb_body[WBC_NRB];
+  float joint_xyz[WBC_NB][3], rb_offset[WBC_NRB][3];
+};
+
+// The walk root -> b. On return (E, p) is body b's frame in F, w and aw its angular velocity and acceleration and ao the CLASSICAL
+// acceleration of its own origin p, all in F's axes. Every body's acceleration is carried at that body's origin, not about F's: the
+// terms added per joint are aw x r + w x (w x r) with r the step from the parent's origin to the child's, so the rounding error is
+// proportional to the terms the tests' magnitude sums. (Spatial vectors about F's origin, as wbc_inverse_dynamics_kernel carries them,
+// add w x v_O and w x (w x x) of size |w|^2 |x| that cancel down to |w|^2 |x - p| at a far body: 78 x 2^-24 of the magnitude at the
+// arm's links in rollout states.) The root's linear velocity enters no acceleration and is never read; nudot[0:3] is the classical
+// acceleration of the root origin, so a body fixed to a root that does not accelerate gets exactly w x (w x x).
+__device__ __forceinline__ void ba_walk(const BaConst& K, int b, size_t e, const float* R, const float* __restrict__ root,
+                                        const float* __restrict__ dofs, const float* __restrict__ nudot, float* E, f3& p, f3& w, f3& aw,
+                                        f3& ao) {
+  p = mk3(0.f, 0.f, 0.f);
+  aw = p; ao = p;
+  w = matT_mul(R, ld3(root + e * 26 + 10));
+  if (nudot) { ao = matT_mul(R, ld3(nudot + e * BD_NCOL)); aw = matT_mul(R, ld3(nudot + e * BD_NCOL + 3)); }
+  for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
+    const int a = K.path[b][k];
+    if (a < 0) break;
+    const int ax = K.axis[a], d = K.dof[a];
+    const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
+    float s, c;
+    sincosf(dofs[e * (2 * WBC_NDOF) + 2 * d], &s, &c);
+    const float t = 1.f - c;
+    const float Q[9] = {c + t * ux * ux, t * ux * uy - s * uz, t * ux * uz + s * uy,
+                        t * uy * ux + s * uz, c + t * uy * uy, t * uy * uz - s * ux,
+                        t * uz * ux - s * uy, t * uz * uy + s * ux, c + t * uz * uz};
+    const f3 r = mat_mul(E, mk3(K.joint_xyz[a][0], K.joint_xyz[a][1], K.joint_xyz[a][2]));    // (E, p) <- (E Rot_a, p + E xyz_a)
+    p = p + r;
+    ao = ao + cross(aw, r) + cross(w, cross(w, r));          // the parent's w and aw carry its origin's acceleration to the joint
+    float En[9];
+#pragma unroll
+    for (int r_ = 0; r_ < 3; ++r_)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) En[r_ * 3 + j] = E[r_ * 3] * Q[j] + E[r_ * 3 + 1] * Q[3 + j] + E[r_ * 3 + 2] * Q[6 + j];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) E[j] = En[j];
+    const f3 Sw = mat_mul(E, mk3(ux, uy, uz));
+    const float qd = dofs[e * (2 * WBC_NDOF) + 2 * d + 1], qdd = nudot ? nudot[e * BD_NCOL + 6 + d] : 0.f;
+    const f3 jw = Sw * qd;                                   // aw += S qdd + w x (S qd), then w += S qd
+    aw = aw + Sw * qdd + cross(w, jw);
+    w = w + jw;
+  }
+}
+
+// Lane r = rigid body r (27 of the 32 lanes of an env's half). No LDS: a lane stores its own six floats (the output needs 4-byte
+// alignment only, so the stores are single dwords; a wavefront's two rows are one contiguous 1296-byte range).
+extern "C" __global__ void __launch_bounds__(64) wbc_body_accel_kernel(BaConst K, const float* __restrict__ root, const float* __restrict__ dofs,
+                                                                      const float* __restrict__ nudot, int n, float* __restrict__ acc) {
+  const int half = BA_EPW == 2 ? threadIdx.x >> 5 : 0, lane = BA_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
+  const int env = blockIdx.x * BA_EPW + half;
+  if (env >= n || lane >= WBC_NRB) return;
+  const size_t e = env;
+  const int r = lane;
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+  float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+  f3 p, w, aw, ao;
+  ba_walk(K, K.rb_body[r], e, R, root, dofs, nudot, E, p, w, aw, ao);
+  const f3 xo = mat_mul(E, mk3(K.rb_offset[r][0], K.rb_offset[r][1], K.rb_offset[r][2]));   // the rigid body's origin from the moving body's
+  const f3 lin = mat_mul(R, ao + cross(aw, xo) + cross(w, cross(w, xo))), ang = mat_mul(R, aw);
+  float* o = acc + (e * WBC_NRB + r) * 6;
+  st3(o, lin); st3(o + 3, ang);
+}
+
+struct CdConst {
+  BaConst A;
+  int32_t col_body[WBC_NDOF];
+  uint32_t anc[WBC_NB];                        // as BodyConst::anc
+  int32_t nb, rb[WBC_CONSTR_MAX_BODIES];       // the listed rigid bodies
+};
+
+// The right-hand-side block of the solve, [N, 3 nb + 1, 26]: rows 3k..3k+2 the linear Jacobian rows of listed body k (zeros where it
+// is inactive), the last row tau - h; and gamma [N, CD_GSTRIDE] = (Jdot nu) of those rows. Lane b < 19 = moving body b leaves its joint
+// axis and origin (F) in LDS, lane 19 + k walks to listed body k and leaves its origin; then lane c = column c writes its entry of
+// every row, so a row is one 104-byte store of consecutive lanes.
+extern "C" __global__ void __launch_bounds__(64) wbc_constraint_rhs_kernel(CdConst C, const float* __restrict__ root,
+                                                                          const float* __restrict__ dofs,
+                                                                          const uint8_t* __restrict__ active, const float* __restrict__ tau,
+                                                                          const float* __restrict__ h, int n, float* __restrict__ rhs,
+                                                                          float* __restrict__ gamma) {
+  __shared__ float sJ[BA_EPW][WBC_NB][6];          // joint axis, joint origin, in F
+  __shared__ float sX[BA_EPW][WBC_CONSTR_MAX_BODIES][3];   // listed body's origin in F
+  const int half = BA_EPW == 2 ? threadIdx.x >> 5 : 0, lane = BA_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
+  const int env = blockIdx.x * BA_EPW + half;
+  const bool live = env < n;
+  const size_t e = live ? env : n - 1;             // the idle half of the last workgroup recomputes the last env and stores nothing
+  const int nb = C.nb, nrow = 3 * nb + 1;
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+  if (lane < WBC_NB + nb) {
+    const bool body = lane < WBC_NB;
+    const int k = body ? 0 : lane - WBC_NB, r = C.rb[k], b = body ? lane : C.A.rb_body[r];
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    f3 p, w, aw, ao;
+    ba_walk(C.A, b, e, R, root, dofs, nullptr, E, p, w, aw, ao);
+    if (body) {
+      const int ax = C.A.axis[b];                            // -1 for the root: no joint axis
+      st3(sJ[half][b], mat_mul(E, mk3(ax == 0 ? 1.f : 0.f, ax == 1 ? 1.f : 0.f, ax == 2 ? 1.f : 0.f)));
+      st3(sJ[half][b] + 3, p);
+    } else {
+      const f3 xo = mat_mul(E, mk3(C.A.rb_offset[r][0], C.A.rb_offset[r][1], C.A.rb_offset[r][2]));
+      st3(sX[half][k], p + xo);
+      if (live) st3(gamma + e * CD_GSTRIDE + 3 * k, mat_mul(R, ao + cross(aw, xo) + cross(w, cross(w, xo))));
+    }
+  }
+  __syncthreads();
+  if (lane < BD_NCOL && live) {
+    const int c = lane, b = c < 6 ? 0 : C.col_body[c - 6], j = c < 3 ? c : c - 3;
+    float* o = rhs + e * (size_t)(nrow * BD_NCOL) + c;
+    for (int k = 0; k < nb; ++k) {
+      const bool act = active ? active[e * nb + k] != 0 : true;
+      const f3 x = ld3(sX[half][k]);
+      f3 lin = mk3(0.f, 0.f, 0.f);
+      if (act) {
+        const f3 ej = mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f);
+        if (c < 3) lin = ej;                                 // v_root: identity
+        else if (c < 6) lin = cross(ej, mat_mul(R, x));      // omega_root: e_j x (origin relative to the root, world axes)
+        else if (b >= 0 && ((C.anc[C.A.rb_body[C.rb[k]]] >> b) & 1u)) lin = mat_mul(R, cross(ld3(sJ[half][b]), x - ld3(sJ[half][b] + 3)));
+      }
+      o[(3 * k) * BD_NCOL] = lin.x; o[(3 * k + 1) * BD_NCOL] = lin.y; o[(3 * k + 2) * BD_NCOL] = lin.z;
+    }
+    o[3 * nb * BD_NCOL] = b >= 0 ? (tau ? tau[e * BD_NCOL + c] : 0.f) - h[e * BD_NCOL + c] : 0.f;
+  }
+}
+
+// Per env, with m = 3 nb rows, J the rows of the right-hand-side block and Y = (M^-1 [J^T | tau - h])^T the mass solve's output:
+// A = J Y^T + damping I from its lower triangle (one entry per lane and round), identity rows and columns where a body is inactive;
+// c = a_des - gamma - J a_free; Cholesky A = L L^T in LDS, lane i = row i, one column per round (left-looking: row i meets row j only);
+// the two triangular solves with lane i holding entry i and the pivot's value handed round through LDS; nudot = a_free + Y^T lambda,
+// lane c = column c. A single-wavefront workgroup: the __syncthreads() order the LDS traffic and cost no barrier instruction.
+extern "C" __global__ void __launch_bounds__(64) wbc_constraint_solve_kernel(const float* __restrict__ rhs, const float* __restrict__ Y,
+                                                                            const float* __restrict__ gamma,
+                                                                            const uint8_t* __restrict__ active,
+                                                                            const float* __restrict__ acc_des, float damping, int nb,
+                                                                            uint32_t live_cols, int n, float* __restrict__ nudot,
+                                                                            float* __restrict__ lambda) {
+  __shared__ float sJ[BA_EPW][CD_MAXROWS][CD_LD], sY[BA_EPW][CD_MAXROWS + 1][CD_LD];
+  __shared__ float sA[BA_EPW][CD_MAXROWS][CD_MAXROWS + 1];   // lower triangle: A, then L
+  __shared__ float sD[BA_EPW][CD_MAXROWS + 1], sV[BA_EPW][CD_MAXROWS + 1];   // 1 / L_jj; the value handed round
+  const int half = BA_EPW == 2 ? threadIdx.x >> 5 : 0, lane = BA_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
+  const int env = blockIdx.x * BA_EPW + half;
+  const bool live = env < n;
+  const size_t e = live ? env : n - 1;             // the idle half of the last workgroup recomputes the last env and stores nothing
+  const int m = 3 * nb;
+  float (*J)[CD_LD] = sJ[half], (*Yt)[CD_LD] = sY[half];
+  float (*A)[CD_MAXROWS + 1] = sA[half];
+  float *D = sD[half], *V = sV[half];
+  const float *rp = rhs + e * (size_t)((m + 1) * BD_NCOL), *yp = Y + e * (size_t)((m + 1) * BD_NCOL);
+  for (int t = lane; t < (m + 1) * BD_NCOL; t += BA_LPE) {
+    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+    Yt[r][c] = yp[t];
+    if (r < m) J[r][c] = rp[t];
+  }
+  uint32_t act = 0;                                // bit i: row i belongs to an active body
+  for (int k = 0; k < nb; ++k)
+    if (!active || active[e * nb + k]) act |= 7u << (3 * k);
+  __syncthreads();
+
+  for (int t = lane; t < m * (m + 1) / 2; t += BA_LPE) {
+    int i = (int)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);              // t = i (i + 1) / 2 + j, j <= i
+    i = i * (i + 1) / 2 > t ? i - 1 : ((i + 1) * (i + 2) / 2 <= t ? i + 1 : i);
+    const int j = t - i * (i + 1) / 2;
+    float a = 0.f;
+    for (int c = 0; c < BD_NCOL; ++c) a += J[i][c] * Yt[j][c];
+    const bool on = ((act >> i) & 1u) && ((act >> j) & 1u);
+    A[i][j] = on ? (i == j ? a + damping : a) : (i == j ? 1.f : 0.f);
+  }
+  const int i = lane;
+  const bool row = i < m, on = row && ((act >> i) & 1u);
+  float ci = 0.f;
+  if (on) {
+    float a = 0.f;
+    for (int c = 0; c < BD_NCOL; ++c) a += J[i][c] * Yt[m][c];
+    ci = ((acc_des ? acc_des[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
+  }
+  for (int j = 0; j < m; ++j) {
+    __syncthreads();
+    float d = A[j][j];
+    for (int k = 0; k < j; ++k) d -= A[j][k] * A[j][k];
+    const float id = 1.f / __fsqrt_rn(d);
+    if (row && i > j) {
+      float s = A[i][j];
+      for (int k = 0; k < j; ++k) s -= A[i][k] * A[j][k];
+      A[i][j] = s * id;
+    }
+    if (i == j) D[j] = id;
+  }
+  for (int j = 0; j < m; ++j) {                    // L y = c
+    if (i == j) V[j] = ci * D[j];
+    __syncthreads();
+    const float yj = V[j];
+    if (i == j) ci = yj;
+    else if (row && i > j) ci -= A[i][j] * yj;
+  }
+  for (int j = m - 1; j >= 0; --j) {               // L^T lambda = y
+    __syncthreads();
+    if (i == j) V[j] = ci * D[j];
+    __syncthreads();
+    const float lj = V[j];
+    if (row && i < j) ci -= A[j][i] * lj;
+  }
+  __syncthreads();
+  if (!live) return;
+  if (lambda && row) lambda[e * m + i] = on ? V[i] : 0.f;
+  if (lane < BD_NCOL) {
+    float a = Yt[m][lane];
+    for (int k = 0; k < m; ++k) a += Yt[k][lane] * V[k];
+    nudot[e * BD_NCOL + lane] = ((live_cols >> lane) & 1u) ? a : 0.f;
+  }
+}
+
+static int ba_const_fill(const DevConst* hc, BaConst& A, IdConst& K) {
+  if (id_const_fill(hc, K) != 0) return 1;
+  const wbc_model& m = hc->model;
+  for (int b = 0; b < WBC_NB; ++b) {
+    A.axis[b] = K.axis[b]; A.dof[b] = K.dof[b];
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k) A.path[b][k] = K.path[b][k];
+    for (int j = 0; j < 3; ++j) A.joint_xyz[b][j] = K.joint_xyz[b][j];
+  }
+  for (int r = 0; r < WBC_NRB; ++r) {
+    A.rb_body[r] = m.rb_body[r];                   // id_const_fill (body_const_fill) checked the range
+    for (int j = 0; j < 3; ++j) A.rb_offset[r][j] = m.rb_offset[r][j];
+  }
+  return 0;
+}
+
+// nudot (device f32 [N,26] or NULL = zeros), acc (device f32 [N,27,6]): include/wbc_sim.h.
+extern "C" int wbc_sim_body_accelerations(wbc_sim* s, const float* nudot, float* acc, void* stream) {
+  StreamDeviceGuard sdg(stream);
+  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_body_accelerations: sim is NULL");
+  if (!acc) return wbc_sim_internal_fail(-1, "wbc_sim_body_accelerations: acc is NULL");
+  if (((uintptr_t)nudot | (uintptr_t)acc) & 3u) return wbc_sim_internal_fail(-1, "wbc_sim_body_accelerations: nudot / acc must be 4-byte aligned");
+  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_body_accelerations: no sim state");
+  if (n <= 0) return 0;
+  BaConst A; IdConst K;
+  if (ba_const_fill(hc, A, K) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_body_accelerations: the model's tree is not one the kernel walks");
+  hipLaunchKernelGGL(wbc_body_accel_kernel, dim3((n + BA_EPW - 1) / BA_EPW), dim3(64), 0, (hipStream_t)stream, A, root, dofs, nudot, n, acc);
+  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_body_accelerations: launch failed");
+}
+
+// Workspace layout (floats): the right-hand-side block [N, 3 nb + 1, 26], the mass solve's output of the same shape, gamma [N, 16].
+extern "C" size_t wbc_sim_constrained_dynamics_workspace_floats(int num_envs, int nbodies) {
+  if (num_envs <= 0 || nbodies < 1 || nbodies > WBC_CONSTR_MAX_BODIES) return 0;
+  return (size_t)num_envs * (2 * (size_t)(3 * nbodies + 1) * BD_NCOL + CD_GSTRIDE);
+}
+
+// Four launches on `stream`: h (the existing inverse-dynamics kernel, into the sim's scratch), the right-hand-side block, the existing
+// mass solve with 3 nb + 1 right-hand sides, the constraint solve. Arguments and conventions: include/wbc_sim.h.
+extern "C" int wbc_sim_constrained_dynamics(wbc_sim* s, const int32_t* rigid_bodies, int nbodies, const uint8_t* active, const float* tau,
+                                            const float* acc_des, float damping, int flags, float* nudot, float* lambda, float* workspace,
+                                            void* stream) {
+  StreamDeviceGuard sdg(stream);
+  const char* who = "wbc_sim_constrained_dynamics";
+  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: sim is NULL");
+  if (!rigid_bodies || !nudot || !workspace) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: rigid_bodies / nudot / workspace is NULL");
+  if (nbodies < 1 || nbodies > WBC_CONSTR_MAX_BODIES) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: nbodies must be 1..WBC_CONSTR_MAX_BODIES");
+  if (!(damping >= 0.f) || !(damping <= 3.4e38f)) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: damping must be finite and >= 0");
+  if (flags & ~WBC_SOLVE_ARMATURE) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: unknown flag bits");
+  if (((uintptr_t)tau | (uintptr_t)acc_des | (uintptr_t)nudot | (uintptr_t)lambda | (uintptr_t)workspace) & 3u)
+    return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: tau / acc_des / nudot / lambda / workspace must be 4-byte aligned");
+  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: no sim state");
+  for (int k = 0; k < nbodies; ++k)
+    if (rigid_bodies[k] < 0 || rigid_bodies[k] >= WBC_NRB) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: rigid-body index outside 0..WBC_NRB-1");
+  CdConst C; IdConst K;
+  if (ba_const_fill(hc, C.A, K) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_constrained_dynamics: the model's tree is not one the kernel walks");
+  for (int k = 0; k < nbodies; ++k)
+    for (int l = 0; l < k; ++l)
+      if (C.A.rb_body[rigid_bodies[k]] == C.A.rb_body[rigid_bodies[l]])
+        return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: two listed rigid bodies ride on the same moving body (dependent rows)");
+  if (n <= 0) return 0;
+  uint32_t live_cols = 63u;
+  for (int d = 0; d < WBC_NDOF; ++d) { C.col_body[d] = K.col_body[d]; if (K.col_body[d] >= 0) live_cols |= 1u << (6 + d); }
+  for (int b = 0; b < WBC_NB; ++b) C.anc[b] = K.anc[b];
+  C.nb = nbodies;
+  for (int k = 0; k < WBC_CONSTR_MAX_BODIES; ++k) C.rb[k] = rigid_bodies[k < nbodies ? k : 0];
+  float* h = nullptr;
+  if (wbc_sim_internal_fd_scratch(s, &h) != 0) return -1;
+  const int nrow = 3 * nbodies + 1;
+  float *blk = workspace, *Y = blk + (size_t)n * nrow * BD_NCOL, *gamma = Y + (size_t)n * nrow * BD_NCOL;
+  int rc = wbc_sim_inverse_dynamics(s, nullptr, h, nullptr, stream);
+  if (rc != 0) return rc;
+  const dim3 grid((n + BA_EPW - 1) / BA_EPW);
+  hipLaunchKernelGGL(wbc_constraint_rhs_kernel, grid, dim3(64), 0, (hipStream_t)stream, C, root, dofs, active, tau, (const float*)h, n, blk, gamma);
+  if (hipGetLastError() != hipSuccess) return wbc_sim_internal_fail(-2, "wbc_sim_constrained_dynamics: launch failed");
+  rc = mass_solve_launch(s, who, blk, (int64_t)nrow * BD_NCOL, nrow, nullptr, Y, flags, stream);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(wbc_constraint_solve_kernel, grid, dim3(64), 0, (hipStream_t)stream, (const float*)blk, (const float*)Y, (const float*)gamma, active,
+                     acc_des, damping, nbodies, live_cols, n, nudot, lambda);
+  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_constrained_dynamics: launch failed");
+}

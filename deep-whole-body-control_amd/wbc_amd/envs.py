@@ -522,6 +522,21 @@ class WidowGo1(LeggedRobot):
         J = self.jacobian_whole[:, int(rigid_body)]                                   # [N, 6, 26], env stride 27 * 156
         return torch.bmm(self.sim.mass_solve(J, armature=armature), J.transpose(1, 2))
 
+    # ---- task-space accelerations and stance-constrained forward dynamics (no counterpart in the reference) ------------------------
+    def rigid_body_accelerations(self, nudot: torch.Tensor = None) -> torch.Tensor:
+        """A fresh f32 [N, 27, 6]: J nudot + Jdot nu of every rigid-body origin in the layout of rigid_body_state[..., 7:13]
+        (classical world-frame linear acceleration, angular acceleration). nudot None: zeros, i.e. the task-space bias acceleration
+        Jdot nu (include/wbc_sim.h: wbc_sim_body_accelerations)."""
+        return self.sim.body_accelerations(nudot)
+
+    def stance_forward_dynamics(self, tau: torch.Tensor = None, stance: torch.Tensor = None, armature: bool = False):
+        """(nudot [N, 26], foot_forces [N, 4, 3]): forward dynamics with the origins of the stance feet (feet_indices) held at zero
+        linear acceleration. stance: bool [N, 4] such as get_foot_contacts(), None: all four feet. foot_forces are the forces applied
+        TO the robot in world axes, exactly 0 for a swing foot (include/wbc_sim.h: wbc_sim_constrained_dynamics)."""
+        if self.__dict__.get("_feet_list") is None:
+            self._feet_list = [int(i) for i in self.feet_indices.tolist()]
+        return self.sim.constrained_dynamics(self._feet_list, tau=tau, active=stance, armature=armature)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])

@@ -253,6 +253,55 @@ class WbcSim:
                                               1 if armature else 0, self._stream()), "wbc_sim_forward_dynamics")
         return out
 
+    # ---- rigid-body accelerations and contact-constrained forward dynamics (include/wbc_sim.h) --------------------------------------
+    def body_accelerations(self, nudot: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """wbc_sim_body_accelerations on the current stream: f32 [N, 27, 6] = J nudot + Jdot nu of every rigid-body origin (rows
+        linear, angular; world frame). nudot f32 [N, 26] in the convention of inverse_dynamics, None: zeros (the result is Jdot nu)."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        if out is None:
+            out = torch.empty((n, abi.NRB, 6), dtype=torch.float32, device=self.device)
+        assert out.device == self.arena.device and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, abi.NRB, 6)
+        if nudot is not None:
+            assert nudot.device == self.arena.device and nudot.dtype == torch.float32 and nudot.is_contiguous()
+            assert tuple(nudot.shape) == (n, ncol), tuple(nudot.shape)
+        check(self.L.wbc_sim_body_accelerations(self.h, nudot.data_ptr() if nudot is not None else None, out.data_ptr(), self._stream()),
+              "wbc_sim_body_accelerations")
+        return out
+
+    def constrained_dynamics(self, rigid_bodies, tau: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,
+                             acc_des: Optional[torch.Tensor] = None, damping: float = 0.0, armature: bool = False, out=None):
+        """wbc_sim_constrained_dynamics on the current stream: forward dynamics with the origins of the listed rigid bodies (1..5
+        indices) held at the linear accelerations acc_des [N, K, 3] (None: zeros) where active [N, K] (bool or uint8; None: all).
+        Returns (nudot [N, 26], lam [N, K, 3]): lam is the force applied TO the robot at each origin, world axes, exactly 0 where
+        inactive. out: an optional (nudot, lam) pair to fill. The workspace is cached per number of bodies."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        rbs = [int(r) for r in (rigid_bodies.tolist() if isinstance(rigid_bodies, torch.Tensor) else rigid_bodies)]
+        k = len(rbs)
+        assert 1 <= k <= 5, k
+        nudot, lam = out if out is not None else (None, None)
+        if nudot is None:
+            nudot = torch.empty((n, ncol), dtype=torch.float32, device=self.device)
+        if lam is None:
+            lam = torch.empty((n, k, 3), dtype=torch.float32, device=self.device)
+        for t, shape in ((tau, (n, ncol)), (acc_des, (n, k, 3)), (nudot, (n, ncol)), (lam, (n, k, 3))):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, tuple(t.shape)
+        if active is not None:
+            assert active.device == self.arena.device and active.dtype in (torch.bool, torch.uint8) and tuple(active.shape) == (n, k)
+            active = active.contiguous()
+            if active.dtype == torch.bool:
+                active = active.view(torch.uint8)
+        cache = self.__dict__.setdefault("_constr_ws", {})
+        if k not in cache:
+            cache[k] = torch.empty(int(self.L.wbc_sim_constrained_dynamics_workspace_floats(n, k)), dtype=torch.float32, device=self.device)
+        idx = (C.c_int32 * k)(*rbs)
+        check(self.L.wbc_sim_constrained_dynamics(self.h, idx, k, active.data_ptr() if active is not None else None,
+                                                  tau.data_ptr() if tau is not None else None,
+                                                  acc_des.data_ptr() if acc_des is not None else None, float(damping),
+                                                  1 if armature else 0, nudot.data_ptr(), lam.data_ptr(), cache[k].data_ptr(),
+                                                  self._stream()), "wbc_sim_constrained_dynamics")
+        return nudot, lam
+
     def episode_stats(self, scale: float, track_state: torch.Tensor = None, track_cap: int = 0) -> torch.Tensor:
         """Means over the envs that reset in the last step of their finished episode's reward sums [NREW] and metric
         sums [NMETRIC], times `scale`, as one fresh device tensor (WG:743-754 without a host sync). With `track_state`

@@ -663,6 +663,48 @@ int wbc_sim_mass_solve(wbc_sim* sim, const float* rhs, int64_t rhs_env_stride, i
  * away from the joint limits. Fingers, translation, alignment and error codes as wbc_sim_mass_solve (NULL nudot: -1). */
 int wbc_sim_forward_dynamics(wbc_sim* sim, const float* tau, float* nudot, int flags, void* stream);
 
+/* How every rigid body accelerates: acc[e, r] = J[e, r] @ nudot_e + (Jdot nu)[e, r] with J the matrix of wbc_sim_body_dynamics, so
+ * that a task-space law has xddot = J nudot + Jdot nu without differencing two Jacobian refreshes.
+ * nudot  device f32 [N, 26] or NULL (= zeros, the result is then Jdot nu), in the convention of wbc_sim_inverse_dynamics:
+ *        nudot[0:3] is the classical acceleration of the root origin.
+ * acc    device f32 [N, WBC_NRB, 6], the layout of rigid_body_state[..., 7:13]: rows 0:3 the classical world-frame linear
+ *        acceleration of rigid body r's ORIGIN (rb_offset), rows 3:6 its angular acceleration.
+ * Pure kinematics: no gravity and no inertias (WBC_T_BODY_PARAMS is not read). The fingers' entries of nudot and of qd are
+ * ignored. The root POSITION is never read: the result is bit-identical under a translation of the robot. One launch
+ * (wbc_body_accel_kernel). Alignment (4 bytes), error codes (-1 NULL sim / acc or misaligned pointer, nothing written; -3; -2)
+ * and stream handling as wbc_sim_inverse_dynamics. */
+int wbc_sim_body_accelerations(wbc_sim* sim, const float* nudot, float* acc, void* stream);
+
+/* Forward dynamics with the origins of up to WBC_CONSTR_MAX_BODIES rigid bodies held by bilateral constraints on their LINEAR
+ * acceleration (the stance feet of the standard whole-body-control model; angular rows are not offered):
+ *     M nudot + h = tau + sum_r J_r^T lambda_r ,      J_r nudot + (Jdot nu)_r = a_des_r - damping lambda_r ,
+ * J_r the three linear rows of wbc_sim_body_dynamics' Jacobian of listed body r.
+ * rigid_bodies  HOST array of nbodies (1..WBC_CONSTR_MAX_BODIES) rigid-body indices, e.g. the four feet, or the feet and the gripper.
+ * active   device u8 [N, nbodies] or NULL (= all active): the per-env stance mask. An inactive body contributes no constraint, its
+ *          entries of lambda are exactly 0 and its entries of acc_des are never used (a NaN there does not spread).
+ * tau      device f32 [N, 26] or NULL (= zeros), as in wbc_sim_forward_dynamics.
+ * acc_des  device f32 [N, nbodies, 3] or NULL (= zeros): the prescribed world-frame accelerations of the origins.
+ * damping  >= 0, added to the diagonal of the Delassus matrix A = J_c M^-1 J_c^T; 0 gives hard constraints.
+ * flags    0 or WBC_SOLVE_ARMATURE (M + armature, as in wbc_sim_mass_solve).
+ * nudot    device f32 [N, 26], fingers exactly 0. lambda: device f32 [N, nbodies, 3] or NULL (not written).
+ *          lambda_r is the force applied TO the robot at body r's origin in world axes: a standing robot's foot forces point up.
+ * workspace  caller-owned device floats, at least wbc_sim_constrained_dynamics_workspace_floats(N, nbodies) of them (0 for a bad
+ *          argument). Nothing is allocated in the call, so it is safe under stream capture. The sim's bias-force scratch of
+ *          wbc_sim_forward_dynamics is used as well, with the same caveat: one stream at a time per sim.
+ * Four launches on `stream`, no host synchronisation: h (wbc_inverse_dynamics_kernel), the right-hand-side block [J_c^T | tau - h]
+ * and gamma = Jdot nu (wbc_constraint_rhs_kernel), the mass solve with 3 nbodies + 1 right-hand sides, and
+ * wbc_constraint_solve_kernel (A, its Cholesky factorisation, lambda, nudot = a_free + M^-1 J_c^T lambda).
+ * -1 with a message in wbc_last_error(), nothing written: NULL sim / rigid_bodies / nudot / workspace; nbodies outside
+ * 1..WBC_CONSTR_MAX_BODIES; an index outside 0..WBC_NRB-1; two entries that ride on the same moving body (duplicates included:
+ * their rows are linearly dependent); damping negative or not finite; unknown flag bits; a pointer that is not 4-byte aligned.
+ * Any other rank deficiency is the caller's to regularise with damping: for an env whose A is not positive definite that env's
+ * outputs are unspecified, and no other env is affected. -3 / -2 as wbc_sim_mass_solve. */
+#define WBC_CONSTR_MAX_BODIES 5
+size_t wbc_sim_constrained_dynamics_workspace_floats(int num_envs, int nbodies);
+int wbc_sim_constrained_dynamics(wbc_sim* sim, const int32_t* rigid_bodies /* host */, int nbodies, const uint8_t* active,
+                                 const float* tau, const float* acc_des, float damping, int flags, float* nudot, float* lambda,
+                                 float* workspace, void* stream);
+
 /* extras["episode"] of reset_idx (widowGo1.py:743-754): out[0:WBC_NREW] = mean over the envs that reset in the last
  * step of their finished episode's reward sums, out[WBC_NREW:+WBC_NMETRIC] the same for the metric sums, both
  * times `scale` (1 / max_episode_length_s). `out`: device, WBC_NREW + WBC_NMETRIC floats. On a step in which no env reset
