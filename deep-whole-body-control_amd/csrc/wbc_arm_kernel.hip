@@ -1283,3 +1283,211 @@ extern "C" int wbc_sim_constrained_dynamics(wbc_sim* s, const int32_t* rigid_bod
                      acc_des, damping, nbodies, live_cols, n, nudot, lambda);
   return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_constrained_dynamics: launch failed");
 }
+
+// ---- centre of mass, centroidal momentum and its matrix (include/wbc_sim.h: wbc_sim_centroidal) ----------------------------------------
+// With c the centre of mass, d_b = c_b - c and every vector in WORLD axes relative to the root origin (the walk starts from E = R):
+//     h_G = (m v_com ; sum I_b w_b + m_b d_b x v_cb),   hdot_G = (m a_com ; sum I_b al_b + w_b x I_b w_b + m_b d_b x a_cb),
+//     I_G = sum I_b + m_b (|d_b|^2 1 - d_b d_b^T).
+// sum m_b d_b x X vanishes for any X common to all bodies, so the walk carries each body's velocity and classical acceleration RELATIVE
+// to the root origin's linear motion (v_root and nudot[0:3] never enter it) at the body's own origin, as ba_walk does; no angular row
+// then holds a term that grows with |v_root| or |nudot[0:3]|, and the linear rows add m v_root and m nudot[0:3] at the end.
+// CM_EPW envs per 64-lane workgroup, one per lane group, three LDS hand-overs:
+//  1) lane b = moving body b walks root -> b in registers and leaves (m, c_b - its origin, its origin, its joint axis, I_b about c_b)
+//     in LDS;
+//  2) every lane sums (m, m c) over the bodies; lane b leaves its body's share of the 18 sums (m_b v_cb, m_b a_cb, the two angular
+//     shares, I_G's) in LDS; lane t sums share t, writes the entries of com / mom / inertia it completes and leaves the sum in LDS;
+//  3) lane c = column c of A_G: (m 1 ; 0) for v_root, (-m [c]x ; I_G) for omega_root, and for a joint the composite (m, m c, I) of the
+//     subtree it moves ABOUT THE JOINT'S OWN ORIGIN o, as wbc_mass_solve_kernel forms it: f = a x (m c)_s, n_o = I_s a, moved to the
+//     centre of mass as n_o + (o - c) x f. A wrist column is then not the difference of two moments about a far point; the levers
+//     are (o_d - o) + (c_d - o_d), so that the joint's own body enters with its model lever and not with a difference of two
+//     root-relative points (fp32 emulation of A_G: 31 x 2^-24 of the magnitude this way, 90 with c_d - o).
+// A single-wavefront workgroup: the __syncthreads() order the LDS traffic and cost no barrier instruction. The root position is never read.
+#ifndef CM_EPW
+#define CM_EPW 2                                // envs per workgroup: 2, or 1 (-DCM_EPW=1, the variant DESIGN.md compares with)
+#endif
+static_assert(CM_EPW == 1 || CM_EPW == 2, "one env per 64 lanes or one per 32-lane half");
+#define CM_BT 16                                // floats per body: m 0, c_b - origin 1..3, origin 4..6, joint axis 7..9, I_b about c_b 10..15
+#define CM_NS 18                                // sums over the bodies: m v 0..2, m a 3..5, k_G 6..8, kdot_G 9..11, I_G 12..17
+#define CM_COM 9
+#define CM_MOM 12
+#define CM_INR 7
+static_assert(WBC_NB <= 64 / CM_EPW && BD_NCOL <= 64 / CM_EPW && CM_NS + 4 <= 64 / CM_EPW, "lanes");
+
+extern "C" __global__ void __launch_bounds__(64) wbc_centroidal_kernel(IdConst K, const float* __restrict__ root, const float* __restrict__ dofs,
+                                                                      const float* __restrict__ body_params,
+                                                                      const float* __restrict__ nudot, int n, float* __restrict__ com,
+                                                                      float* __restrict__ mom, float* __restrict__ cmm,
+                                                                      float* __restrict__ inertia) {
+  __shared__ float sB[CM_EPW][WBC_NB][CM_BT];
+  __shared__ float sD[CM_EPW][WBC_NB][CM_NS];
+  __shared__ float sSum[CM_EPW][CM_NS];
+  const int half = CM_EPW == 2 ? threadIdx.x >> 5 : 0, lane = CM_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
+  const int env = blockIdx.x * CM_EPW + half;
+  const bool live = env < n;
+  const size_t e = live ? env : n - 1;             // the idle half of the last workgroup recomputes the last env and stores nothing
+  float (*B)[CM_BT] = sB[half];
+  f3 vc = mk3(0.f, 0.f, 0.f), ac = vc, Lw = vc, Nw = vc;   // lane b: relative velocity / acceleration of c_b, I_b w_b, I_b al_b + w_b x I_b w_b
+
+  if (lane < WBC_NB) {
+    const int b = lane;
+    float E[9];
+    quat_to_mat(root + e * 26 + 3, E);
+    f3 p = mk3(0.f, 0.f, 0.f), Sw = p, vo = p, ao = p, aw = p;
+    f3 w = ld3(root + e * 26 + 10);
+    if (nudot) aw = ld3(nudot + e * BD_NCOL + 3);
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
+      const int a = K.path[b][k];
+      if (a < 0) break;
+      const int ax = K.axis[a], d = K.dof[a];
+      const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
+      float s, c;
+      sincosf(dofs[e * (2 * WBC_NDOF) + 2 * d], &s, &c);
+      const float t = 1.f - c;
+      const float Q[9] = {c + t * ux * ux, t * ux * uy - s * uz, t * ux * uz + s * uy,
+                          t * uy * ux + s * uz, c + t * uy * uy, t * uy * uz - s * ux,
+                          t * uz * ux - s * uy, t * uz * uy + s * ux, c + t * uz * uz};
+      const f3 r = mat_mul(E, mk3(K.joint_xyz[a][0], K.joint_xyz[a][1], K.joint_xyz[a][2]));    // (E, p) <- (E Rot_a, p + E xyz_a)
+      p = p + r;
+      vo = vo + cross(w, r);                                   // the parent's w and aw carry its origin's motion to the joint
+      ao = ao + cross(aw, r) + cross(w, cross(w, r));
+      float En[9];
+#pragma unroll
+      for (int r_ = 0; r_ < 3; ++r_)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) En[r_ * 3 + j] = E[r_ * 3] * Q[j] + E[r_ * 3 + 1] * Q[3 + j] + E[r_ * 3 + 2] * Q[6 + j];
+#pragma unroll
+      for (int j = 0; j < 9; ++j) E[j] = En[j];
+      Sw = mat_mul(E, mk3(ux, uy, uz));
+      const float qd = dofs[e * (2 * WBC_NDOF) + 2 * d + 1], qdd = nudot ? nudot[e * BD_NCOL + 6 + d] : 0.f;
+      const f3 jw = Sw * qd;                                   // aw += S qdd + w x (S qd), then w += S qd
+      aw = aw + Sw * qdd + cross(w, jw);
+      w = w + jw;
+    }
+    // the per-env root composite and gripper body (body_params), the model's otherwise
+    float m = K.mass[b], cm[3] = {K.com[b][0], K.com[b][1], K.com[b][2]}, I6[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) I6[j] = K.inertia[b][j];
+    const int slot = b == 0 ? 0 : (b == K.gripper_body ? 10 : -1);
+    if (slot >= 0) {
+      const float* bp = body_params + e * 20 + slot;
+      m = bp[0];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) cm[j] = bp[1 + j];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) I6[j] = bp[4 + j];
+    }
+    const float Ib[9] = {I6[0], I6[3], I6[4], I6[3], I6[1], I6[5], I6[4], I6[5], I6[2]};
+    float EI[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) EI[r * 3 + k] = E[r * 3] * Ib[k] + E[r * 3 + 1] * Ib[3 + k] + E[r * 3 + 2] * Ib[6 + k];
+    auto ibar = [&](int r, int k) { return EI[r * 3] * E[k * 3] + EI[r * 3 + 1] * E[k * 3 + 1] + EI[r * 3 + 2] * E[k * 3 + 2]; };
+    const float Iw[9] = {ibar(0, 0), ibar(0, 1), ibar(0, 2), ibar(0, 1), ibar(1, 1), ibar(1, 2), ibar(0, 2), ibar(1, 2), ibar(2, 2)};
+    const f3 rc = mat_mul(E, mk3(cm[0], cm[1], cm[2]));
+    vc = vo + cross(w, rc);
+    ac = ao + cross(aw, rc) + cross(w, cross(w, rc));
+    Lw = mat_mul(Iw, w);
+    Nw = mat_mul(Iw, aw) + cross(w, Lw);
+    float* o = B[b];
+    o[0] = m; st3(o + 1, rc); st3(o + 4, p); st3(o + 7, Sw);
+    o[10] = Iw[0]; o[11] = Iw[4]; o[12] = Iw[8]; o[13] = Iw[1]; o[14] = Iw[2]; o[15] = Iw[5];
+  }
+  __syncthreads();
+
+  float mt = 0.f;
+  f3 mc = mk3(0.f, 0.f, 0.f);
+  for (int d = 0; d < WBC_NB; ++d) { mt += B[d][0]; mc = mc + B[d][0] * (ld3(B[d] + 4) + ld3(B[d] + 1)); }
+  const float im = 1.f / mt;
+  const f3 cg = mc * im;
+  if (lane < WBC_NB) {
+    const float* q = B[lane];
+    const float m = q[0];
+    const f3 d = (ld3(q + 4) + ld3(q + 1)) - cg, P = m * vc, F = m * ac;
+    const float dd = dot(d, d);
+    float* o = sD[half][lane];
+    st3(o, P); st3(o + 3, F); st3(o + 6, Lw + cross(d, P)); st3(o + 9, Nw + cross(d, F));
+    o[12] = q[10] + m * (dd - d.x * d.x); o[13] = q[11] + m * (dd - d.y * d.y); o[14] = q[12] + m * (dd - d.z * d.z);
+    o[15] = q[13] - m * d.x * d.y; o[16] = q[14] - m * d.x * d.z; o[17] = q[15] - m * d.y * d.z;
+  }
+  __syncthreads();
+
+  if (lane < CM_NS) {
+    const int t = lane, j = t % 3;
+    float s = 0.f;
+    for (int d = 0; d < WBC_NB; ++d) s += sD[half][d][t];
+    sSum[half][t] = s;
+    if (live) {
+      if (t < 6) {                                             // linear rows: the root origin's own motion comes in here
+        const bool vel = t < 3;
+        const float x0 = vel ? root[e * 26 + 7 + j] : (nudot ? nudot[e * BD_NCOL + j] : 0.f);
+        if (com) com[e * CM_COM + 3 + t] = x0 + s * im;
+        if (mom) mom[e * CM_MOM + (vel ? 0 : 6) + j] = mt * x0 + s;
+      } else if (t < 12) {
+        if (mom) mom[e * CM_MOM + (t < 9 ? 3 : 9) + j] = s;
+      } else if (inertia) {
+        inertia[e * CM_INR + 1 + (t - 12)] = s;
+      }
+    }
+  } else if (lane < CM_NS + 3) {
+    const int j = lane - CM_NS;
+    if (live && com) com[e * CM_COM + j] = j == 0 ? cg.x : j == 1 ? cg.y : cg.z;
+  } else if (lane == CM_NS + 3) {
+    if (live && inertia) inertia[e * CM_INR] = mt;
+  }
+  if (!cmm) return;
+  __syncthreads();
+
+  if (lane < BD_NCOL && live) {
+    const int c = lane, j = c < 3 ? c : c - 3;
+    const f3 ej = mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f);
+    f3 lin = mk3(0.f, 0.f, 0.f), ang = lin;
+    if (c < 3) {
+      lin = mt * ej;                                           // exactly m on the diagonal, exactly 0 elsewhere
+    } else if (c < 6) {
+      const float* I = sSum[half] + 12;                        // xx yy zz xy xz yz
+      lin = cross(ej, mc);
+      ang = j == 0 ? mk3(I[0], I[3], I[4]) : j == 1 ? mk3(I[3], I[1], I[5]) : mk3(I[4], I[5], I[2]);
+    } else {
+      const int b = K.col_body[c - 6];
+      if (b >= 0) {
+        const f3 P = ld3(B[b] + 4), a = ld3(B[b] + 7);
+        float xx = 0.f, yy = 0.f, zz = 0.f, xy = 0.f, xz = 0.f, yz = 0.f;
+        f3 h = mk3(0.f, 0.f, 0.f);
+        for (int d = 0; d < WBC_NB; ++d)
+          if ((K.anc[d] >> b) & 1u) {
+            const float* q = B[d];
+            const float md = q[0];
+            const f3 r = (ld3(q + 4) - P) + ld3(q + 1);      // the joint's own body: exactly its model lever
+            const float rr = dot(r, r);
+            h = h + md * r;
+            xx += q[10] + md * (rr - r.x * r.x); yy += q[11] + md * (rr - r.y * r.y); zz += q[12] + md * (rr - r.z * r.z);
+            xy += q[13] - md * r.x * r.y; xz += q[14] - md * r.x * r.z; yz += q[15] - md * r.y * r.z;
+          }
+        lin = cross(a, h);
+        ang = mk3(xx * a.x + xy * a.y + xz * a.z, xy * a.x + yy * a.y + yz * a.z, xz * a.x + yz * a.y + zz * a.z) + cross(P - cg, lin);
+      }
+    }
+    float* o = cmm + e * (6 * BD_NCOL) + c;
+    o[0] = lin.x; o[BD_NCOL] = lin.y; o[2 * BD_NCOL] = lin.z;
+    o[3 * BD_NCOL] = ang.x; o[4 * BD_NCOL] = ang.y; o[5 * BD_NCOL] = ang.z;
+  }
+}
+
+// nudot (device f32 [N,26] or NULL = zeros); com [N,9], mom [N,12], cmm [N,6,26], inertia [N,7] (device f32, caller-owned, any may be NULL,
+// not all): include/wbc_sim.h.
+extern "C" int wbc_sim_centroidal(wbc_sim* s, const float* nudot, float* com, float* mom, float* cmm, float* inertia, void* stream) {
+  StreamDeviceGuard sdg(stream);
+  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_centroidal: sim is NULL");
+  if (!com && !mom && !cmm && !inertia) return wbc_sim_internal_fail(-1, "wbc_sim_centroidal: com, mom, cmm and inertia are all NULL");
+  if (((uintptr_t)nudot | (uintptr_t)com | (uintptr_t)mom | (uintptr_t)cmm | (uintptr_t)inertia) & 3u)
+    return wbc_sim_internal_fail(-1, "wbc_sim_centroidal: nudot / com / mom / cmm / inertia must be 4-byte aligned");
+  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_centroidal: no sim state");
+  if (n <= 0) return 0;
+  IdConst K;
+  if (id_const_fill(hc, K) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_centroidal: the model's tree is not one the kernel walks");
+  hipLaunchKernelGGL(wbc_centroidal_kernel, dim3((n + CM_EPW - 1) / CM_EPW), dim3(64), 0, (hipStream_t)stream, K, root, dofs, bp, nudot, n, com, mom,
+                     cmm, inertia);
+  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_centroidal: launch failed");
+}

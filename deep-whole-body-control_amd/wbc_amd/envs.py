@@ -537,6 +537,28 @@ class WidowGo1(LeggedRobot):
             self._feet_list = [int(i) for i in self.feet_indices.tolist()]
         return self.sim.constrained_dynamics(self._feet_list, tau=tau, active=stance, armature=armature)
 
+    # ---- centre of mass and centroidal momentum (no counterpart in the reference): one launch, include/wbc_sim.h: wbc_sim_centroidal ----
+    def centre_of_mass(self):
+        """(position [N, 3], velocity [N, 3]) of the robot's centre of mass in the world frame: the root position plus the kernel's
+        offset from the root origin (the kernel itself never reads the position), and v_com."""
+        com = self.sim.centroidal()[0]
+        return self.root_states[:, 0:3] + com[:, 0:3], com[:, 3:6]
+
+    def centroidal_momentum(self, nudot: torch.Tensor = None):
+        """(h_G [N, 6], hdot_G [N, 6]): linear momentum and angular momentum about the centre of mass (world axes), and their rate
+        A_G nudot + Adot_G nu -- the net external wrench about the centre of mass, weight included. nudot None: zeros (Adot_G nu)."""
+        mom = self.sim.centroidal(nudot)[1]
+        return mom[:, 0:6], mom[:, 6:12]
+
+    def centroidal_momentum_matrix(self) -> torch.Tensor:
+        """A fresh f32 [N, 6, 26] A_G with h_G = A_G nu in the coordinates of mm_whole; A_G[:, 0:3] / mass is the centre-of-mass Jacobian."""
+        return self.sim.centroidal()[2]
+
+    def centroidal_inertia(self):
+        """(mass [N], I_G [N, 3, 3]): the total mass and the locked centroidal inertia in world axes."""
+        inr = self.sim.centroidal()[3]
+        return inr[:, 0], inr[:, [1, 4, 5, 4, 2, 6, 5, 6, 3]].view(-1, 3, 3)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])

@@ -302,6 +302,23 @@ class WbcSim:
                                                   self._stream()), "wbc_sim_constrained_dynamics")
         return nudot, lam
 
+    # ---- centre of mass, centroidal momentum and its matrix (include/wbc_sim.h: wbc_sim_centroidal) ----------------------------------
+    def centroidal(self, nudot: Optional[torch.Tensor] = None, com: Optional[torch.Tensor] = None, mom: Optional[torch.Tensor] = None,
+                   cmm: Optional[torch.Tensor] = None, inertia: Optional[torch.Tensor] = None):
+        """One wbc_sim_centroidal launch on the current stream. Returns (com [N, 9], mom [N, 12], cmm [N, 6, 26], inertia [N, 7]):
+        (c - p_root, v_com, a_com), (h_G, hdot_G), A_G and (m, I_G as xx yy zz xy xz yz), world axes, angular rows about the centre of
+        mass. Outputs that are not passed are allocated; nudot f32 [N, 26] in the convention of inverse_dynamics, None: zeros (a_com
+        and hdot_G are then the bias parts). A launch that writes fewer outputs goes through the C-ABI with NULL pointers."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        shapes = ((n, 9), (n, 12), (n, 6, ncol), (n, 7))
+        outs = [torch.empty(sh, dtype=torch.float32, device=self.device) if t is None else t for t, sh in zip((com, mom, cmm, inertia), shapes)]
+        for t, sh in zip([nudot] + outs, ((n, ncol),) + shapes):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        check(self.L.wbc_sim_centroidal(self.h, nudot.data_ptr() if nudot is not None else None, *[t.data_ptr() for t in outs],
+                                        self._stream()), "wbc_sim_centroidal")
+        return tuple(outs)
+
     def episode_stats(self, scale: float, track_state: torch.Tensor = None, track_cap: int = 0) -> torch.Tensor:
         """Means over the envs that reset in the last step of their finished episode's reward sums [NREW] and metric
         sums [NMETRIC], times `scale`, as one fresh device tensor (WG:743-754 without a host sync). With `track_state`

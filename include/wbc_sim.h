@@ -97,8 +97,9 @@ typedef struct {
    * and COUNTED (tensor WBC_T_DROPPED_HITS: per env, accumulated over the substeps; the tests assert it stays 0).
    * Primitives of the candidates, all in frame F from the cached sphere centres (cp_sph: the compact index of a robot sphere):
    *   limbs -- capsules between two sphere centres (thigh: hip-side end to knee, r 0.017; calf: knee to foot, r 0.008, with its end
-   *   spheres knee r 0.02 / foot r 0.02; upper arm: shoulder joint to elbow, forearm: elbow to wrist, r 0.025; hand: wrist to gripper
-   *   tip, r 0.02; equal end indices would make a single sphere); kind WBC_PR_LIMBS tests limb pr_a against
+   *   spheres knee r 0.02 / foot r 0.02; upper arm: shoulder joint to elbow, forearm: elbow to wrist, hand: wrist to gripper tip, with
+   *   the radii fitted to the arm's meshes that wbc_amd/assets/arm_primitives.json records (r 0.040 / 0.025 / 0.0275; that file is the
+   *   single source); equal end indices would make a single sphere); kind WBC_PR_LIMBS tests limb pr_a against
    *   limb pr_b as the union of shaft and end spheres (deepest feature pair wins: one contact per limb pair);
    *   kind WBC_PR_SPHERE_BOX tests robot sphere pr_a against the free box (knees, shins, trunk corners, wrist, elbow). */
   int32_t ncp;
@@ -704,6 +705,28 @@ size_t wbc_sim_constrained_dynamics_workspace_floats(int num_envs, int nbodies);
 int wbc_sim_constrained_dynamics(wbc_sim* sim, const int32_t* rigid_bodies /* host */, int nbodies, const uint8_t* active,
                                  const float* tau, const float* acc_des, float damping, int flags, float* nudot, float* lambda,
                                  float* workspace, void* stream);
+
+/* Centre of mass, centroidal momentum, its rate, the centroidal momentum matrix and the locked centroidal inertia of the robot, in the
+ * coordinates of wbc_sim_body_dynamics (nu = (v_root, omega_root, qd), world axes, 26 columns) with the inertias of the per-env
+ * WBC_T_BODY_PARAMS, from the sim's current root / DoF state. One launch (wbc_centroidal_kernel).
+ * nudot    device f32 [N, 26] or NULL (= zeros), in the convention of wbc_sim_inverse_dynamics: nudot[0:3] is the classical
+ *          acceleration of the root origin.
+ * com      device f32 [N, 9]: c - p_root, the centre of mass relative to the root origin (world axes; add WBC_T_ROOT_STATES[:, 0, 0:3]
+ *          for its world position); v_com; a_com = J_com nudot + Jdot_com nu (NULL nudot: the bias part Jdot_com nu).
+ * mom      device f32 [N, 12]: h_G = (m v_com ; k_G), k_G the angular momentum about the centre of mass in world axes; then
+ *          hdot_G = A_G nudot + Adot_G nu (NULL nudot: Adot_G nu). hdot_G is kinematics times inertia and reads no gravity: along a
+ *          motion of the robot it equals the net external wrench about the centre of mass, the weight included.
+ * cmm      device f32 [N, 6, 26] = A_G, h_G = A_G nu: rows 0:3 linear, rows 3:6 angular about the centre of mass. The block
+ *          [0:3, 0:3] is exactly m on the diagonal and exactly 0 off it, the block [3:6, 0:3] is exactly 0, and the locked fingers'
+ *          columns 24, 25 are exactly 0. The centre-of-mass Jacobian is cmm[:, 0:3, :] / m.
+ * inertia  device f32 [N, 7]: the total mass m, then the locked centroidal inertia I_G = A_G[3:6, 3:6] in world axes in the model's
+ *          six-value order xx, yy, zz, xy, xz, yz.
+ * Any output may be NULL and is then not written; not all four. Every pointer needs 4-byte alignment only. The fingers' entries of
+ * nudot and of qd are ignored. The root POSITION is never read: every output is bit-identical under a translation of the robot, and
+ * the angular rows hold no term that grows with |v_root| or |nudot[0:3]|. Nothing is allocated in the call, so it is safe under
+ * stream capture. Error codes (-1 NULL sim, all outputs NULL or a misaligned pointer, nothing written; -3; -2) and stream handling as
+ * wbc_sim_inverse_dynamics. */
+int wbc_sim_centroidal(wbc_sim* sim, const float* nudot, float* com, float* mom, float* cmm, float* inertia, void* stream);
 
 /* extras["episode"] of reset_idx (widowGo1.py:743-754): out[0:WBC_NREW] = mean over the envs that reset in the last
  * step of their finished episode's reward sums, out[WBC_NREW:+WBC_NMETRIC] the same for the metric sums, both
