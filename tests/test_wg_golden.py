@@ -83,8 +83,6 @@ def compare(tag, got, ref, checks, exact=EXACT):
     worst = {}
     for name, atol, rtol in checks:
         a, b = np.asarray(got(name), dtype=np.float64), np.asarray(ref[name], dtype=np.float64)
-        if name == "GOAL_STATE":
-            pass
         np.testing.assert_allclose(a, b, atol=atol, rtol=rtol, err_msg=f"{tag} {name}")
         worst[name] = float(np.max(np.abs(a - b))) if a.size else 0.0
     return worst
