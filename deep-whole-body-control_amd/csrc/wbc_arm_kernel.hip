@@ -1491,3 +1491,316 @@ extern "C" int wbc_sim_centroidal(wbc_sim* s, const float* nudot, float* com, fl
                      cmm, inertia);
   return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_centroidal: launch failed");
 }
+
+// ---- analytic derivatives of inverse and forward dynamics (include/wbc_sim.h: wbc_sim_inverse_dynamics_derivatives) ----------------------
+// The tangent of wbc_inverse_dynamics_kernel's recursion (its walk in classical form), carried in forward mode: a lane owns one (moving body d, direction x) pair,
+// redoes d's path walk root -> d with every quantity paired with its derivative along x, and leaves d(force about F's origin), d(own-joint
+// torques) and d(m c) in LDS; lanes over the entries (row c, direction x) then sum the subtrees with the ancestor masks and add dS_c . F_c,
+// which is closed form (a joint above c turns c's axis and origin about its own). A body depends only on the root directions and on the
+// joints of its own path, so for this robot 102 pairs are live per output (19 x 3 root directions + 45 path joints): two rounds of 64 lanes.
+// The root's LINEAR velocity is not read at all: the walk carries angular velocities and classical accelerations, which hold no linear
+// velocity (Galilean invariance), and those columns are written as literal zeros, as are
+// the translation columns (the root position is not read either), the fingers and every pair of joints on different chains.
+// Root rotation (world rotation vector, world components of nu / nudot held fixed): in F every root vector w, wdot, vdot, g turns by
+// -phi x (.), phi = R^T e_j, the joints' S do not change, and the world rows 0:6 of the result turn by e_j x (.).
+// One env per 64-lane workgroup; 17.4 KB of LDS (8 workgroups per CU).
+#define DD_NT 18                                // tangent slots per body: root rotation 0..2, root omega 3..5, q of path[b][i] 6 + i, qd of path[b][i] 12 + i
+#define DD_PT 12                                // floats per (body, slot): d(moment about F's origin) 0..2, d(force) 3..5, d(own-joint torques) 6, 7, d(m c) 8..10
+#define DD_MAXPAIR (WBC_NB * (3 + WBC_MAX_DEPTH))
+#define DD_MENV (BD_NCOL * BD_NCOL)
+struct DdConst {
+  IdConst K;
+  int32_t depth[WBC_NB];                        // joints between the root and b
+  int32_t npair;                                // live (body, direction) pairs of one output
+  uint8_t pair_body[DD_MAXPAIR], pair_u[DD_MAXPAIR];   // u: 0..2 a root direction, 3 + i the joint path[b][i]
+};
+struct d3 { f3 v, d; };                         // a vector and its derivative along the lane's direction
+struct du { float v, d; };
+__device__ __forceinline__ d3 mkd3(f3 v, f3 d) { d3 r; r.v = v; r.d = d; return r; }
+__device__ __forceinline__ d3 operator+(d3 a, d3 b) { return mkd3(a.v + b.v, a.d + b.d); }
+__device__ __forceinline__ d3 operator*(d3 a, du s) { return mkd3(a.v * s.v, a.d * s.v + a.v * s.d); }
+__device__ __forceinline__ d3 operator*(d3 a, float s) { return mkd3(a.v * s, a.d * s); }
+__device__ __forceinline__ d3 cross(d3 a, d3 b) { return mkd3(cross(a.v, b.v), cross(a.d, b.v) + cross(a.v, b.d)); }
+__device__ __forceinline__ du dot(d3 a, d3 b) { du r; r.v = dot(a.v, b.v); r.d = dot(a.d, b.v) + dot(a.v, b.d); return r; }
+__device__ __forceinline__ d3 mat_mul(const float* M, const float* dM, d3 x) { return mkd3(mat_mul(M, x.v), mat_mul(dM, x.v) + mat_mul(M, x.d)); }
+__device__ __forceinline__ d3 matT_mul(const float* M, const float* dM, d3 x) { return mkd3(matT_mul(M, x.v), matT_mul(dM, x.v) + matT_mul(M, x.d)); }
+
+extern "C" __global__ void __launch_bounds__(64) wbc_dynamics_derivatives_kernel(DdConst C, const float* __restrict__ root,
+                                                                                const float* __restrict__ dofs,
+                                                                                const float* __restrict__ body_params,
+                                                                                const float* __restrict__ nudot, int n,
+                                                                                float* __restrict__ out_dq, float* __restrict__ out_dnu,
+                                                                                float* __restrict__ eye, int transposed, int negate) {
+  __shared__ __align__(16) float sT[WBC_NB][DD_NT][DD_PT];
+  __shared__ __align__(16) float sF[WBC_NB][12];  // per body: moment about F's origin 0..2, force 3..5 (gravity excluded), m 8, m c 9..11
+  __shared__ float sS[WBC_NB][6];                  // the body's joint in F: axis, origin
+  const IdConst& K = C.K;
+  const int lane = threadIdx.x;
+  const size_t e = blockIdx.x;
+  if (eye && blockIdx.x == 0)
+    for (int idx = lane; idx < DD_MENV; idx += 64) eye[idx] = idx / BD_NCOL == idx % BD_NCOL ? 1.f : 0.f;
+  if (!out_dq && !out_dnu) return;
+  const f3 zero = mk3(0.f, 0.f, 0.f);
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+  const f3 gF = matT_mul(R, mk3(K.gravity[0], K.gravity[1], K.gravity[2]));
+  const f3 w0 = matT_mul(R, ld3(root + e * 26 + 10));
+  const f3 al0 = nudot ? matT_mul(R, ld3(nudot + e * BD_NCOL + 3)) : zero, a0 = nudot ? matT_mul(R, ld3(nudot + e * BD_NCOL)) : zero;
+
+  for (int which = 0; which < 2; ++which) {
+    if (!(which ? out_dnu : out_dq)) continue;
+    for (int pi = lane; pi < C.npair; pi += 64) {
+      const int b = C.pair_body[pi], u = C.pair_u[pi];
+      const int t = u < 3 ? u + 3 * which : 3 + u + 6 * which;
+      // seeds of the root directions: rotation turns every root vector by -phi x (.), omega_j moves the angular velocity alone
+      const f3 phi = matT_mul(R, mk3(u == 0 ? 1.f : 0.f, u == 1 ? 1.f : 0.f, u == 2 ? 1.f : 0.f));
+      const float rot = t < 3 ? 1.f : 0.f, omg = t >= 3 && t < 6 ? 1.f : 0.f;
+      const d3 g = mkd3(gF, cross(gF, phi) * rot);
+      // angular velocity, angular acceleration and the CLASSICAL acceleration of the body's own origin, in F's axes (the shape of ba_walk):
+      // every later lever is then a link offset or a centre-of-mass offset, never the distance to the base origin
+      d3 vw = mkd3(w0, cross(w0, phi) * rot + phi * omg);
+      d3 aw = mkd3(al0, cross(al0, phi) * rot), ao = mkd3(a0, cross(a0, phi) * rot);
+      float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, dE[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      d3 p = mkd3(zero, zero), Sw = p;
+      for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
+        const int a = K.path[b][k];
+        if (a < 0) break;
+        const int ax = K.axis[a], d = K.dof[a];
+        const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
+        const float dq = t == 6 + k ? 1.f : 0.f;
+        float s, c;
+        sincosf(dofs[e * (2 * WBC_NDOF) + 2 * d], &s, &c);
+        const float tc = 1.f - c, ds = c * dq, dc = -s * dq, dt = s * dq;
+        const float Q[9] = {c + tc * ux * ux, tc * ux * uy - s * uz, tc * ux * uz + s * uy,
+                            tc * uy * ux + s * uz, c + tc * uy * uy, tc * uy * uz - s * ux,
+                            tc * uz * ux - s * uy, tc * uz * uy + s * ux, c + tc * uz * uz};
+        const float dQ[9] = {dc + dt * ux * ux, dt * ux * uy - ds * uz, dt * ux * uz + ds * uy,
+                             dt * uy * ux + ds * uz, dc + dt * uy * uy, dt * uy * uz - ds * ux,
+                             dt * uz * ux - ds * uy, dt * uz * uy + ds * ux, dc + dt * uz * uz};
+        const f3 xyz = mk3(K.joint_xyz[a][0], K.joint_xyz[a][1], K.joint_xyz[a][2]);
+        const d3 r = mkd3(mat_mul(E, xyz), mat_mul(dE, xyz));   // a_o <- a_o + alpha x r + w x (w x r) with the parent's alpha, w; (E, p) <- (E Rot_a, p + E xyz_a)
+        ao = ao + cross(aw, r) + cross(vw, cross(vw, r));
+        p = p + r;
+        float En[9], dEn[9];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            En[r * 3 + j] = E[r * 3] * Q[j] + E[r * 3 + 1] * Q[3 + j] + E[r * 3 + 2] * Q[6 + j];
+            dEn[r * 3 + j] = (dE[r * 3] * Q[j] + dE[r * 3 + 1] * Q[3 + j] + dE[r * 3 + 2] * Q[6 + j]) +
+                             (E[r * 3] * dQ[j] + E[r * 3 + 1] * dQ[3 + j] + E[r * 3 + 2] * dQ[6 + j]);
+          }
+#pragma unroll
+        for (int j = 0; j < 9; ++j) { E[j] = En[j]; dE[j] = dEn[j]; }
+        const f3 uu = mk3(ux, uy, uz);
+        Sw = mkd3(mat_mul(E, uu), mat_mul(dE, uu));
+        du qd;
+        qd.v = dofs[e * (2 * WBC_NDOF) + 2 * d + 1];
+        qd.d = t == 12 + k ? 1.f : 0.f;
+        const float qdd = nudot ? nudot[e * BD_NCOL + 6 + d] : 0.f;
+        const d3 jw = Sw * qd;                                 // alpha += axis qdd + w x (axis qd), then w += axis qd
+        aw = aw + Sw * qdd + cross(vw, jw);
+        vw = vw + jw;
+      }
+      float m = K.mass[b], com[3] = {K.com[b][0], K.com[b][1], K.com[b][2]}, I6[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) I6[j] = K.inertia[b][j];
+      const int slot = b == 0 ? 0 : (b == K.gripper_body ? 10 : -1);
+      if (slot >= 0) {
+        const float* bp = body_params + e * 20 + slot;
+        m = bp[0];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) I6[j] = bp[4 + j];
+      }
+      // as wbc_inverse_dynamics_kernel: the body's own joint sees the body's own force and weight through the lever in BODY axes
+      const int axb = K.axis[b];
+      const f3 cm = mk3(com[0], com[1], com[2]), ub = mk3(axb == 0 ? 1.f : 0.f, axb == 1 ? 1.f : 0.f, axb == 2 ? 1.f : 0.f);
+      const f3 lev = cross(cm, ub);
+      const d3 cmd = mkd3(cm, zero), ubd = mkd3(ub, zero), levd = mkd3(lev, zero);
+      const d3 rc = mat_mul(E, dE, cmd), Cc = p + rc;
+      const d3 fl = (ao + cross(aw, rc) + cross(vw, cross(vw, rc))) * m;
+      const d3 wl = matT_mul(E, dE, vw), al = matT_mul(E, dE, aw);
+      const float Ib[9] = {I6[0], I6[3], I6[4], I6[3], I6[1], I6[5], I6[4], I6[5], I6[2]};
+      const d3 Iw = mkd3(mat_mul(Ib, wl.v), mat_mul(Ib, wl.d));
+      const d3 ncl = mkd3(mat_mul(Ib, al.v), mat_mul(Ib, al.d)) + cross(wl, Iw);
+      const d3 nF = mat_mul(E, dE, ncl) + cross(Cc, fl);
+      const float o6d = dot(ubd, ncl).d - dot(levd, matT_mul(E, dE, fl)).d;
+      const float o7d = m * dot(matT_mul(E, dE, g), levd).d;
+      float* o = sT[b][t];
+      st3(o, nF.d); st3(o + 3, fl.d); o[6] = o6d; o[7] = o7d; st3(o + 8, Cc.d * m); o[11] = 0.f;
+      if (u == 0) {                                            // every body has this pair: it leaves the primal quantities too
+        float* f = sF[b];
+        st3(f, nF.v); st3(f + 3, fl.v); f[6] = 0.f; f[7] = 0.f; f[8] = m; st3(f + 9, Cc.v * m);
+        st3(sS[b], Sw.v); st3(sS[b] + 3, p.v);
+      }
+    }
+  }
+  __syncthreads();
+
+  for (int which = 0; which < 2; ++which) {
+    float* __restrict__ out = which ? out_dnu : out_dq;
+    if (!out) continue;
+    for (int idx = lane; idx < DD_MENV; idx += 64) {
+      const int i = idx / BD_NCOL, j = idx - i * BD_NCOL;
+      const int c = transposed ? j : i, x = transposed ? i : j;   // row of tau, direction
+      const int rb = c < 6 ? 0 : K.col_body[c - 6], cb = x < 6 ? 0 : K.col_body[x - 6];
+      float val = 0.f;
+      // live: neither a finger nor a root translation / linear-velocity direction, and the two on one chain
+      if (rb >= 0 && cb >= 0 && x >= 3 && (((K.anc[rb] >> cb) & 1u) || ((K.anc[cb] >> rb) & 1u))) {
+        const int tr = x < 6 ? x - 3 + 3 * which : 6 + 6 * which + C.depth[cb] - 1;
+        const int jr = c < 3 ? c : c - 3;
+        const bool theta = which == 0 && x < 6;
+        f3 Np = zero, Fp = zero, hs = zero, dN = zero, dF = zero, dH = zero;
+        float ms = 0.f;
+        for (int d = 0; d < WBC_NB; ++d) {
+          const bool inC = ((K.anc[d] >> rb) & 1u) && (c < 6 || d != rb);   // a joint's own body comes in through slots 6, 7
+          if (!inC) continue;
+          const float4* f4 = reinterpret_cast<const float4*>(sF[d]);
+          const float4 u0 = f4[0], u1 = f4[1], u2 = f4[2];
+          Np = Np + mk3(u0.x, u0.y, u0.z); Fp = Fp + mk3(u0.w, u1.x, u1.y);
+          ms += u2.x; hs = hs + mk3(u2.y, u2.z, u2.w);
+          if ((K.anc[d] >> cb) & 1u) {                         // d is moved by the direction: the pair (d, tr) was written
+            const float4* t4 = reinterpret_cast<const float4*>(sT[d][tr]);
+            const float4 v0 = t4[0], v1 = t4[1], v2 = t4[2];
+            dN = dN + mk3(v0.x, v0.y, v0.z); dF = dF + mk3(v0.w, v1.x, v1.y);
+            dH = dH + mk3(v2.x, v2.y, v2.z);
+          }
+        }
+        const f3 phi = matT_mul(R, mk3(x == 3 ? 1.f : 0.f, x == 4 ? 1.f : 0.f, x == 5 ? 1.f : 0.f));   // R^T e_(x-3): root directions only
+        const f3 gw = mk3(K.gravity[0], K.gravity[1], K.gravity[2]);
+        if (c < 6) {
+          const f3 row = matT_mul(R, mk3(jr == 0 ? 1.f : 0.f, jr == 1 ? 1.f : 0.f, jr == 2 ? 1.f : 0.f));
+          if (c < 3) {
+            val = dot(row, dF);
+            if (theta) val += dot(row, cross(phi, Fp));
+          } else {
+            val = dot(row, dN);
+            if (theta) val += dot(row, cross(phi, Np));
+            if (which == 0) {                                  // the weight's moment, formed in world axes as the primal kernel forms it
+              const f3 Rh = mat_mul(R, hs);
+              const f3 ej = mk3(x == 3 ? 1.f : 0.f, x == 4 ? 1.f : 0.f, x == 5 ? 1.f : 0.f);
+              const f3 nw = cross(gw, theta ? cross(ej, Rh) : mat_mul(R, dH));
+              val += jr == 0 ? nw.x : jr == 1 ? nw.y : nw.z;
+            }
+          }
+        } else {
+          const f3 a = ld3(sS[rb]), po = ld3(sS[rb] + 3), l = cross(po, a);
+          f3 da = zero, dpo = zero;
+          if (which == 0 && x >= 6 && cb != rb && ((K.anc[rb] >> cb) & 1u)) {   // a joint above c turns c's axis and origin about its own
+            const f3 ak = ld3(sS[cb]), pk = ld3(sS[cb] + 3);
+            da = cross(ak, a); dpo = cross(ak, po - pk);
+          }
+          const f3 dl = cross(dpo, a) + cross(po, da);
+          const bool own = (K.anc[rb] >> cb) & 1u;              // the pair (rb, tr) exists
+          val = (own ? sT[rb][tr][6] : 0.f) + (dot(a, dN) + dot(l, dF)) + (dot(da, Np) + dot(dl, Fp));
+          if (which == 0) {
+            const f3 w = hs - ms * po, dw = dH - ms * dpo;
+            const f3 dg = theta ? cross(gF, phi) : zero;
+            val += (own ? sT[rb][tr][7] : 0.f) + dot(da, cross(gF, w)) + dot(a, cross(dg, w)) + dot(a, cross(gF, dw));
+          }
+        }
+        if (negate) val = -val;
+      }
+      out[e * DD_MENV + idx] = val;
+    }
+  }
+}
+
+// dst[e, i, j] = src[e, j, i] for up to three [N, 26, 26] tensors (NULL pairs are skipped): the conventional layout of the forward-dynamics
+// derivatives, whose solves produce one direction's 26 values contiguously.
+extern "C" __global__ void __launch_bounds__(64) wbc_derivatives_transpose_kernel(const float* __restrict__ s0, float* __restrict__ d0,
+                                                                                 const float* __restrict__ s1, float* __restrict__ d1,
+                                                                                 const float* __restrict__ s2, float* __restrict__ d2) {
+  const size_t base = (size_t)blockIdx.x * DD_MENV;
+  for (int idx = threadIdx.x; idx < DD_MENV; idx += 64) {
+    const int i = idx / BD_NCOL, j = idx - i * BD_NCOL, src = j * BD_NCOL + i;
+    if (d0) d0[base + idx] = s0[base + src];
+    if (d1) d1[base + idx] = s1[base + src];
+    if (d2) d2[base + idx] = s2[base + src];
+  }
+}
+
+// Fills C from the model. 0, or 1: a tree the kernel cannot walk.
+static int dd_const_fill(const DevConst* hc, DdConst& C) {
+  if (id_const_fill(hc, C.K) != 0) return 1;
+  C.npair = 0;
+  for (int b = 0; b < WBC_NB; ++b) {
+    int depth = 0;
+    while (depth < WBC_MAX_DEPTH && C.K.path[b][depth] >= 0) ++depth;
+    C.depth[b] = depth;
+    for (int u = 0; u < 3 + depth; ++u) { C.pair_body[C.npair] = (uint8_t)b; C.pair_u[C.npair] = (uint8_t)u; ++C.npair; }
+  }
+  for (int i = C.npair; i < DD_MAXPAIR; ++i) { C.pair_body[i] = 0; C.pair_u[i] = 0; }
+  return 0;
+}
+
+static int derivatives_launch(wbc_sim* s, const char* who, const float* nudot, float* dq, float* dnu, float* eye, int transposed, int negate,
+                              void* stream) {
+  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
+  char msg[160];
+  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) { snprintf(msg, sizeof msg, "%s: no sim state", who); return wbc_sim_internal_fail(-1, msg); }
+  if (n <= 0) return 0;
+  DdConst C;
+  if (dd_const_fill(hc, C) != 0) { snprintf(msg, sizeof msg, "%s: the model's tree is not one the kernel walks", who); return wbc_sim_internal_fail(-3, msg); }
+  hipLaunchKernelGGL(wbc_dynamics_derivatives_kernel, dim3(dq || dnu ? n : 1), dim3(64), 0, (hipStream_t)stream, C, root, dofs, bp, nudot, n, dq, dnu,
+                     eye, transposed, negate);
+  if (hipGetLastError() == hipSuccess) return 0;
+  snprintf(msg, sizeof msg, "%s: launch failed", who);
+  return wbc_sim_internal_fail(-2, msg);
+}
+
+// nudot (device f32 [N,26] or NULL = zeros); dtau_dq / dtau_dnu (device f32 [N,26,26], caller-owned, either may be NULL): include/wbc_sim.h.
+extern "C" int wbc_sim_inverse_dynamics_derivatives(wbc_sim* s, const float* nudot, float* dtau_dq, float* dtau_dnu, int flags, void* stream) {
+  StreamDeviceGuard sdg(stream);
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics_derivatives: sim is NULL");
+  if (!dtau_dq && !dtau_dnu) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics_derivatives: dtau_dq and dtau_dnu are both NULL");
+  if (flags & ~WBC_DERIV_TRANSPOSED) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics_derivatives: unknown flag bits");
+  if (((uintptr_t)nudot | (uintptr_t)dtau_dq | (uintptr_t)dtau_dnu) & 3u)
+    return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics_derivatives: nudot / dtau_dq / dtau_dnu must be 4-byte aligned");
+  return derivatives_launch(s, "wbc_sim_inverse_dynamics_derivatives", nudot, dtau_dq, dtau_dnu, nullptr, (flags & WBC_DERIV_TRANSPOSED) ? 1 : 0, 0, stream);
+}
+
+// Workspace: -dtau/dq^T and -dtau/dnu^T (the solves' right-hand sides), three solve results awaiting their transpose, one 26 x 26 identity.
+extern "C" size_t wbc_sim_forward_dynamics_derivatives_workspace_floats(int num_envs) {
+  return num_envs > 0 ? (size_t)num_envs * DD_MENV * 5 + DD_MENV : 0;
+}
+
+// tau (device f32 [N,26] or NULL), nudot [N,26], dnudot_dq / dnudot_dnu / minv [N,26,26] (any may be NULL, not all): include/wbc_sim.h.
+extern "C" int wbc_sim_forward_dynamics_derivatives(wbc_sim* s, const float* tau, float* nudot, float* dnudot_dq, float* dnudot_dnu, float* minv,
+                                                    int flags, float* workspace, void* stream) {
+  StreamDeviceGuard sdg(stream);
+  const char* who = "wbc_sim_forward_dynamics_derivatives";
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: sim is NULL");
+  if (!nudot || !workspace) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: nudot / workspace is NULL");
+  if (!dnudot_dq && !dnudot_dnu && !minv) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: dnudot_dq, dnudot_dnu and minv are all NULL");
+  if (flags & ~(WBC_SOLVE_ARMATURE | WBC_DERIV_TRANSPOSED)) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: unknown flag bits");
+  if (((uintptr_t)tau | (uintptr_t)nudot | (uintptr_t)dnudot_dq | (uintptr_t)dnudot_dnu | (uintptr_t)minv | (uintptr_t)workspace) & 3u)
+    return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: tau / nudot / dnudot_dq / dnudot_dnu / minv / workspace must be 4-byte aligned");
+  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
+  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: no sim state");
+  if (n <= 0) return 0;
+  const int solve_flags = flags & WBC_SOLVE_ARMATURE;
+  const bool tr = flags & WBC_DERIV_TRANSPOSED;
+  int rc = wbc_sim_forward_dynamics(s, tau, nudot, solve_flags, stream);
+  if (rc != 0) return rc;
+  const size_t blk = (size_t)n * DD_MENV;
+  float* rq = dnudot_dq ? workspace : nullptr;
+  float* rn = dnudot_dnu ? workspace + blk : nullptr;
+  float* eye = minv ? workspace + 5 * blk : nullptr;
+  rc = derivatives_launch(s, who, nudot, rq, rn, eye, 1, 1, stream);
+  if (rc != 0) return rc;
+  // one direction's 26 values are one right-hand side: the solves write the transposed layout, straight into the caller's tensors if asked
+  float* xq = tr ? dnudot_dq : workspace + 2 * blk;
+  float* xn = tr ? dnudot_dnu : workspace + 3 * blk;
+  float* xm = tr ? minv : workspace + 4 * blk;
+  if (dnudot_dq && (rc = mass_solve_launch(s, who, rq, DD_MENV, BD_NCOL, nullptr, xq, solve_flags, stream)) != 0) return rc;
+  if (dnudot_dnu && (rc = mass_solve_launch(s, who, rn, DD_MENV, BD_NCOL, nullptr, xn, solve_flags, stream)) != 0) return rc;
+  if (minv && (rc = mass_solve_launch(s, who, eye, 0, BD_NCOL, nullptr, xm, solve_flags, stream)) != 0) return rc;
+  if (!tr) {
+    hipLaunchKernelGGL(wbc_derivatives_transpose_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, xq, dnudot_dq, xn, dnudot_dnu, xm, minv);
+    if (hipGetLastError() != hipSuccess) return wbc_sim_internal_fail(-2, "wbc_sim_forward_dynamics_derivatives: launch failed");
+  }
+  return 0;
+}

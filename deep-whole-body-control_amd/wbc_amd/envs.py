@@ -559,6 +559,19 @@ class WidowGo1(LeggedRobot):
         inr = self.sim.centroidal()[3]
         return inr[:, 0], inr[:, [1, 4, 5, 4, 2, 6, 5, 6, 3]].view(-1, 3, 3)
 
+    # ---- first-order layer (no counterpart in the reference): include/wbc_sim.h: wbc_sim_inverse_dynamics_derivatives ----
+    def inverse_dynamics_derivatives(self, nudot: torch.Tensor = None):
+        """(dtau_dq, dtau_dnu), fresh f32 [N, 26, 26] indexed [N, i, j] = d tau_i / d x_j of inverse_dynamics(nudot) at the current
+        state: one launch. dq is the configuration tangent with "qdot = nu" (root translation, WORLD-frame rotation vector, joint
+        increments); the world components of nu and nudot are held fixed."""
+        return self.sim.inverse_dynamics_derivatives(nudot)
+
+    def forward_dynamics_derivatives(self, tau: torch.Tensor = None, armature: bool = False):
+        """(nudot [N, 26], dnudot_dq, dnudot_dnu, minv [N, 26, 26]), fresh tensors indexed [N, i, j]: forward_dynamics(tau) with its
+        partial derivatives -M^-1 dtau/dq, -M^-1 dtau/dnu (taken at that nudot) and d nudot / d tau = M^-1, the linearisation
+        d nudot = dnudot_dq dq + dnudot_dnu dnu + minv dtau a trajectory optimiser needs."""
+        return self.sim.forward_dynamics_derivatives(tau, armature=armature)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])

@@ -319,6 +319,47 @@ class WbcSim:
                                         self._stream()), "wbc_sim_centroidal")
         return tuple(outs)
 
+    # ---- analytic derivatives of inverse and forward dynamics (include/wbc_sim.h: wbc_sim_inverse_dynamics_derivatives) ----------------
+    def inverse_dynamics_derivatives(self, nudot: Optional[torch.Tensor] = None, dq: Optional[torch.Tensor] = None,
+                                     dnu: Optional[torch.Tensor] = None, transposed: bool = False):
+        """One wbc_sim_inverse_dynamics_derivatives launch on the current stream. Returns (dtau_dq, dtau_dnu), f32 [N, 26, 26] with
+        [e, i, j] = d tau_i / d x_j ([e, j, i] with transposed: one direction's 26 values contiguous, what mass_solve reads), in the
+        tangent convention of include/wbc_sim.h (world-frame rotation vector, world components of nu / nudot held fixed). Outputs that
+        are not passed are allocated; nudot f32 [N, 26] in the convention of inverse_dynamics, None: zeros. A launch that writes one
+        output goes through the C-ABI with a NULL pointer."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        outs = [torch.empty((n, ncol, ncol), dtype=torch.float32, device=self.device) if t is None else t for t in (dq, dnu)]
+        for t, sh in zip([nudot] + outs, ((n, ncol), (n, ncol, ncol), (n, ncol, ncol))):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        check(self.L.wbc_sim_inverse_dynamics_derivatives(self.h, nudot.data_ptr() if nudot is not None else None, outs[0].data_ptr(),
+                                                          outs[1].data_ptr(), 2 if transposed else 0, self._stream()),
+              "wbc_sim_inverse_dynamics_derivatives")
+        return tuple(outs)
+
+    def forward_dynamics_derivatives(self, tau: Optional[torch.Tensor] = None, nudot: Optional[torch.Tensor] = None,
+                                     dq: Optional[torch.Tensor] = None, dnu: Optional[torch.Tensor] = None,
+                                     minv: Optional[torch.Tensor] = None, armature: bool = False, transposed: bool = False):
+        """wbc_sim_forward_dynamics_derivatives on the current stream. Returns (nudot [N, 26], dnudot_dq, dnudot_dnu, minv [N, 26, 26]):
+        nudot = M^-1 (tau - h) (tau None: zeros), its partial derivatives in the layout and tangent convention of
+        inverse_dynamics_derivatives, and d nudot / d tau = M^-1. armature: M + diag(0_6, joint_armature) throughout. Outputs that are
+        not passed are allocated; the workspace is cached on the sim."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        if nudot is None:
+            nudot = torch.empty((n, ncol), dtype=torch.float32, device=self.device)
+        outs = [torch.empty((n, ncol, ncol), dtype=torch.float32, device=self.device) if t is None else t for t in (dq, dnu, minv)]
+        for t, sh in zip([tau, nudot] + outs, ((n, ncol), (n, ncol)) + ((n, ncol, ncol),) * 3):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        assert tau is None or abs(tau.data_ptr() - nudot.data_ptr()) >= 4 * nudot.numel(), "nudot overlaps tau"
+        if "_fdd_ws" not in self.__dict__:
+            self._fdd_ws = torch.empty(int(self.L.wbc_sim_forward_dynamics_derivatives_workspace_floats(n)), dtype=torch.float32,
+                                       device=self.device)
+        check(self.L.wbc_sim_forward_dynamics_derivatives(self.h, tau.data_ptr() if tau is not None else None, nudot.data_ptr(),
+                                                          *[t.data_ptr() for t in outs], (1 if armature else 0) | (2 if transposed else 0),
+                                                          self._fdd_ws.data_ptr(), self._stream()), "wbc_sim_forward_dynamics_derivatives")
+        return (nudot,) + tuple(outs)
+
     def episode_stats(self, scale: float, track_state: torch.Tensor = None, track_cap: int = 0) -> torch.Tensor:
         """Means over the envs that reset in the last step of their finished episode's reward sums [NREW] and metric
         sums [NMETRIC], times `scale`, as one fresh device tensor (WG:743-754 without a host sync). With `track_state`

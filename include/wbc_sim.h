@@ -728,6 +728,55 @@ int wbc_sim_constrained_dynamics(wbc_sim* sim, const int32_t* rigid_bodies /* ho
  * wbc_sim_inverse_dynamics. */
 int wbc_sim_centroidal(wbc_sim* sim, const float* nudot, float* com, float* mom, float* cmm, float* inertia, void* stream);
 
+/* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and
+ * of nudot(q, nu, tau) in the coordinates of wbc_sim_body_dynamics, from the sim's current root / DoF state, WBC_T_BODY_PARAMS and all
+ * three gravity components. The sim's state is read, never written.
+ * Configuration tangent dq in R^26, chosen so that "qdot = nu":
+ *   dq[0:3]  translates the root origin, world axes;
+ *   dq[3:6]  is a WORLD-frame rotation vector, R <- exp([dtheta]x) R;
+ *   dq[6+d]  increments DoF d.
+ * Partial derivatives with respect to dq hold the WORLD components of nu and nudot fixed; the rows of tau are those of
+ * wbc_sim_inverse_dynamics (0:3 net external force, 3:6 net external moment about the root origin, world axes, 6: joint torques).
+ * With this choice, along any motion d tau / dt = (dtau/dq) nu + (dtau/dnu) nudot + M d(nudot)/dt.
+ *
+ * wbc_sim_inverse_dynamics_derivatives: ONE launch (wbc_dynamics_derivatives_kernel).
+ * nudot     device f32 [N, 26] or NULL (= zeros), in the convention of wbc_sim_inverse_dynamics.
+ * dtau_dq, dtau_dnu   device f32 [N, 26, 26], [e, i, j] = d tau_i / d x_j; either may be NULL (not written), not both. With
+ *           WBC_DERIV_TRANSPOSED in flags the layout is [e, j, i]: one direction's 26 values are contiguous, the right-hand-side
+ *           layout wbc_sim_mass_solve reads (rhs_env_stride 676, nrhs 26).
+ * Exact structure, written as literal zeros: dtau_dq[:, :, 0:3] (the root position is never read: every output is bit-identical under
+ * a translation of the robot), dtau_dnu[:, :, 0:3] (Galilean invariance: v_root does not enter the arithmetic), rows and columns
+ * 24, 25 (locked fingers; their entries of nudot and of qd are ignored) and every joint-row x joint-column entry whose two joints lie
+ * on different chains.
+ * RIGID-BODY dynamics only, exactly as wbc_sim_inverse_dynamics: no armature, no limit stops, no contacts. Nothing is allocated, so
+ * the call is safe under stream capture. Every pointer needs 4-byte alignment only.
+ *
+ * wbc_sim_forward_dynamics_derivatives:
+ * tau       device f32 [N, 26] or NULL (= zeros), nudot device f32 [N, 26] (required): nudot = M^-1 (tau - h), the bits of
+ *           wbc_sim_forward_dynamics.
+ * dnudot_dq   = -M^-1 dtau/dq taken at that nudot;  dnudot_dnu = -M^-1 dtau/dnu;  minv = d nudot / d tau = M^-1. Device f32
+ *           [N, 26, 26] in the layout rules above ([e, i, j] = d nudot_i / d x_j, or [e, j, i] with WBC_DERIV_TRANSPOSED); each may be
+ *           NULL, not all three. The zero columns 0:3 of the first two and the fingers' rows and columns are exactly zero.
+ * flags     any of WBC_SOLVE_ARMATURE (M + diag(0_6, joint_armature) throughout; the armature is constant, so the formula is
+ *           unchanged) and WBC_DERIV_TRANSPOSED.
+ * workspace caller-owned device floats, at least wbc_sim_forward_dynamics_derivatives_workspace_floats(N) of them (0 for a bad
+ *           argument). Nothing is allocated in the call. The sim's bias-force scratch of wbc_sim_forward_dynamics is used as well,
+ *           with the same caveat: one stream at a time per sim.
+ * Launches on `stream`, no host synchronisation: h (wbc_inverse_dynamics_kernel) and the solve for nudot (the two launches of
+ * wbc_sim_forward_dynamics); wbc_dynamics_derivatives_kernel at that nudot, writing -dtau/dq and -dtau/dnu transposed into the
+ * workspace (and a 26 x 26 identity when minv is wanted); one wbc_mass_solve_kernel launch of 26 right-hand sides per requested
+ * output, which leaves the transposed layout -- straight in the caller's tensors with WBC_DERIV_TRANSPOSED; otherwise one
+ * wbc_derivatives_transpose_kernel launch moves all of them to [e, i, j]. Seven launches for everything in the conventional layout,
+ * six transposed.
+ * Both: -1 with a message in wbc_last_error(), nothing written, for a NULL sim (/ nudot / workspace), all outputs NULL, unknown flag
+ * bits or a pointer that is not 4-byte aligned; -3 for a model whose tree the kernel cannot walk; -2 if a launch fails. Stream / device
+ * handling as wbc_sim_centroidal. */
+#define WBC_DERIV_TRANSPOSED 2   /* distinct from WBC_SOLVE_ARMATURE (1): the two functions share `flags` */
+int wbc_sim_inverse_dynamics_derivatives(wbc_sim* sim, const float* nudot, float* dtau_dq, float* dtau_dnu, int flags, void* stream);
+size_t wbc_sim_forward_dynamics_derivatives_workspace_floats(int num_envs);
+int wbc_sim_forward_dynamics_derivatives(wbc_sim* sim, const float* tau, float* nudot, float* dnudot_dq, float* dnudot_dnu, float* minv,
+                                         int flags, float* workspace, void* stream);
+
 /* extras["episode"] of reset_idx (widowGo1.py:743-754): out[0:WBC_NREW] = mean over the envs that reset in the last
  * step of their finished episode's reward sums, out[WBC_NREW:+WBC_NMETRIC] the same for the metric sums, both
  * times `scale` (1 / max_episode_length_s). `out`: device, WBC_NREW + WBC_NMETRIC floats. On a step in which no env reset
