@@ -1804,3 +1804,389 @@ extern "C" int wbc_sim_forward_dynamics_derivatives(wbc_sim* s, const float* tau
   }
   return 0;
 }
+
+// ---- whole-body inverse dynamics for task-space accelerations (include/wbc_sim.h: wbc_sim_task_inverse_dynamics) ---------------------
+// Per env: the joint torques tau_j (18) that minimise the weighted task, posture, contact-force and torque terms subject to the
+// equations of motion and the active stance rows. The feasible set is the image of tau_j under stance-constrained forward dynamics,
+//     (nudot, lambda) = (a_0, lambda_0) + (G_a, G_lambda) tau_j ,
+// so the problem is an unconstrained least-squares one in 18 unknowns. It is solved in its SQUARE-ROOT form: the sqrt(weight)-scaled
+// rows [posture 24 | force 3 ns | task 6 nt | torque 18] x [18 columns | constant] are stacked (at most 90 x 19) and reduced by
+// Householder reflections; the normal equations G^T H G are never formed (their condition number is the square of the stack's: the
+// internal-force directions of a multi-foot stance are seen by w_force and w_torque alone). The outputs (nudot, lambda) are then
+// RECOMPUTED from tau_j by the constrained-dynamics chain itself (a_free = M^-1 (S^T tau_j - h), Cholesky of the Delassus matrix), so
+// the equations of motion and the stance rows hold to that chain's rounding whatever the least-squares solve did.
+// Launches: h (wbc_inverse_dynamics_kernel), wbc_taskid_rhs_kernel, the mass solve with 3 ns + 1 + 18 right-hand sides
+// [J_c^T | -h | S^T], wbc_taskid_solve_kernel. The root position is never read.
+#define TI_NJ WBC_NJ                             // joint torques: the unknowns
+#define TI_NL (6 + TI_NJ)                        // live coordinates
+#define TI_MAXS (3 * WBC_TASKID_MAX_STANCE)      // 12 stance rows at most
+#define TI_MAXT (6 * WBC_TASKID_MAX_TASKS)       // 36 task rows at most
+#define TI_MAXRHS (TI_MAXS + 1 + TI_NJ)          // 31 right-hand sides of the mass solve at most
+#define TI_NC (TI_NJ + 1)                        // columns of the stack: the unknowns and the constant
+#define TI_MAXROWS (TI_NL + TI_MAXS + TI_MAXT + TI_NJ)   // 90 rows of the stack at most
+#define TI_QG 3                                  // row groups of the reflections: lane = group * TI_NC + column
+static_assert(TI_MAXRHS <= WBC_SOLVE_MAX_RHS && WBC_NB + WBC_TASKID_MAX_STANCE + WBC_TASKID_MAX_TASKS <= BA_LPE && TI_MAXS <= CD_GSTRIDE &&
+              TI_QG * TI_NC <= 64 && WBC_TASKID_MAX_STANCE <= WBC_CONSTR_MAX_BODIES, "lanes");
+struct TiConst {
+  BaConst A;
+  int32_t col_body[WBC_NDOF];
+  uint32_t anc[WBC_NB];                        // as BodyConst::anc
+  int32_t ns, nt, srb[WBC_TASKID_MAX_STANCE], trb[WBC_TASKID_MAX_TASKS];   // the listed stance and task rigid bodies
+  int32_t jcol[TI_NJ];                         // column (of 26) of joint torque j
+};
+
+// The mass solve's right-hand sides [N, 3 ns + 1 + 18, 26]: the stance bodies' linear Jacobian rows (zeros where inactive), -h, the 18
+// unit rows S^T; gamma [N, CD_GSTRIDE] = (Jdot nu) of the stance rows; the task bodies' Jacobian rows jt [N, 6 nt, 26] (linear, angular)
+// and gt [N, TI_MAXT] = their Jdot nu. Lanes as wbc_constraint_rhs_kernel: b < 19 = moving body b, then one lane per listed body.
+extern "C" __global__ void __launch_bounds__(64) wbc_taskid_rhs_kernel(TiConst C, const float* __restrict__ root, const float* __restrict__ dofs,
+                                                                      const uint8_t* __restrict__ active, const float* __restrict__ h, int n,
+                                                                      float* __restrict__ rhs, float* __restrict__ gamma,
+                                                                      float* __restrict__ jt, float* __restrict__ gt) {
+  __shared__ float sJ[BA_EPW][WBC_NB][6];          // joint axis, joint origin, in F
+  __shared__ float sX[BA_EPW][WBC_TASKID_MAX_STANCE + WBC_TASKID_MAX_TASKS][3];   // listed body's origin in F
+  const int half = BA_EPW == 2 ? threadIdx.x >> 5 : 0, lane = BA_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
+  const int env = blockIdx.x * BA_EPW + half;
+  const bool live = env < n;
+  const size_t e = live ? env : n - 1;             // the idle half of the last workgroup recomputes the last env and stores nothing
+  const int ns = C.ns, nt = C.nt, m = 3 * ns, nr = m + 1 + TI_NJ;
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+  if (lane < WBC_NB + ns + nt) {
+    const bool body = lane < WBC_NB;
+    const int k = body ? 0 : lane - WBC_NB;
+    const int r = body ? 0 : (k < ns ? C.srb[k] : C.trb[k - ns]), b = body ? lane : C.A.rb_body[r];
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    f3 p, w, aw, ao;
+    ba_walk(C.A, b, e, R, root, dofs, nullptr, E, p, w, aw, ao);
+    if (body) {
+      const int ax = C.A.axis[b];                            // -1 for the root: no joint axis
+      st3(sJ[half][b], mat_mul(E, mk3(ax == 0 ? 1.f : 0.f, ax == 1 ? 1.f : 0.f, ax == 2 ? 1.f : 0.f)));
+      st3(sJ[half][b] + 3, p);
+    } else {
+      const f3 xo = mat_mul(E, mk3(C.A.rb_offset[r][0], C.A.rb_offset[r][1], C.A.rb_offset[r][2]));
+      st3(sX[half][k], p + xo);
+      const f3 lin = mat_mul(R, ao + cross(aw, xo) + cross(w, cross(w, xo)));
+      if (live) {
+        if (k < ns) st3(gamma + e * CD_GSTRIDE + 3 * k, lin);
+        else { st3(gt + e * TI_MAXT + 6 * (k - ns), lin); st3(gt + e * TI_MAXT + 6 * (k - ns) + 3, mat_mul(R, aw)); }
+      }
+    }
+  }
+  __syncthreads();
+  if (lane < BD_NCOL && live) {
+    const int c = lane, b = c < 6 ? 0 : C.col_body[c - 6], j = c < 3 ? c : c - 3;
+    const f3 ej = mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f);
+    float* o = rhs + e * (size_t)(nr * BD_NCOL) + c;
+    for (int k = 0; k < ns; ++k) {
+      const bool act = active ? active[e * ns + k] != 0 : true;
+      const f3 x = ld3(sX[half][k]);
+      f3 lin = mk3(0.f, 0.f, 0.f);
+      if (act) {
+        if (c < 3) lin = ej;                                 // v_root: identity
+        else if (c < 6) lin = cross(ej, mat_mul(R, x));      // omega_root: e_j x (origin relative to the root, world axes)
+        else if (b >= 0 && ((C.anc[C.A.rb_body[C.srb[k]]] >> b) & 1u)) lin = mat_mul(R, cross(ld3(sJ[half][b]), x - ld3(sJ[half][b] + 3)));
+      }
+      o[(3 * k) * BD_NCOL] = lin.x; o[(3 * k + 1) * BD_NCOL] = lin.y; o[(3 * k + 2) * BD_NCOL] = lin.z;
+    }
+    o[m * BD_NCOL] = b >= 0 ? 0.f - h[e * BD_NCOL + c] : 0.f;
+    for (int q = 0; q < TI_NJ; ++q) o[(m + 1 + q) * BD_NCOL] = C.jcol[q] == c ? 1.f : 0.f;
+    float* t = jt + e * (size_t)(6 * nt * BD_NCOL) + c;
+    for (int k = 0; k < nt; ++k) {
+      const f3 x = ld3(sX[half][ns + k]);
+      f3 lin = mk3(0.f, 0.f, 0.f), ang = lin;
+      if (c < 3) lin = ej;
+      else if (c < 6) { lin = cross(ej, mat_mul(R, x)); ang = ej; }
+      else if (b >= 0 && ((C.anc[C.A.rb_body[C.trb[k]]] >> b) & 1u)) {
+        const f3 a = ld3(sJ[half][b]);
+        lin = mat_mul(R, cross(a, x - ld3(sJ[half][b] + 3)));
+        ang = mat_mul(R, a);
+      }
+      t[(6 * k) * BD_NCOL] = lin.x; t[(6 * k + 1) * BD_NCOL] = lin.y; t[(6 * k + 2) * BD_NCOL] = lin.z;
+      t[(6 * k + 3) * BD_NCOL] = ang.x; t[(6 * k + 4) * BD_NCOL] = ang.y; t[(6 * k + 5) * BD_NCOL] = ang.z;
+    }
+  }
+}
+
+struct TsConst {
+  int32_t jcol[TI_NJ];                         // column (of 26) of joint torque j
+  int32_t lcol[TI_NL];                         // column of live coordinate s: the root's six, then the joints'
+  float sp, sf, st, damping;                   // sqrt of the posture, force and torque weights; the Delassus damping
+};
+
+// One env per 64-lane workgroup. With m = 3 ns, Y = (M^-1 [J_c^T | -h | S^T])^T the mass solve's output and S the stack in LDS:
+//  1) A = J_c Y_c^T + damping I (lower triangle, identity where inactive) and, in the stack's force rows, [-J_c Y_s^T | a_stance - gamma
+//     - J_c y_h]; Cholesky of A as wbc_constraint_solve_kernel; lane j = column j solves its column in place: [G_lambda | lambda_0];
+//  2) posture rows [G_a | a_0] = [Y_s^T | y_h] + Y_c^T [G_lambda | lambda_0] on the live coordinates; task rows sqrt(w) (J_t [G_a | a_0] +
+//     (0 | Jdot nu - acc)), zero where w = 0 (acc is not read there); then the posture rows lose nudot_ref and take sqrt(w_posture),
+//     the force rows sqrt(w_force), and the torque rows are sqrt(w_torque) I: w_torque > 0 gives the stack full column rank;
+//  3) 18 Householder reflections, lane = group * 19 + column: three groups share the rows of a column's dot product with the pivot
+//     column (rows k + group, step 3: 57 consecutive LDS words per read), partial sums meet in LDS. The pivot column is left as it
+//     is (its reflected value alpha goes to sDiag), so no lane writes what another reads;
+//  4) R tau_j = -(Q^T b) by back-substitution, then a_free = y_h + Y_s^T tau_j and the tail of wbc_constraint_solve_kernel.
+// A single-wavefront workgroup: the __syncthreads() order the LDS traffic and cost no barrier instruction.
+extern "C" __global__ void __launch_bounds__(64) wbc_taskid_solve_kernel(TsConst C, const float* __restrict__ rhs, const float* __restrict__ Y,
+                                                                        const float* __restrict__ gamma, const float* __restrict__ jt,
+                                                                        const float* __restrict__ gt, const uint8_t* __restrict__ active,
+                                                                        const float* __restrict__ stance_acc, const float* __restrict__ task_acc,
+                                                                        const float* __restrict__ task_weight, const float* __restrict__ nudot_ref,
+                                                                        int ns, int nt, int n, float* __restrict__ tau, float* __restrict__ nudot,
+                                                                        float* __restrict__ lambda) {
+  __shared__ float sY[TI_MAXRHS][CD_LD], sJc[TI_MAXS][CD_LD], sJt[TI_MAXT][CD_LD];
+  __shared__ float sS[TI_MAXROWS * TI_NC];         // the stack, row-major, pitch 19
+  __shared__ float sA[TI_MAXS][TI_MAXS + 1];       // lower triangle: A, then L
+  __shared__ float sD[TI_MAXS + 1], sV[TI_MAXS + 1];   // 1 / L_jj; the value handed round
+  __shared__ float sP[TI_QG][TI_NC], sDiag[TI_NJ], sTau[TI_NJ], sAf[BD_NCOL];
+  const int lane = threadIdx.x;
+  if ((int)blockIdx.x >= n) return;
+  const size_t e = blockIdx.x;
+  const int m = 3 * ns, mt = 6 * nt, nr = m + 1 + TI_NJ;
+  const int F0 = TI_NL, T0 = F0 + m, Q0 = T0 + mt, nrow = Q0 + TI_NJ;
+  const float *rp = rhs + e * (size_t)(nr * BD_NCOL), *yp = Y + e * (size_t)(nr * BD_NCOL), *jp = jt + e * (size_t)(mt * BD_NCOL);
+  for (int t = lane; t < nr * BD_NCOL; t += 64) {
+    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+    sY[r][c] = yp[t];
+    if (r < m) sJc[r][c] = rp[t];
+  }
+  for (int t = lane; t < mt * BD_NCOL; t += 64) {
+    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+    sJt[r][c] = jp[t];
+  }
+  uint32_t act = 0;                                // bit i: row i belongs to an active stance body
+  for (int k = 0; k < ns; ++k)
+    if (!active || active[e * ns + k]) act |= 7u << (3 * k);
+  __syncthreads();
+
+  // 1) the Delassus matrix and the 19 right-hand sides of its factor
+  for (int t = lane; t < m * (m + 1) / 2; t += 64) {
+    int i = (int)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);              // t = i (i + 1) / 2 + j, j <= i
+    i = i * (i + 1) / 2 > t ? i - 1 : ((i + 1) * (i + 2) / 2 <= t ? i + 1 : i);
+    const int j = t - i * (i + 1) / 2;
+    float a = 0.f;
+    for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * sY[j][c];
+    const bool on = ((act >> i) & 1u) && ((act >> j) & 1u);
+    sA[i][j] = on ? (i == j ? a + C.damping : a) : (i == j ? 1.f : 0.f);
+  }
+  for (int t = lane; t < m * TI_NC; t += 64) {
+    const int i = t / TI_NC, j = t - i * TI_NC;
+    float v = 0.f;
+    if ((act >> i) & 1u) {
+      const float* y = sY[j < TI_NJ ? m + 1 + j : m];
+      float a = 0.f;
+      for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * y[c];
+      v = j < TI_NJ ? 0.f - a : ((stance_acc ? stance_acc[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
+    }
+    sS[(F0 + i) * TI_NC + j] = v;
+  }
+  {
+    const int i = lane;
+    const bool row = i < m;
+    for (int j = 0; j < m; ++j) {
+      __syncthreads();
+      float d = sA[j][j];
+      for (int k = 0; k < j; ++k) d -= sA[j][k] * sA[j][k];
+      const float id = 1.f / __fsqrt_rn(d);
+      if (row && i > j) {
+        float s = sA[i][j];
+        for (int k = 0; k < j; ++k) s -= sA[i][k] * sA[j][k];
+        sA[i][j] = s * id;
+      }
+      if (i == j) sD[j] = id;
+    }
+  }
+  __syncthreads();
+  if (lane < TI_NC) {                              // L L^T x = column `lane`, in place
+    float* x = sS + F0 * TI_NC + lane;
+    for (int i = 0; i < m; ++i) {
+      float s = x[i * TI_NC];
+      for (int k = 0; k < i; ++k) s -= sA[i][k] * x[k * TI_NC];
+      x[i * TI_NC] = s * sD[i];
+    }
+    for (int i = m - 1; i >= 0; --i) {
+      float s = x[i * TI_NC];
+      for (int k = i + 1; k < m; ++k) s -= sA[k][i] * x[k * TI_NC];
+      x[i * TI_NC] = s * sD[i];
+    }
+  }
+  __syncthreads();
+
+  // 2) the stack
+  for (int t = lane; t < TI_NL * TI_NC; t += 64) {
+    const int s = t / TI_NC, j = t - s * TI_NC, c = C.lcol[s];
+    float a = sY[j < TI_NJ ? m + 1 + j : m][c];
+    for (int k = 0; k < m; ++k) a += sY[k][c] * sS[(F0 + k) * TI_NC + j];
+    sS[t] = a;
+  }
+  __syncthreads();
+  for (int t = lane; t < mt * TI_NC; t += 64) {
+    const int r = t / TI_NC, j = t - r * TI_NC;
+    const float w = task_weight ? task_weight[e * mt + r] : 1.f;
+    float v = 0.f;
+    if (w > 0.f) {
+      float a = 0.f;
+      for (int s = 0; s < TI_NL; ++s) a += sJt[r][C.lcol[s]] * sS[s * TI_NC + j];
+      if (j == TI_NJ) a += gt[e * TI_MAXT + r] - task_acc[e * mt + r];
+      v = __fsqrt_rn(w) * a;
+    }
+    sS[(T0 + r) * TI_NC + j] = v;
+  }
+  __syncthreads();
+  for (int t = lane; t < TI_NL * TI_NC; t += 64) {
+    const int s = t / TI_NC, j = t - s * TI_NC;
+    const float ref = (j == TI_NJ && nudot_ref) ? nudot_ref[e * BD_NCOL + C.lcol[s]] : 0.f;
+    sS[t] = C.sp * (sS[t] - ref);
+  }
+  for (int t = lane; t < m * TI_NC; t += 64) sS[F0 * TI_NC + t] *= C.sf;
+  for (int t = lane; t < TI_NJ * TI_NC; t += 64) {
+    const int i = t / TI_NC, j = t - i * TI_NC;
+    sS[Q0 * TI_NC + t] = i == j ? C.st : 0.f;
+  }
+  __syncthreads();
+
+  // 3) Householder reflections
+  {
+    const int g = lane / TI_NC, j = lane - g * TI_NC;
+    const bool mine = g < TI_QG;
+    for (int k = 0; k < TI_NJ; ++k) {
+      if (mine) {
+        float part = 0.f;
+        if (j >= k)
+          for (int r = k + g; r < nrow; r += TI_QG) part += sS[r * TI_NC + k] * sS[r * TI_NC + j];
+        sP[g][j] = part;
+      }
+      __syncthreads();
+      const float skk = (sP[0][k] + sP[1][k]) + sP[2][k], akk = sS[k * TI_NC + k];
+      const float nrm = __fsqrt_rn(skk), alpha = akk >= 0.f ? 0.f - nrm : nrm, vk = akk - alpha;
+      float tj = 0.f;                              // 2 (v . a_j) / (v . v), v = a_k - alpha e_k: v . v = -2 alpha v_k
+      if (mine && j > k) tj = (((sP[0][j] + sP[1][j]) + sP[2][j]) - alpha * sS[k * TI_NC + j]) * (-1.f / (alpha * vk));
+      __syncthreads();
+      if (mine && j > k)
+        for (int r = k + g; r < nrow; r += TI_QG) sS[r * TI_NC + j] -= tj * (r == k ? vk : sS[r * TI_NC + k]);
+      if (lane == k) sDiag[k] = alpha;
+      __syncthreads();
+    }
+  }
+
+  // 4) tau_j, then (nudot, lambda) of constrained forward dynamics with it
+  for (int k = TI_NJ - 1; k >= 0; --k) {
+    float x = 0.f - sS[k * TI_NC + TI_NJ];
+    for (int j = k + 1; j < TI_NJ; ++j) x -= sS[k * TI_NC + j] * sTau[j];
+    if (lane == 0) sTau[k] = x / sDiag[k];
+    __syncthreads();
+  }
+  int jq = -1;                                     // lane c < 26: the joint torque that drives column c
+  for (int q = 0; q < TI_NJ; ++q) jq = C.jcol[q] == lane ? q : jq;
+  if (lane < BD_NCOL) {
+    float a = sY[m][lane];
+    for (int q = 0; q < TI_NJ; ++q) a += sY[m + 1 + q][lane] * sTau[q];
+    sAf[lane] = a;
+  }
+  __syncthreads();
+  const int i = lane;
+  const bool row = i < m, on = row && ((act >> i) & 1u);
+  float ci = 0.f;
+  if (on) {
+    float a = 0.f;
+    for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * sAf[c];
+    ci = ((stance_acc ? stance_acc[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
+  }
+  for (int j = 0; j < m; ++j) {                    // L y = c
+    if (i == j) sV[j] = ci * sD[j];
+    __syncthreads();
+    const float yj = sV[j];
+    if (i == j) ci = yj;
+    else if (row && i > j) ci -= sA[i][j] * yj;
+  }
+  for (int j = m - 1; j >= 0; --j) {               // L^T lambda = y
+    __syncthreads();
+    if (i == j) sV[j] = ci * sD[j];
+    __syncthreads();
+    const float lj = sV[j];
+    if (row && i < j) ci -= sA[j][i] * lj;
+  }
+  __syncthreads();
+  if (lambda && row) lambda[e * m + i] = on ? sV[i] : 0.f;
+  if (lane < BD_NCOL) {
+    tau[e * BD_NCOL + lane] = jq >= 0 ? sTau[jq] : 0.f;
+    if (nudot) {
+      float a = sAf[lane];
+      for (int k = 0; k < m; ++k) a += sY[k][lane] * sV[k];
+      nudot[e * BD_NCOL + lane] = (lane < 6 || jq >= 0) ? a : 0.f;
+    }
+  }
+}
+
+// Workspace layout (floats): the right-hand-side block [N, 3 ns + 19, 26], the mass solve's output of the same shape, gamma [N, 16],
+// the task rows' Jacobian [N, 6 nt, 26] and their Jdot nu [N, 36].
+extern "C" size_t wbc_sim_task_inverse_dynamics_workspace_floats(int num_envs, int nstance, int ntasks) {
+  if (num_envs <= 0 || nstance < 0 || nstance > WBC_TASKID_MAX_STANCE || ntasks < 0 || ntasks > WBC_TASKID_MAX_TASKS) return 0;
+  return (size_t)num_envs * (2 * (size_t)(3 * nstance + 1 + TI_NJ) * BD_NCOL + CD_GSTRIDE + (size_t)6 * ntasks * BD_NCOL + TI_MAXT);
+}
+
+// Four launches on `stream`. Arguments and conventions: include/wbc_sim.h.
+extern "C" int wbc_sim_task_inverse_dynamics(wbc_sim* s, const int32_t* stance_bodies, int nstance, const uint8_t* active, const float* stance_acc,
+                                             const int32_t* task_bodies, int ntasks, const float* task_acc, const float* task_weight,
+                                             const float* nudot_ref, const wbc_taskid_weights* weights, int flags, float* tau, float* nudot,
+                                             float* lambda, float* workspace, void* stream) {
+  StreamDeviceGuard sdg(stream);
+  const char* who = "wbc_sim_task_inverse_dynamics";
+  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
+  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: sim is NULL");
+  if (!tau || !workspace || !weights) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: tau / workspace / weights is NULL");
+  if (nstance < 0 || nstance > WBC_TASKID_MAX_STANCE) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: nstance must be 0..WBC_TASKID_MAX_STANCE");
+  if (ntasks < 0 || ntasks > WBC_TASKID_MAX_TASKS) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: ntasks must be 0..WBC_TASKID_MAX_TASKS");
+  if ((nstance > 0 && !stance_bodies) || (ntasks > 0 && (!task_bodies || !task_acc)))
+    return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: stance_bodies / task_bodies / task_acc is NULL with a count above 0");
+  auto fin_ge0 = [](float x) { return x >= 0.f && x <= 3.402823466e38f; };   // finite: up to FLT_MAX
+  if (!(weights->torque > 0.f) || !fin_ge0(weights->torque)) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: weights.torque must be finite and > 0");
+  if (!fin_ge0(weights->posture) || !fin_ge0(weights->force) || !fin_ge0(weights->damping))
+    return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: weights.posture / force / damping must be finite and >= 0");
+  if (flags & ~WBC_SOLVE_ARMATURE) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: unknown flag bits");
+  if (((uintptr_t)stance_acc | (uintptr_t)task_acc | (uintptr_t)task_weight | (uintptr_t)nudot_ref | (uintptr_t)tau | (uintptr_t)nudot | (uintptr_t)lambda |
+       (uintptr_t)workspace) & 3u)
+    return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: stance_acc / task_acc / task_weight / nudot_ref / tau / nudot / lambda / workspace must be 4-byte aligned");
+  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: no sim state");
+  for (int k = 0; k < nstance; ++k)
+    if (stance_bodies[k] < 0 || stance_bodies[k] >= WBC_NRB) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: rigid-body index outside 0..WBC_NRB-1");
+  for (int k = 0; k < ntasks; ++k)
+    if (task_bodies[k] < 0 || task_bodies[k] >= WBC_NRB) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: rigid-body index outside 0..WBC_NRB-1");
+  TiConst C; IdConst K;
+  if (ba_const_fill(hc, C.A, K) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_task_inverse_dynamics: the model's tree is not one the kernel walks");
+  for (int k = 0; k < nstance; ++k)
+    for (int l = 0; l < k; ++l)
+      if (C.A.rb_body[stance_bodies[k]] == C.A.rb_body[stance_bodies[l]])
+        return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: two stance bodies ride on the same moving body (dependent rows)");
+  for (int k = 0; k < ntasks; ++k)
+    for (int l = 0; l < k; ++l)
+      if (C.A.rb_body[task_bodies[k]] == C.A.rb_body[task_bodies[l]])
+        return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: two task bodies ride on the same moving body (dependent rows)");
+  TsConst T;
+  int nj = 0;
+  for (int d = 0; d < WBC_NDOF; ++d) {
+    C.col_body[d] = K.col_body[d];
+    if (K.col_body[d] >= 0) { if (nj < TI_NJ) C.jcol[nj] = 6 + d; ++nj; }
+  }
+  if (nj != TI_NJ) return wbc_sim_internal_fail(-3, "wbc_sim_task_inverse_dynamics: the model's tree is not one the kernel walks");
+  if (n <= 0) return 0;
+  for (int b = 0; b < WBC_NB; ++b) C.anc[b] = K.anc[b];
+  C.ns = nstance; C.nt = ntasks;
+  for (int k = 0; k < WBC_TASKID_MAX_STANCE; ++k) C.srb[k] = nstance > 0 ? stance_bodies[k < nstance ? k : 0] : 0;
+  for (int k = 0; k < WBC_TASKID_MAX_TASKS; ++k) C.trb[k] = ntasks > 0 ? task_bodies[k < ntasks ? k : 0] : 0;
+  for (int q = 0; q < TI_NJ; ++q) { T.jcol[q] = C.jcol[q]; T.lcol[6 + q] = C.jcol[q]; }
+  for (int c = 0; c < 6; ++c) T.lcol[c] = c;
+  T.sp = sqrtf(weights->posture); T.sf = sqrtf(weights->force); T.st = sqrtf(weights->torque); T.damping = weights->damping;
+  float* h = nullptr;
+  if (wbc_sim_internal_fd_scratch(s, &h) != 0) return -1;
+  const int nr = 3 * nstance + 1 + TI_NJ;
+  float *blk = workspace, *Y = blk + (size_t)n * nr * BD_NCOL, *gamma = Y + (size_t)n * nr * BD_NCOL, *jt = gamma + (size_t)n * CD_GSTRIDE,
+        *gt = jt + (size_t)n * 6 * ntasks * BD_NCOL;
+  int rc = wbc_sim_inverse_dynamics(s, nullptr, h, nullptr, stream);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(wbc_taskid_rhs_kernel, dim3((n + BA_EPW - 1) / BA_EPW), dim3(64), 0, (hipStream_t)stream, C, root, dofs, active, (const float*)h, n,
+                     blk, gamma, jt, gt);
+  if (hipGetLastError() != hipSuccess) return wbc_sim_internal_fail(-2, "wbc_sim_task_inverse_dynamics: launch failed");
+  rc = mass_solve_launch(s, who, blk, (int64_t)nr * BD_NCOL, nr, nullptr, Y, flags, stream);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(wbc_taskid_solve_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, T, (const float*)blk, (const float*)Y, (const float*)gamma,
+                     (const float*)jt, (const float*)gt, active, stance_acc, task_acc, task_weight, nudot_ref, nstance, ntasks, n, tau, nudot, lambda);
+  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_task_inverse_dynamics: launch failed");
+}

@@ -100,6 +100,11 @@ class WbcSideJob(C.Structure):
                 ("n", i32), ("track_cap", i32), ("nblocks", i32), ("scale", f32)]
 
 
+class WbcTaskIdWeights(C.Structure):
+    """wbc_taskid_weights (include/wbc_sim.h): the scalar weights of wbc_sim_task_inverse_dynamics."""
+    _fields_ = [("posture", f32), ("force", f32), ("torque", f32), ("damping", f32)]
+
+
 # enum wbc_tensor_id, same order as the header
 TENSOR_IDS = [
     "ROOT_STATES", "DOF_STATE", "NET_CONTACT_FORCE", "RIGID_BODY_STATE", "FORCE_SENSOR", "TORQUES", "OBS_BUF",

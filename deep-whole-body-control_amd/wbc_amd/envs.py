@@ -537,6 +537,37 @@ class WidowGo1(LeggedRobot):
             self._feet_list = [int(i) for i in self.feet_indices.tolist()]
         return self.sim.constrained_dynamics(self._feet_list, tau=tau, active=stance, armature=armature)
 
+    def whole_body_inverse_dynamics(self, base_acc: torch.Tensor = None, ee_acc: torch.Tensor = None, swing_acc: torch.Tensor = None,
+                                    stance: torch.Tensor = None, qdd_ref: torch.Tensor = None, weights: dict = None,
+                                    armature: bool = False):
+        """The classical whole-body controller as one call (include/wbc_sim.h: wbc_sim_task_inverse_dynamics): the joint torques that
+        give the trunk the acceleration base_acc [N, 6], the gripper ee_acc [N, 6] (linear, angular; world axes) and the swing feet
+        the linear accelerations swing_acc [N, 4, 3], while the stance feet (stance bool [N, 4] such as get_foot_contacts(), None: all
+        four) stay put. A task that is None carries no weight; a foot's task weight is 0 where it stands, so swing_acc needs a
+        stance mask (it is refused with stance=None, where every foot stands). qdd_ref [N, 26]: the
+        posture term's target for nudot (None: zeros). weights: dict with any of base, ee, swing (task weights, default 1), posture,
+        force, torque, damping (defaults of WbcSim.task_inverse_dynamics). No friction cones or torque limits: clamp the result.
+        Returns (torques [N, 20] for sim.set_dof_forces, nudot [N, 26], foot_forces [N, 4, 3])."""
+        if self.__dict__.get("_feet_list") is None:
+            self._feet_list = [int(i) for i in self.feet_indices.tolist()]
+        n, dev = self.num_envs, self.device
+        wts = dict(base=1.0, ee=1.0, swing=1.0)
+        wts.update(weights or {})
+        acc = torch.zeros((n, 6, 6), dtype=torch.float32, device=dev)
+        w = torch.zeros((n, 6, 6), dtype=torch.float32, device=dev)
+        if base_acc is not None:
+            acc[:, 0], w[:, 0] = base_acc, float(wts["base"])
+        if ee_acc is not None:
+            acc[:, 1], w[:, 1] = ee_acc, float(wts["ee"])
+        if swing_acc is not None:
+            assert stance is not None, "swing_acc needs a stance mask: with stance=None all four feet stand and no foot has a swing task"
+            acc[:, 2:, 0:3] = swing_acc
+            w[:, 2:, 0:3] = float(wts["swing"]) * (~stance.bool()).float().unsqueeze(-1)
+        scalars = {k: float(wts[k]) for k in ("posture", "force", "torque", "damping") if k in wts}
+        tau, nudot, lam = self.sim.task_inverse_dynamics(self._feet_list, [0, int(self.gripper_idx)] + self._feet_list, acc, w,
+                                                         active=stance, nudot_ref=qdd_ref, armature=armature, **scalars)
+        return tau[:, 6:].contiguous(), nudot, lam
+
     # ---- centre of mass and centroidal momentum (no counterpart in the reference): one launch, include/wbc_sim.h: wbc_sim_centroidal ----
     def centre_of_mass(self):
         """(position [N, 3], velocity [N, 3]) of the robot's centre of mass in the world frame: the root position plus the kernel's

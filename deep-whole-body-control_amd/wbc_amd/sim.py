@@ -302,6 +302,53 @@ class WbcSim:
                                                   self._stream()), "wbc_sim_constrained_dynamics")
         return nudot, lam
 
+    # ---- whole-body inverse dynamics for task-space accelerations (include/wbc_sim.h: wbc_sim_task_inverse_dynamics) ------------------
+    def task_inverse_dynamics(self, stance_bodies=(), task_bodies=(), task_acc: Optional[torch.Tensor] = None,
+                              task_weight: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,
+                              stance_acc: Optional[torch.Tensor] = None, nudot_ref: Optional[torch.Tensor] = None,
+                              posture: float = 1e-2, force: float = 1e-4, torque: float = 1e-3, damping: float = 0.0,
+                              armature: bool = False, out=None):
+        """wbc_sim_task_inverse_dynamics on the current stream: the joint torques that give the origins of task_bodies (0..6 rigid-body
+        indices) the accelerations task_acc [N, T, 6] (linear, angular; per-row weights task_weight [N, T, 6] >= 0, None: ones) while
+        the origins of stance_bodies (0..4 indices) keep the linear accelerations stance_acc [N, K, 3] (None: zeros) where active
+        [N, K] (bool or uint8; None: all), in the weighted least-squares sense of include/wbc_sim.h with the scalar weights posture
+        (towards nudot_ref [N, 26], None: zeros), force, torque (> 0) and the Delassus damping. No inequalities: clamp the result.
+        Returns (tau [N, 26], nudot [N, 26], lam [N, K, 3]): tau[:, 6:] is what set_dof_forces takes, rows 0:6 and the fingers are
+        exactly 0. out: an optional (tau, nudot, lam) triple to fill. The workspace is cached per (K, T)."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        srb = [int(r) for r in (stance_bodies.tolist() if isinstance(stance_bodies, torch.Tensor) else stance_bodies)]
+        trb = [int(r) for r in (task_bodies.tolist() if isinstance(task_bodies, torch.Tensor) else task_bodies)]
+        k, t = len(srb), len(trb)
+        assert 0 <= k <= 4 and 0 <= t <= 6, (k, t)
+        assert t == 0 or task_acc is not None, "task_acc is needed with task bodies"
+        tau, nudot, lam = out if out is not None else (None, None, None)
+        if tau is None:
+            tau = torch.empty((n, ncol), dtype=torch.float32, device=self.device)
+        if nudot is None:
+            nudot = torch.empty((n, ncol), dtype=torch.float32, device=self.device)
+        if lam is None:
+            lam = torch.empty((n, k, 3), dtype=torch.float32, device=self.device)
+        for x, shape in ((task_acc, (n, t, 6)), (task_weight, (n, t, 6)), (stance_acc, (n, k, 3)), (nudot_ref, (n, ncol)), (tau, (n, ncol)),
+                         (nudot, (n, ncol)), (lam, (n, k, 3))):
+            if x is not None:
+                assert x.device == self.arena.device and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == shape, tuple(x.shape)
+        if active is not None:
+            assert active.device == self.arena.device and active.dtype in (torch.bool, torch.uint8) and tuple(active.shape) == (n, k)
+            active = active.contiguous()
+            if active.dtype == torch.bool:
+                active = active.view(torch.uint8)
+        cache = self.__dict__.setdefault("_taskid_ws", {})
+        if (k, t) not in cache:
+            cache[(k, t)] = torch.empty(int(self.L.wbc_sim_task_inverse_dynamics_workspace_floats(n, k, t)), dtype=torch.float32,
+                                        device=self.device)
+        ptr = lambda x: x.data_ptr() if x is not None and x.numel() > 0 else None
+        w = abi.WbcTaskIdWeights(float(posture), float(force), float(torque), float(damping))
+        check(self.L.wbc_sim_task_inverse_dynamics(self.h, (C.c_int32 * max(k, 1))(*srb), k, ptr(active), ptr(stance_acc),
+                                                   (C.c_int32 * max(t, 1))(*trb), t, ptr(task_acc), ptr(task_weight), ptr(nudot_ref),
+                                                   C.byref(w), 1 if armature else 0, tau.data_ptr(), nudot.data_ptr(), ptr(lam),
+                                                   cache[(k, t)].data_ptr(), self._stream()), "wbc_sim_task_inverse_dynamics")
+        return tau, nudot, lam
+
     # ---- centre of mass, centroidal momentum and its matrix (include/wbc_sim.h: wbc_sim_centroidal) ----------------------------------
     def centroidal(self, nudot: Optional[torch.Tensor] = None, com: Optional[torch.Tensor] = None, mom: Optional[torch.Tensor] = None,
                    cmm: Optional[torch.Tensor] = None, inertia: Optional[torch.Tensor] = None):

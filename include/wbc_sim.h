@@ -706,6 +706,58 @@ int wbc_sim_constrained_dynamics(wbc_sim* sim, const int32_t* rigid_bodies /* ho
                                  const float* tau, const float* acc_des, float damping, int flags, float* nudot, float* lambda,
                                  float* workspace, void* stream);
 
+/* Whole-body inverse dynamics for task-space accelerations: the joint torques that produce wanted accelerations of a few rigid bodies
+ * while the stance feet stay put. Coordinates, nu, nudot, tau rows and rigid-body indices are those of wbc_sim_body_dynamics /
+ * wbc_sim_inverse_dynamics / wbc_sim_constrained_dynamics; state, WBC_T_BODY_PARAMS and all three gravity components as there. Per env:
+ *     minimise over (nudot, lambda, tau_j)
+ *         1/2 sum_{k<ntasks} sum_{i<6} w[k,i] ((J_k nudot + Jdot_k nu)_i - acc[k,i])^2     origin of task body k: linear 0:3, angular 3:6
+ *       + 1/2 posture |nudot - nudot_ref|^2 (24 live coordinates) + 1/2 force |lambda|^2 + 1/2 torque |tau_j|^2
+ *     subject to
+ *         M nudot + h = S^T tau_j + sum_r J_r^T lambda_r                 (the six root rows carry no actuation)
+ *         J_r nudot + (Jdot nu)_r = stance_acc_r - damping lambda_r      for every ACTIVE stance body r (three linear rows)
+ * tau_j are the 18 revolute joint torques; the locked fingers' entries are exactly 0 everywhere. torque > 0 makes the solution unique
+ * for every stance pattern. NO INEQUALITIES are offered: no friction cones, no unilateral contact and no torque limits -- a caller
+ * clamps the result, or raises `force` / `torque`.
+ * stance_bodies  HOST array of nstance (0..WBC_TASKID_MAX_STANCE) rigid-body indices, e.g. the four feet.
+ * active      device u8 [N, nstance] or NULL (= all active). An inactive body contributes no constraint, its lambda is exactly 0 and
+ *             its stance_acc is never read (a NaN there does not spread).
+ * stance_acc  device f32 [N, nstance, 3] or NULL (= zeros).
+ * task_bodies HOST array of ntasks (0..WBC_TASKID_MAX_TASKS) rigid-body indices. A body may be both a stance and a task body (a foot
+ *             that swings in one env and stands in the next: task weight 0 where it is active).
+ * task_acc    device f32 [N, ntasks, 6]; task_weight device f32 [N, ntasks, 6] >= 0 or NULL (= ones). A row of weight 0 is skipped and
+ *             its task_acc is never read.
+ * nudot_ref   device f32 [N, 26] or NULL (= zeros). weights: HOST struct; damping as in wbc_sim_constrained_dynamics.
+ * flags       0 or WBC_SOLVE_ARMATURE (M + armature throughout).
+ * tau         device f32 [N, 26]: rows 0:6 and the fingers exactly 0, rows 6: tau_j in DoF order (tau[:, 6:] is what
+ *             wbc_sim_set_dof_forces takes). nudot: device f32 [N, 26] or NULL. lambda: device f32 [N, nstance, 3] or NULL; the force
+ *             applied TO the robot, as in wbc_sim_constrained_dynamics.
+ * workspace   caller-owned device floats, at least wbc_sim_task_inverse_dynamics_workspace_floats(N, nstance, ntasks) of them (0 for a
+ *             bad argument). Nothing is allocated in the call, so it is safe under stream capture. The sim's bias-force scratch is used
+ *             as well: one stream at a time per sim.
+ * Four launches on `stream`, no host synchronisation: h, the right-hand sides [J_c^T | -h | S^T] with the task rows
+ * (wbc_taskid_rhs_kernel), the mass solve with 3 nstance + 19 right-hand sides, and wbc_taskid_solve_kernel: the problem reduced to
+ * the 18 torques through stance-constrained forward dynamics and solved in square-root form (Householder reflections of the stacked
+ * sqrt(weight)-scaled rows, at most 90 x 19); (nudot, lambda) are then those of constrained forward dynamics with tau.
+ * The root POSITION is never read: outputs are bit-identical under a translation of the robot.
+ * Accuracy (fp32): the equations of motion and the stance rows hold to the rounding of wbc_sim_constrained_dynamics for every call.
+ * First-order optimality holds to fp32 rounding of the SIZES of the objective's terms (|J nudot| + |Jdot nu| + |acc|, |nudot| +
+ * |nudot_ref|, |lambda|, |tau|). It is NOT held to that level where a term is a small difference of large fp32 quantities that those
+ * sizes do not show: with ntasks = 0 and nudot_ref = 0 (or NULL) the posture term pins the light wrist joints' accelerations near 0
+ * while a_0 = -M^-1 h and M^-1 S^T tau_j are each tens of rad/s^2 there; the reduced gradient then sits one to two orders above its
+ * level with tasks or with a reference of the size of the accelerations at play.
+ * -1 with a message in wbc_last_error(), nothing written: NULL sim / tau / workspace / weights; NULL stance_bodies, task_bodies or
+ * task_acc with its count above 0; a count out of range; an index outside 0..WBC_NRB-1; two stance entries, or two task entries, on the
+ * same moving body; torque <= 0 or not finite; posture, force or damping negative or not finite; unknown flag bits; a pointer that is
+ * not 4-byte aligned. -3 / -2 as wbc_sim_mass_solve. */
+#define WBC_TASKID_MAX_STANCE 4
+#define WBC_TASKID_MAX_TASKS 6
+typedef struct { float posture, force, torque, damping; } wbc_taskid_weights;
+size_t wbc_sim_task_inverse_dynamics_workspace_floats(int num_envs, int nstance, int ntasks);
+int wbc_sim_task_inverse_dynamics(wbc_sim* sim, const int32_t* stance_bodies /* host */, int nstance, const uint8_t* active,
+                                  const float* stance_acc, const int32_t* task_bodies /* host */, int ntasks, const float* task_acc,
+                                  const float* task_weight, const float* nudot_ref, const wbc_taskid_weights* weights /* host */,
+                                  int flags, float* tau, float* nudot, float* lambda, float* workspace, void* stream);
+
 /* Centre of mass, centroidal momentum, its rate, the centroidal momentum matrix and the locked centroidal inertia of the robot, in the
  * coordinates of wbc_sim_body_dynamics (nu = (v_root, omega_root, qd), world axes, 26 columns) with the inertias of the per-env
  * WBC_T_BODY_PARAMS, from the sim's current root / DoF state. One launch (wbc_centroidal_kernel).
