@@ -10,6 +10,7 @@
 
 #include "wbc_device.h"
 #include "wbc_stream_guard.h"
+#include "wbc_tree.h"
 
 #define ARM_N 6
 #define ARM_NLINK 9          // rigid bodies whose weight the reference compensates: the last 9 of the actor
@@ -214,14 +215,8 @@ extern "C" int wbc_sim_arm_dynamics(wbc_sim* s, const int* link_rb9, const float
 #define BD_JCHUNK 9                            // rigid bodies per LDS chunk of J (5.6 KB)
 static_assert(WBC_NRB % BD_JCHUNK == 0 && (BD_JCHUNK * BD_JROW) % 4 == 0, "J chunks");
 
-struct BodyConst {
-  int32_t parent[WBC_NB], axis[WBC_NB], dof[WBC_NB];
-  uint32_t anc[WBC_NB];                        // bit a: moving body a is on the path root..b (b included)
-  int32_t col_body[WBC_NDOF];                  // moving body DoF d drives; -1: none (the locked fingers)
-  int32_t rb_body[WBC_NRB];
-  int32_t gripper_body;
-  float rb_offset[WBC_NRB][3];
-  float joint_xyz[WBC_NB][3], mass[WBC_NB], com[WBC_NB][3], inertia[WBC_NB][6];
+struct BodyConst : TreeJoints, TreeCols, TreeRigid, TreeInertia {
+  int32_t parent[WBC_NB];                      // this kernel walks from b UP to the root
 };
 
 extern "C" __global__ void __launch_bounds__(64) wbc_body_dynamics_kernel(BodyConst B, const float* __restrict__ root,
@@ -249,15 +244,8 @@ extern "C" __global__ void __launch_bounds__(64) wbc_body_dynamics_kernel(BodyCo
     f3 p = mk3(0.f, 0.f, 0.f);
     int a = b;
     for (int it = 0; it < WBC_MAX_DEPTH && a > 0; ++it) {      // (E, p) <- (Rot_a E, xyz_a + Rot_a p)
-      const int ax = B.axis[a];
-      const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
-      float s, c;
-      sincosf(dofs[(size_t)env * (2 * WBC_NDOF) + 2 * B.dof[a]], &s, &c);
-      const float t = 1.f - c;
-      const float Q[9] = {c + t * ux * ux, t * ux * uy - s * uz, t * ux * uz + s * uy,
-                          t * uy * ux + s * uz, c + t * uy * uy, t * uy * uz - s * ux,
-                          t * uz * ux - s * uy, t * uz * uy + s * ux, c + t * uz * uz};
-      float En[9];
+      float Q[9], En[9];
+      tree_joint_rot(B.axis[a], dofs[(size_t)env * (2 * WBC_NDOF) + 2 * B.dof[a]], Q);
 #pragma unroll
       for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -274,33 +262,25 @@ extern "C" __global__ void __launch_bounds__(64) wbc_body_dynamics_kernel(BodyCo
     float m = B.mass[b], com[3] = {B.com[b][0], B.com[b][1], B.com[b][2]}, I6[6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) I6[j] = B.inertia[b][j];
-    const int slot = b == 0 ? 0 : (b == B.gripper_body ? 10 : -1);
+    const int slot = b == 0 ? TREE_BP_ROOT : (b == B.gripper_body ? TREE_BP_GRIPPER : -1);
     if (slot >= 0) {
-      const float* bp = body_params + (size_t)env * 20 + slot;
+      const float* bp = body_params + (size_t)env * TREE_BP_STRIDE + slot;
       m = bp[0];
 #pragma unroll
       for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
 #pragma unroll
       for (int j = 0; j < 6; ++j) I6[j] = bp[4 + j];
     }
+    float Ibar[6];
     const f3 C = p + mat_mul(E, mk3(com[0], com[1], com[2]));
-    const float Ib[9] = {I6[0], I6[3], I6[4], I6[3], I6[1], I6[5], I6[4], I6[5], I6[2]};
-    float EI[9], Ibar[9];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) EI[r * 3 + k] = E[r * 3] * Ib[k] + E[r * 3 + 1] * Ib[3 + k] + E[r * 3 + 2] * Ib[6 + k];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) Ibar[r * 3 + k] = EI[r * 3] * E[k * 3] + EI[r * 3 + 1] * E[k * 3 + 1] + EI[r * 3 + 2] * E[k * 3 + 2];
+    tree_rotate_inertia(E, I6, Ibar);
     const float CC = dot(C, C);
     sI[b][0] = m; sI[b][1] = m * C.x; sI[b][2] = m * C.y; sI[b][3] = m * C.z;
     sI[b][4] = Ibar[0] + m * (CC - C.x * C.x);
-    sI[b][5] = Ibar[4] + m * (CC - C.y * C.y);
-    sI[b][6] = Ibar[8] + m * (CC - C.z * C.z);
-    sI[b][7] = Ibar[1] - m * C.x * C.y;
-    sI[b][8] = Ibar[2] - m * C.x * C.z;
+    sI[b][5] = Ibar[1] + m * (CC - C.y * C.y);
+    sI[b][6] = Ibar[2] + m * (CC - C.z * C.z);
+    sI[b][7] = Ibar[3] - m * C.x * C.y;
+    sI[b][8] = Ibar[4] - m * C.x * C.z;
     sI[b][9] = Ibar[5] - m * C.y * C.z;
     const int ax = B.axis[b];                                  // -1 for the root: no joint axis
     const f3 axF = mk3(ax == 0 ? E[0] : ax == 1 ? E[1] : ax == 2 ? E[2] : 0.f,
@@ -424,58 +404,114 @@ extern "C" __global__ void __launch_bounds__(64) wbc_body_dynamics_kernel(BodyCo
   }
 }
 
+// ---- host side of the whole-body calls ------------------------------------------------------------------------------------------------
 extern "C" int wbc_sim_internal_fail(int code, const char* msg);
 
-// Fills B from the model. 0, or 1: a tree the kernels cannot walk, 2: a rigid body that rides on no moving body.
-static int body_const_fill(const wbc_model& m, BodyConst& B) {
-  for (int d = 0; d < WBC_NDOF; ++d) B.col_body[d] = -1;
+// What every whole-body entry point starts from: the stream's device current for the call's duration, the sim's state tensors (`have`:
+// there is a sim) and the refusals "<entry point>: <what>" for wbc_last_error(). Its own argument checks stay in the entry point, in order.
+struct WbCall {
+  StreamDeviceGuard sdg;
+  const char* who;
+  const DevConst* hc = nullptr;
+  const float *root = nullptr, *dofs = nullptr, *bp = nullptr, *mp = nullptr;
+  int n = 0;
+  bool have;
+  WbCall(const char* who_, wbc_sim* s, void* stream) : sdg(stream), who(who_) {
+    have = s && wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) == 0;
+  }
+  int fail(int code, const char* what) const {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return wbc_sim_internal_fail(code, msg);
+  }
+  int no_sim() const { return fail(-1, "sim is NULL"); }
+  int no_state() const { return fail(-1, "no sim state"); }
+  int no_tree() const { return fail(-3, "the model's tree is not one the kernel walks"); }
+  int launched() const { return hipGetLastError() == hipSuccess ? 0 : fail(-2, "launch failed"); }   // after a launch
+};
+
+// The parts of the argument structs (wbc_tree.h) from the model, one function each. 0, or 1: a tree the kernels cannot walk.
+static int tree_joints_fill(const wbc_model& m, TreeJoints& J) {
   for (int b = 0; b < WBC_NB; ++b) {
-    B.parent[b] = m.parent[b]; B.axis[b] = m.axis[b]; B.dof[b] = m.dof[b]; B.mass[b] = m.mass[b];
-    for (int j = 0; j < 3; ++j) { B.joint_xyz[b][j] = m.joint_xyz[b][j]; B.com[b][j] = m.com[b][j]; }
-    for (int j = 0; j < 6; ++j) B.inertia[b][j] = m.inertia[b][j];
+    J.axis[b] = m.axis[b]; J.dof[b] = m.dof[b];
+    for (int j = 0; j < 3; ++j) J.joint_xyz[b][j] = m.joint_xyz[b][j];
     // the kernels walk at most WBC_MAX_DEPTH joints between a body and the root and index 32-bit ancestor masks
-    uint32_t anc = 1u << b;
     int depth = 0;
-    for (int a = b; a > 0; a = m.parent[a]) {
+    for (int a = b; a > 0; a = m.parent[a])
       if (m.parent[a] < 0 || m.parent[a] >= a || ++depth > WBC_MAX_DEPTH || m.axis[a] < 0 || m.axis[a] > 2 || m.dof[a] < 0 || m.dof[a] >= WBC_NDOF)
         return 1;
-      anc |= 1u << m.parent[a];
-    }
-    B.anc[b] = anc;
-    if (b > 0) B.col_body[m.dof[b]] = b;
   }
+  return 0;
+}
+static int tree_walk_fill(const wbc_model& m, TreeWalk& W) {
+  if (tree_joints_fill(m, W) != 0) return 1;
+  for (int b = 0; b < WBC_NB; ++b) {
+    int up[WBC_MAX_DEPTH], depth = 0;                          // tree_joints_fill bounded the depth
+    for (int a = b; a > 0; a = m.parent[a]) up[depth++] = a;
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k) W.path[b][k] = k < depth ? up[depth - 1 - k] : -1;
+  }
+  return 0;
+}
+static void tree_cols_fill(const wbc_model& m, TreeCols& C) {
+  for (int d = 0; d < WBC_NDOF; ++d) C.col_body[d] = -1;
+  for (int b = 0; b < WBC_NB; ++b) {
+    C.anc[b] = 1u << b;
+    for (int a = b; a > 0; a = m.parent[a]) C.anc[b] |= 1u << m.parent[a];
+    if (b > 0) C.col_body[m.dof[b]] = b;
+  }
+}
+static bool tree_rigid_ok(const wbc_model& m) {
+  for (int r = 0; r < WBC_NRB; ++r)
+    if (m.rb_body[r] < 0 || m.rb_body[r] >= WBC_NB) return false;
+  return true;
+}
+// 0, or 2: a rigid body that rides on no moving body.
+static int tree_rigid_fill(const wbc_model& m, TreeRigid& B) {
+  if (!tree_rigid_ok(m)) return 2;
   for (int r = 0; r < WBC_NRB; ++r) {
-    if (m.rb_body[r] < 0 || m.rb_body[r] >= WBC_NB) return 2;
     B.rb_body[r] = m.rb_body[r];
     for (int j = 0; j < 3; ++j) B.rb_offset[r][j] = m.rb_offset[r][j];
   }
-  B.gripper_body = m.gripper_body;
+  return 0;
+}
+static void tree_inertia_fill(const wbc_model& m, TreeInertia& I) {
+  I.gripper_body = m.gripper_body;
+  for (int b = 0; b < WBC_NB; ++b) {
+    I.mass[b] = m.mass[b];
+    for (int j = 0; j < 3; ++j) I.com[b][j] = m.com[b][j];
+    for (int j = 0; j < 6; ++j) I.inertia[b][j] = m.inertia[b][j];
+  }
+}
+// 0, or 1: a model the whole-body calls refuse (a bad rb_body too, whether or not the kernel reads the rigid bodies).
+static int tree_const_fill(const wbc_model& m, TreeConst& K) {
+  if (tree_walk_fill(m, K) != 0 || !tree_rigid_ok(m)) return 1;
+  tree_cols_fill(m, K); tree_inertia_fill(m, K);
   return 0;
 }
 
 // Outputs (device, caller-owned, 16-byte aligned, either may be NULL): jac f32 [N,27,6,26], mm f32 [N,26,26] (include/wbc_sim.h).
 extern "C" int wbc_sim_body_dynamics(wbc_sim* s, float* jac, float* mm, void* stream) {
-  StreamDeviceGuard sdg(stream);
-  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: sim is NULL");
-  if (!jac && !mm) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: jac and mm are both NULL");
-  if (((uintptr_t)jac | (uintptr_t)mm) & 15u) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: jac / mm must be 16-byte aligned");
-  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_body_dynamics: no sim state");
+  WbCall c("wbc_sim_body_dynamics", s, stream);
+  if (!s) return c.no_sim();
+  if (!jac && !mm) return c.fail(-1, "jac and mm are both NULL");
+  if (((uintptr_t)jac | (uintptr_t)mm) & 15u) return c.fail(-1, "jac / mm must be 16-byte aligned");
+  if (!c.have) return c.no_state();
+  const wbc_model& m = c.hc->model;
   BodyConst B;
-  switch (body_const_fill(hc->model, B)) {
-    case 1: return wbc_sim_internal_fail(-3, "wbc_sim_body_dynamics: the model's tree is not one the kernel walks");
-    case 2: return wbc_sim_internal_fail(-3, "wbc_sim_body_dynamics: bad rb_body");
-  }
+  if (tree_joints_fill(m, B) != 0) return c.no_tree();
+  if (tree_rigid_fill(m, B) != 0) return c.fail(-3, "bad rb_body");
+  tree_cols_fill(m, B); tree_inertia_fill(m, B);
+  for (int b = 0; b < WBC_NB; ++b) B.parent[b] = m.parent[b];
   // the J chunk is dynamic LDS: a mass-matrix-only refresh keeps the small footprint (twice the resident envs per CU)
   const size_t jbytes = jac ? BD_JCHUNK * BD_JROW * sizeof(float) : 0;
-  hipLaunchKernelGGL(wbc_body_dynamics_kernel, dim3(n), dim3(64), jbytes, (hipStream_t)stream, B, root, dofs, bp, n, jac, mm);
-  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_body_dynamics: launch failed");
+  hipLaunchKernelGGL(wbc_body_dynamics_kernel, dim3(c.n), dim3(64), jbytes, (hipStream_t)stream, B, c.root, c.dofs, c.bp, c.n, jac, mm);
+  return c.launched();
 }
 
 // ---- whole-body inverse dynamics: tau = M nudot + C nu + g in the coordinates of wbc_sim_body_dynamics (include/wbc_sim.h) ---------
 // Recursive Newton-Euler with every spatial vector about F's origin in F's axes, so neither pass needs a parent-child transform.
 // Two envs per 64-lane workgroup, one per 32-lane half (19 bodies / 26 columns fit in 32 lanes); two phases, ONE LDS hand-over:
-//  1) lane b = moving body b walks its ancestor path from the root DOWN (IdConst::path) and carries in registers the frame (E, p),
+//  1) lane b = moving body b walks its ancestor path from the root DOWN (TreeWalk::path), one tree_frame_step per joint, and carries in registers the frame (E, p),
 //     the spatial velocity and the spatial acceleration. The depth-sequential velocity-product term v x S qd is thereby a
 //     loop-carried register dependence of at most WBC_MAX_DEPTH steps (each lane redoes its ancestors' joints) instead of an LDS
 //     round trip per tree level. Then the body's force m a_com and its moment about F's origin (from I_b alpha + omega x I_b omega
@@ -489,15 +525,7 @@ extern "C" int wbc_sim_body_dynamics(wbc_sim* s, float* jac, float* mm, void* st
 #define ID_EPW 2                                // envs per workgroup: 2, or 1 (-DID_EPW=1, the variant DESIGN.md compares with)
 #endif
 static_assert(ID_EPW == 1 || ID_EPW == 2, "one env per 64 lanes or one per 32-lane half");
-struct IdConst {
-  int32_t axis[WBC_NB], dof[WBC_NB];
-  int32_t path[WBC_NB][WBC_MAX_DEPTH];         // moving bodies on the way root -> b (root excluded, b last), padded with -1
-  uint32_t anc[WBC_NB];                        // as BodyConst::anc
-  int32_t col_body[WBC_NDOF];
-  int32_t gripper_body;
-  float joint_xyz[WBC_NB][3], mass[WBC_NB], com[WBC_NB][3], inertia[WBC_NB][6];
-  float gravity[3];
-};
+struct IdConst : TreeConst { float gravity[3]; };
 
 extern "C" __global__ void __launch_bounds__(64) wbc_inverse_dynamics_kernel(IdConst K, const float* __restrict__ root,
                                                                             const float* __restrict__ dofs,
@@ -527,26 +555,14 @@ extern "C" __global__ void __launch_bounds__(64) wbc_inverse_dynamics_kernel(IdC
       if (nudot) { av = matT_mul(R, ld3(nudot + e * BD_NCOL)); aw = matT_mul(R, ld3(nudot + e * BD_NCOL + 3)); }
       av = av - cross(vw, vv);
     }
+#pragma nounroll                                  // kept a loop, as the compiler chose to while the step was written out here
     for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
       const int a = K.path[b][k];
       if (a < 0) break;
-      const int ax = K.axis[a], d = K.dof[a];
-      const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
-      float s, c;
-      sincosf(dofs[e * (2 * WBC_NDOF) + 2 * d], &s, &c);
-      const float t = 1.f - c;
-      const float Q[9] = {c + t * ux * ux, t * ux * uy - s * uz, t * ux * uz + s * uy,
-                          t * uy * ux + s * uz, c + t * uy * uy, t * uy * uz - s * ux,
-                          t * uz * ux - s * uy, t * uz * uy + s * ux, c + t * uz * uz};
-      p = p + mat_mul(E, mk3(K.joint_xyz[a][0], K.joint_xyz[a][1], K.joint_xyz[a][2]));     // (E, p) <- (E Rot_a, p + E xyz_a)
-      float En[9];
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) En[r * 3 + j] = E[r * 3] * Q[j] + E[r * 3 + 1] * Q[3 + j] + E[r * 3 + 2] * Q[6 + j];
-#pragma unroll
-      for (int j = 0; j < 9; ++j) E[j] = En[j];
-      Sw = mat_mul(E, mk3(ux, uy, uz));
+      const int d = K.dof[a];
+      float Q[9];
+      const f3 u = tree_joint_rot(K.axis[a], dofs[e * (2 * WBC_NDOF) + 2 * d], Q);
+      Sw = tree_frame_step(E, p, Q, K.joint_xyz[a], u);
       Sv = cross(p, Sw);
       if (dyn) {
         const float qd = dofs[e * (2 * WBC_NDOF) + 2 * d + 1], qdd = nudot ? nudot[e * BD_NCOL + 6 + d] : 0.f;
@@ -560,9 +576,9 @@ extern "C" __global__ void __launch_bounds__(64) wbc_inverse_dynamics_kernel(IdC
     float m = K.mass[b], com[3] = {K.com[b][0], K.com[b][1], K.com[b][2]}, I6[6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) I6[j] = K.inertia[b][j];
-    const int slot = b == 0 ? 0 : (b == K.gripper_body ? 10 : -1);
+    const int slot = b == 0 ? TREE_BP_ROOT : (b == K.gripper_body ? TREE_BP_GRIPPER : -1);
     if (slot >= 0) {
-      const float* bp = body_params + e * 20 + slot;
+      const float* bp = body_params + e * TREE_BP_STRIDE + slot;
       m = bp[0];
 #pragma unroll
       for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
@@ -573,7 +589,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_inverse_dynamics_kernel(IdC
     // and the lever is the model's: a force that (nearly) passes through the axis then yields its small torque to fp32 accuracy,
     // which the difference of two moments about the far base origin would not. Descendants reach the joint through F (phase 2).
     const int axb = K.axis[b];                                 // -1 for the root: no joint axis
-    const f3 cm = mk3(com[0], com[1], com[2]), ub = mk3(axb == 0 ? 1.f : 0.f, axb == 1 ? 1.f : 0.f, axb == 2 ? 1.f : 0.f);
+    const f3 cm = mk3(com[0], com[1], com[2]), ub = tree_axis(axb);
     const f3 C = p + mat_mul(E, cm), h = m * C, lev = cross(cm, ub);
     float* o = sF[half][b];
     if (dyn) {
@@ -640,39 +656,26 @@ extern "C" __global__ void __launch_bounds__(64) wbc_inverse_dynamics_kernel(IdC
   }
 }
 
-// Fills K from the model. 0, or 1: a tree the kernels cannot walk.
+// Fills K from the model. 0, or 1: a model the kernels refuse.
 static int id_const_fill(const DevConst* hc, IdConst& K) {
-  BodyConst B;
-  if (body_const_fill(hc->model, B) != 0) return 1;
-  for (int d = 0; d < WBC_NDOF; ++d) K.col_body[d] = B.col_body[d];
-  for (int b = 0; b < WBC_NB; ++b) {
-    K.axis[b] = B.axis[b]; K.dof[b] = B.dof[b]; K.anc[b] = B.anc[b]; K.mass[b] = B.mass[b];
-    for (int j = 0; j < 3; ++j) { K.joint_xyz[b][j] = B.joint_xyz[b][j]; K.com[b][j] = B.com[b][j]; }
-    for (int j = 0; j < 6; ++j) K.inertia[b][j] = B.inertia[b][j];
-    int up[WBC_MAX_DEPTH], depth = 0;                          // body_const_fill bounded the depth
-    for (int a = b; a > 0; a = B.parent[a]) up[depth++] = a;
-    for (int k = 0; k < WBC_MAX_DEPTH; ++k) K.path[b][k] = k < depth ? up[depth - 1 - k] : -1;
-  }
-  K.gripper_body = B.gripper_body;
+  if (tree_const_fill(hc->model, K) != 0) return 1;
   for (int j = 0; j < 3; ++j) K.gravity[j] = hc->cfg.gravity[j];
   return 0;
 }
 
 // nudot (device f32 [N,26] or NULL = zeros), tau / grav (device f32 [N,26], caller-owned, either may be NULL): include/wbc_sim.h.
 extern "C" int wbc_sim_inverse_dynamics(wbc_sim* s, const float* nudot, float* tau, float* grav, void* stream) {
-  StreamDeviceGuard sdg(stream);
-  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: sim is NULL");
-  if (!tau && !grav) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: tau and grav are both NULL");
-  if (((uintptr_t)nudot | (uintptr_t)tau | (uintptr_t)grav) & 3u)
-    return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: nudot / tau / grav must be 4-byte aligned");
-  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics: no sim state");
-  if (n <= 0) return 0;
+  WbCall c("wbc_sim_inverse_dynamics", s, stream);
+  if (!s) return c.no_sim();
+  if (!tau && !grav) return c.fail(-1, "tau and grav are both NULL");
+  if (((uintptr_t)nudot | (uintptr_t)tau | (uintptr_t)grav) & 3u) return c.fail(-1, "nudot / tau / grav must be 4-byte aligned");
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
   IdConst K;
-  if (id_const_fill(hc, K) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_inverse_dynamics: the model's tree is not one the kernel walks");
-  hipLaunchKernelGGL(wbc_inverse_dynamics_kernel, dim3((n + ID_EPW - 1) / ID_EPW), dim3(64), 0, (hipStream_t)stream, K, root, dofs, bp, nudot, n,
-                     tau, grav);
-  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_inverse_dynamics: launch failed");
+  if (id_const_fill(c.hc, K) != 0) return c.no_tree();
+  hipLaunchKernelGGL(wbc_inverse_dynamics_kernel, dim3((c.n + ID_EPW - 1) / ID_EPW), dim3(64), 0, (hipStream_t)stream, K, c.root, c.dofs, c.bp, nudot,
+                     c.n, tau, grav);
+  return c.launched();
 }
 
 // ---- mass-matrix solves: out = M^-1 rhs in the coordinates of wbc_sim_body_dynamics (include/wbc_sim.h) ------------------------------
@@ -681,7 +684,7 @@ extern "C" int wbc_sim_inverse_dynamics(wbc_sim* s, const float* nudot, float* t
 // root and its own. Row s of M is kept in LDS as [the root columns | its chain's columns up to itself]: position u of a row is the same
 // coordinate in the rows of all its ancestors, and nothing outside these rows is ever non-zero -- Featherstone's L^T D L factorisation
 // (leaves first) has no fill-in. MS_EPW envs per 64-lane workgroup, one per lane group:
-//  1) lane b = moving body b: forward kinematics root -> b in registers (as wbc_inverse_dynamics_kernel), centre of mass and
+//  1) lane b = moving body b: forward kinematics root -> b in registers (tree_frame_step per joint), centre of mass and
 //     rotational inertia about it in F to LDS;
 //  2) lane s = coordinate s: composite of the subtree it moves ABOUT ITS OWN JOINT ORIGIN (the root: F's origin), so that the light
 //     wrist joints' entries are not the difference of two moments about the far base origin, and F_s = Ic_s S_s;
@@ -701,7 +704,7 @@ static_assert(MS_EPW == 1 || MS_EPW == 2, "one env per 64 lanes or one per 32-la
 #define MS_TN ((WBC_NB + MS_NS) * MS_BT)        // those tables; the solve's hand-over between its two passes reuses them
 static_assert(WBC_SOLVE_MAX_RHS <= MS_LPE && (MS_NS - 6) * WBC_SOLVE_MAX_RHS <= MS_TN && WBC_NB <= MS_LPE && MS_NS <= MS_LPE, "lanes / LDS reuse");
 struct MsConst {
-  IdConst K;                                   // tree walk and inertias (gravity unused)
+  TreeConst K;
   int32_t ns;                                  // live coordinates
   int32_t co_body[MS_NS], co_col[MS_NS];       // moving body and column (of 26) of coordinate s
   int32_t co_na[MS_NS], co_anc0[MS_NS];        // number of ancestors; the coordinate at row position 6 (its chain's first joint)
@@ -718,7 +721,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_mass_solve_kernel(MsConst C
   __shared__ float sH[MS_EPW][MS_NS][MS_W];        // rows of M, then of L (unit lower, M = L^T D L)
   __shared__ float sID[MS_EPW][MS_NS];             // 1 / D
   __shared__ float sT[MS_EPW][MS_TN];
-  const IdConst& K = C.K;
+  const TreeConst& K = C.K;
   const int half = MS_EPW == 2 ? threadIdx.x >> 5 : 0, lane = MS_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
   const int env = blockIdx.x * MS_EPW + half;
   const bool live = env < n;
@@ -733,50 +736,31 @@ extern "C" __global__ void __launch_bounds__(64) wbc_mass_solve_kernel(MsConst C
     const int b = lane;
     float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
     f3 p = mk3(0.f, 0.f, 0.f), Sw = p;
+#pragma nounroll                                  // kept a loop, as the compiler chose to while the step was written out here
     for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
       const int a = K.path[b][k];
       if (a < 0) break;
-      const int ax = K.axis[a];
-      const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
-      float s, c;
-      sincosf(dofs[e * (2 * WBC_NDOF) + 2 * K.dof[a]], &s, &c);
-      const float t = 1.f - c;
-      const float Q[9] = {c + t * ux * ux, t * ux * uy - s * uz, t * ux * uz + s * uy,
-                          t * uy * ux + s * uz, c + t * uy * uy, t * uy * uz - s * ux,
-                          t * uz * ux - s * uy, t * uz * uy + s * ux, c + t * uz * uz};
-      p = p + mat_mul(E, mk3(K.joint_xyz[a][0], K.joint_xyz[a][1], K.joint_xyz[a][2]));     // (E, p) <- (E Rot_a, p + E xyz_a)
-      float En[9];
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) En[r * 3 + j] = E[r * 3] * Q[j] + E[r * 3 + 1] * Q[3 + j] + E[r * 3 + 2] * Q[6 + j];
-#pragma unroll
-      for (int j = 0; j < 9; ++j) E[j] = En[j];
-      Sw = mat_mul(E, mk3(ux, uy, uz));
+      float Q[9];
+      const f3 u = tree_joint_rot(K.axis[a], dofs[e * (2 * WBC_NDOF) + 2 * K.dof[a]], Q);
+      Sw = tree_frame_step(E, p, Q, K.joint_xyz[a], u);
     }
-    // the per-env root composite and gripper body (body_params), the model's otherwise
     float m = K.mass[b], com[3] = {K.com[b][0], K.com[b][1], K.com[b][2]}, I6[6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) I6[j] = K.inertia[b][j];
-    const int slot = b == 0 ? 0 : (b == K.gripper_body ? 10 : -1);
+    const int slot = b == 0 ? TREE_BP_ROOT : (b == K.gripper_body ? TREE_BP_GRIPPER : -1);
     if (slot >= 0) {
-      const float* bp = body_params + e * 20 + slot;
+      const float* bp = body_params + e * TREE_BP_STRIDE + slot;
       m = bp[0];
 #pragma unroll
       for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
 #pragma unroll
       for (int j = 0; j < 6; ++j) I6[j] = bp[4 + j];
     }
-    const float Ib[9] = {I6[0], I6[3], I6[4], I6[3], I6[1], I6[5], I6[4], I6[5], I6[2]};
-    float EI[9];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) EI[r * 3 + k] = E[r * 3] * Ib[k] + E[r * 3 + 1] * Ib[3 + k] + E[r * 3 + 2] * Ib[6 + k];
-    auto ibar = [&](int r, int k) { return EI[r * 3] * E[k * 3] + EI[r * 3 + 1] * E[k * 3 + 1] + EI[r * 3 + 2] * E[k * 3 + 2]; };
+    float Iw[6];
+    tree_rotate_inertia(E, I6, Iw);
     float* o = sB + b * MS_BT;
     st3(o, p); st3(o + 3, Sw); o[6] = m; st3(o + 7, p + mat_mul(E, mk3(com[0], com[1], com[2])));
-    o[10] = ibar(0, 0); o[11] = ibar(1, 1); o[12] = ibar(2, 2); o[13] = ibar(0, 1); o[14] = ibar(0, 2); o[15] = ibar(1, 2);
+    o[10] = Iw[0]; o[11] = Iw[1]; o[12] = Iw[2]; o[13] = Iw[3]; o[14] = Iw[4]; o[15] = Iw[5];
   }
   __syncthreads();
 
@@ -903,8 +887,8 @@ extern "C" int wbc_sim_internal_fd_scratch(wbc_sim* s, float** h);
 
 // Fills C from the model and the chains. 0, or 1: a tree the kernel cannot walk.
 static int ms_const_fill(const DevConst* hc, MsConst& C) {
-  if (id_const_fill(hc, C.K) != 0) return 1;
   const wbc_model& m = hc->model;
+  if (tree_const_fill(m, C.K) != 0) return 1;
   for (int s = 0; s < MS_NS; ++s) { C.co_body[s] = 0; C.co_col[s] = s < 6 ? s : 0; C.co_na[s] = s < 6 ? s : 0; C.co_anc0[s] = 6; C.arm[s] = 0.f; }
   int s = 6;
   C.nchain = 0;
@@ -927,55 +911,50 @@ static int ms_const_fill(const DevConst* hc, MsConst& C) {
   return 0;
 }
 
-static int mass_solve_launch(wbc_sim* s, const char* who, const float* rhs, int64_t rhs_env_stride, int nrhs, const float* sub, float* out,
-                             int flags, void* stream) {
-  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
-  char msg[160];
-  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) { snprintf(msg, sizeof msg, "%s: no sim state", who); return wbc_sim_internal_fail(-1, msg); }
-  if (n <= 0) return 0;
+static int mass_solve_launch(const WbCall& c, const float* rhs, int64_t rhs_env_stride, int nrhs, const float* sub, float* out, int flags, void* stream) {
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
   MsConst C;
-  if (ms_const_fill(hc, C) != 0) { snprintf(msg, sizeof msg, "%s: the model's tree is not one the kernel walks", who); return wbc_sim_internal_fail(-3, msg); }
-  hipLaunchKernelGGL(wbc_mass_solve_kernel, dim3((n + MS_EPW - 1) / MS_EPW), dim3(64), 0, (hipStream_t)stream, C, root, dofs, bp, rhs, rhs_env_stride,
-                     nrhs, sub, n, out, (flags & WBC_SOLVE_ARMATURE) ? 1 : 0);
-  if (hipGetLastError() == hipSuccess) return 0;
-  snprintf(msg, sizeof msg, "%s: launch failed", who);
-  return wbc_sim_internal_fail(-2, msg);
+  if (ms_const_fill(c.hc, C) != 0) return c.no_tree();
+  hipLaunchKernelGGL(wbc_mass_solve_kernel, dim3((c.n + MS_EPW - 1) / MS_EPW), dim3(64), 0, (hipStream_t)stream, C, c.root, c.dofs, c.bp, rhs,
+                     rhs_env_stride, nrhs, sub, c.n, out, (flags & WBC_SOLVE_ARMATURE) ? 1 : 0);
+  return c.launched();
 }
 
 // rhs (device f32, right-hand side k of env e at rhs + e * rhs_env_stride + 26 k), out (device f32 [N, nrhs, 26]): include/wbc_sim.h.
 extern "C" int wbc_sim_mass_solve(wbc_sim* s, const float* rhs, int64_t rhs_env_stride, int nrhs, float* out, int flags, void* stream) {
-  StreamDeviceGuard sdg(stream);
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: sim is NULL");
-  if (!rhs || !out) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: rhs / out is NULL");
-  if (nrhs < 1 || nrhs > WBC_SOLVE_MAX_RHS) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: nrhs must be 1..WBC_SOLVE_MAX_RHS");
-  if (rhs_env_stride < (int64_t)BD_NCOL * nrhs) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: rhs_env_stride is below 26 * nrhs");
-  if (flags & ~WBC_SOLVE_ARMATURE) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: unknown flag bits");
-  if (((uintptr_t)rhs | (uintptr_t)out) & 3u) return wbc_sim_internal_fail(-1, "wbc_sim_mass_solve: rhs / out must be 4-byte aligned");
-  return mass_solve_launch(s, "wbc_sim_mass_solve", rhs, rhs_env_stride, nrhs, nullptr, out, flags, stream);
+  WbCall c("wbc_sim_mass_solve", s, stream);
+  if (!s) return c.no_sim();
+  if (!rhs || !out) return c.fail(-1, "rhs / out is NULL");
+  if (nrhs < 1 || nrhs > WBC_SOLVE_MAX_RHS) return c.fail(-1, "nrhs must be 1..WBC_SOLVE_MAX_RHS");
+  if (rhs_env_stride < (int64_t)BD_NCOL * nrhs) return c.fail(-1, "rhs_env_stride is below 26 * nrhs");
+  if (flags & ~WBC_SOLVE_ARMATURE) return c.fail(-1, "unknown flag bits");
+  if (((uintptr_t)rhs | (uintptr_t)out) & 3u) return c.fail(-1, "rhs / out must be 4-byte aligned");
+  return mass_solve_launch(c, rhs, rhs_env_stride, nrhs, nullptr, out, flags, stream);
 }
 
 // nudot = M^-1 (tau - h): wbc_inverse_dynamics_kernel writes h into the sim's [N, 26] scratch, the solve subtracts it as it loads.
 extern "C" int wbc_sim_forward_dynamics(wbc_sim* s, const float* tau, float* nudot, int flags, void* stream) {
-  StreamDeviceGuard sdg(stream);
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics: sim is NULL");
-  if (!nudot) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics: nudot is NULL");
-  if (flags & ~WBC_SOLVE_ARMATURE) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics: unknown flag bits");
-  if (((uintptr_t)tau | (uintptr_t)nudot) & 3u) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics: tau / nudot must be 4-byte aligned");
+  WbCall c("wbc_sim_forward_dynamics", s, stream);
+  if (!s) return c.no_sim();
+  if (!nudot) return c.fail(-1, "nudot is NULL");
+  if (flags & ~WBC_SOLVE_ARMATURE) return c.fail(-1, "unknown flag bits");
+  if (((uintptr_t)tau | (uintptr_t)nudot) & 3u) return c.fail(-1, "tau / nudot must be 4-byte aligned");
   float* h = nullptr;
   if (wbc_sim_internal_fd_scratch(s, &h) != 0) return -1;
   const int rc = wbc_sim_inverse_dynamics(s, nullptr, h, nullptr, stream);
   if (rc != 0) return rc;
-  return mass_solve_launch(s, "wbc_sim_forward_dynamics", tau, BD_NCOL, 1, h, nudot, flags, stream);
+  return mass_solve_launch(c, tau, BD_NCOL, 1, h, nudot, flags, stream);
 }
 
 // ---- rigid-body accelerations and contact-constrained forward dynamics (include/wbc_sim.h) ---------------------------------------------
 // acc = J nudot + Jdot nu for every rigid-body origin, and the solve of
 //     M nudot + h = tau + sum_r J_r^T lambda_r,    J_r nudot + (Jdot nu)_r = a_des_r - damping lambda_r
-// for up to WBC_CONSTR_MAX_BODIES bodies whose origins' linear accelerations are prescribed. Both start from a walk in the shape of phase 1 of
-// wbc_inverse_dynamics_kernel (a copy: that kernel's code generation is left alone): a lane follows IdConst-style path[] from the root
-// DOWN and carries the frame (E, p), the angular velocity w, the angular acceleration a_w and the classical acceleration a_o of the
-// body's origin in F's axes in registers. With x a point of the body relative to that origin, its classical acceleration is
-// R (a_o + a_w x x + w x (w x x)) and the angular one R a_w. The root position is never read.
+// for up to WBC_CONSTR_MAX_BODIES bodies whose origins' linear accelerations are prescribed. Both start from ba_walk: a lane follows
+// TreeWalk::path from the root DOWN, one tree_accel_step (wbc_tree.h) per joint, and carries the frame (E, p), the angular velocity w,
+// the angular acceleration a_w and the classical acceleration a_o of the body's origin in F's axes in registers. With x a point of the
+// body relative to that origin, its classical acceleration is R (a_o + a_w x x + w x (w x x)) and the angular one R a_w. The root
+// position is never read.
 #ifndef BA_EPW
 #define BA_EPW 2                                // envs per workgroup of the three kernels below: 2, or 1 (-DBA_EPW=1, the variant DESIGN.md compares with)
 #endif
@@ -985,12 +964,7 @@ static_assert(BA_EPW == 1 || BA_EPW == 2, "one env per 64 lanes or one per 32-la
 #define CD_GSTRIDE 16                           // floats of gamma per env in the workspace
 #define CD_LD 27                                // LDS row pitch of the 26-column blocks (odd: rows land in different banks)
 static_assert(WBC_NRB <= BA_LPE && WBC_NB + WBC_CONSTR_MAX_BODIES <= BA_LPE && CD_MAXROWS + 1 <= WBC_SOLVE_MAX_RHS && CD_MAXROWS <= CD_GSTRIDE, "lanes");
-struct BaConst {
-  int32_t axis[WBC_NB], dof[WBC_NB];
-  int32_t path[WBC_NB][WBC_MAX_DEPTH];         // as IdConst::path
-  int32_t rb_body[WBC_NRB];
-  float joint_xyz[WBC_NB][3], rb_offset[WBC_NRB][3];
-};
+struct BaConst : TreeWalk, TreeRigid {};
 
 // The walk root -> b. On return (E, p) is body b's frame in F, w and aw its angular velocity and acceleration and ao the CLASSICAL
 // acceleration of its own origin p, all in F's axes. Every body's acceleration is carried at that body's origin, not about F's: the
@@ -999,39 +973,18 @@ struct BaConst {
 // add w x v_O and w x (w x x) of size |w|^2 |x| that cancel down to |w|^2 |x - p| at a far body: 78 x 2^-24 of the magnitude at the
 // arm's links in rollout states.) The root's linear velocity enters no acceleration and is never read; nudot[0:3] is the classical
 // acceleration of the root origin, so a body fixed to a root that does not accelerate gets exactly w x (w x x).
-__device__ __forceinline__ void ba_walk(const BaConst& K, int b, size_t e, const float* R, const float* __restrict__ root,
+__device__ __forceinline__ void ba_walk(const TreeWalk& K, int b, size_t e, const float* R, const float* __restrict__ root,
                                         const float* __restrict__ dofs, const float* __restrict__ nudot, float* E, f3& p, f3& w, f3& aw,
                                         f3& ao) {
   p = mk3(0.f, 0.f, 0.f);
   aw = p; ao = p;
   w = matT_mul(R, ld3(root + e * 26 + 10));
   if (nudot) { ao = matT_mul(R, ld3(nudot + e * BD_NCOL)); aw = matT_mul(R, ld3(nudot + e * BD_NCOL + 3)); }
+#pragma nounroll                                  // kept a loop, as the compiler chose to while the step was written out here
   for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
     const int a = K.path[b][k];
     if (a < 0) break;
-    const int ax = K.axis[a], d = K.dof[a];
-    const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
-    float s, c;
-    sincosf(dofs[e * (2 * WBC_NDOF) + 2 * d], &s, &c);
-    const float t = 1.f - c;
-    const float Q[9] = {c + t * ux * ux, t * ux * uy - s * uz, t * ux * uz + s * uy,
-                        t * uy * ux + s * uz, c + t * uy * uy, t * uy * uz - s * ux,
-                        t * uz * ux - s * uy, t * uz * uy + s * ux, c + t * uz * uz};
-    const f3 r = mat_mul(E, mk3(K.joint_xyz[a][0], K.joint_xyz[a][1], K.joint_xyz[a][2]));    // (E, p) <- (E Rot_a, p + E xyz_a)
-    p = p + r;
-    ao = ao + cross(aw, r) + cross(w, cross(w, r));          // the parent's w and aw carry its origin's acceleration to the joint
-    float En[9];
-#pragma unroll
-    for (int r_ = 0; r_ < 3; ++r_)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) En[r_ * 3 + j] = E[r_ * 3] * Q[j] + E[r_ * 3 + 1] * Q[3 + j] + E[r_ * 3 + 2] * Q[6 + j];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) E[j] = En[j];
-    const f3 Sw = mat_mul(E, mk3(ux, uy, uz));
-    const float qd = dofs[e * (2 * WBC_NDOF) + 2 * d + 1], qdd = nudot ? nudot[e * BD_NCOL + 6 + d] : 0.f;
-    const f3 jw = Sw * qd;                                   // aw += S qdd + w x (S qd), then w += S qd
-    aw = aw + Sw * qdd + cross(w, jw);
-    w = w + jw;
+    tree_accel_step(K, a, e, dofs, nudot, E, p, w, aw, ao, nullptr);
   }
 }
 
@@ -1055,10 +1008,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_body_accel_kernel(BaConst K
   st3(o, lin); st3(o + 3, ang);
 }
 
-struct CdConst {
-  BaConst A;
-  int32_t col_body[WBC_NDOF];
-  uint32_t anc[WBC_NB];                        // as BodyConst::anc
+struct CdConst : TreeWalk, TreeRigid, TreeCols {
   int32_t nb, rb[WBC_CONSTR_MAX_BODIES];       // the listed rigid bodies
 };
 
@@ -1082,16 +1032,15 @@ extern "C" __global__ void __launch_bounds__(64) wbc_constraint_rhs_kernel(CdCon
   quat_to_mat(root + e * 26 + 3, R);
   if (lane < WBC_NB + nb) {
     const bool body = lane < WBC_NB;
-    const int k = body ? 0 : lane - WBC_NB, r = C.rb[k], b = body ? lane : C.A.rb_body[r];
+    const int k = body ? 0 : lane - WBC_NB, r = C.rb[k], b = body ? lane : C.rb_body[r];
     float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
     f3 p, w, aw, ao;
-    ba_walk(C.A, b, e, R, root, dofs, nullptr, E, p, w, aw, ao);
+    ba_walk(C, b, e, R, root, dofs, nullptr, E, p, w, aw, ao);
     if (body) {
-      const int ax = C.A.axis[b];                            // -1 for the root: no joint axis
-      st3(sJ[half][b], mat_mul(E, mk3(ax == 0 ? 1.f : 0.f, ax == 1 ? 1.f : 0.f, ax == 2 ? 1.f : 0.f)));
+      st3(sJ[half][b], mat_mul(E, tree_axis(C.axis[b])));    // -1 for the root: no joint axis
       st3(sJ[half][b] + 3, p);
     } else {
-      const f3 xo = mat_mul(E, mk3(C.A.rb_offset[r][0], C.A.rb_offset[r][1], C.A.rb_offset[r][2]));
+      const f3 xo = mat_mul(E, mk3(C.rb_offset[r][0], C.rb_offset[r][1], C.rb_offset[r][2]));
       st3(sX[half][k], p + xo);
       if (live) st3(gamma + e * CD_GSTRIDE + 3 * k, mat_mul(R, ao + cross(aw, xo) + cross(w, cross(w, xo))));
     }
@@ -1108,7 +1057,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_constraint_rhs_kernel(CdCon
         const f3 ej = mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f);
         if (c < 3) lin = ej;                                 // v_root: identity
         else if (c < 6) lin = cross(ej, mat_mul(R, x));      // omega_root: e_j x (origin relative to the root, world axes)
-        else if (b >= 0 && ((C.anc[C.A.rb_body[C.rb[k]]] >> b) & 1u)) lin = mat_mul(R, cross(ld3(sJ[half][b]), x - ld3(sJ[half][b] + 3)));
+        else if (b >= 0 && ((C.anc[C.rb_body[C.rb[k]]] >> b) & 1u)) lin = mat_mul(R, cross(ld3(sJ[half][b]), x - ld3(sJ[half][b] + 3)));
       }
       o[(3 * k) * BD_NCOL] = lin.x; o[(3 * k + 1) * BD_NCOL] = lin.y; o[(3 * k + 2) * BD_NCOL] = lin.z;
     }
@@ -1202,34 +1151,21 @@ extern "C" __global__ void __launch_bounds__(64) wbc_constraint_solve_kernel(con
   }
 }
 
-static int ba_const_fill(const DevConst* hc, BaConst& A, IdConst& K) {
-  if (id_const_fill(hc, K) != 0) return 1;
-  const wbc_model& m = hc->model;
-  for (int b = 0; b < WBC_NB; ++b) {
-    A.axis[b] = K.axis[b]; A.dof[b] = K.dof[b];
-    for (int k = 0; k < WBC_MAX_DEPTH; ++k) A.path[b][k] = K.path[b][k];
-    for (int j = 0; j < 3; ++j) A.joint_xyz[b][j] = K.joint_xyz[b][j];
-  }
-  for (int r = 0; r < WBC_NRB; ++r) {
-    A.rb_body[r] = m.rb_body[r];                   // id_const_fill (body_const_fill) checked the range
-    for (int j = 0; j < 3; ++j) A.rb_offset[r][j] = m.rb_offset[r][j];
-  }
-  return 0;
-}
+// W and B are the two bases of one argument struct (BaConst, CdConst, TiConst). 0, or 1: a model the kernels refuse.
+static int ba_const_fill(const wbc_model& m, TreeWalk& W, TreeRigid& B) { return tree_walk_fill(m, W) != 0 || tree_rigid_fill(m, B) != 0; }
 
 // nudot (device f32 [N,26] or NULL = zeros), acc (device f32 [N,27,6]): include/wbc_sim.h.
 extern "C" int wbc_sim_body_accelerations(wbc_sim* s, const float* nudot, float* acc, void* stream) {
-  StreamDeviceGuard sdg(stream);
-  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_body_accelerations: sim is NULL");
-  if (!acc) return wbc_sim_internal_fail(-1, "wbc_sim_body_accelerations: acc is NULL");
-  if (((uintptr_t)nudot | (uintptr_t)acc) & 3u) return wbc_sim_internal_fail(-1, "wbc_sim_body_accelerations: nudot / acc must be 4-byte aligned");
-  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_body_accelerations: no sim state");
-  if (n <= 0) return 0;
-  BaConst A; IdConst K;
-  if (ba_const_fill(hc, A, K) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_body_accelerations: the model's tree is not one the kernel walks");
-  hipLaunchKernelGGL(wbc_body_accel_kernel, dim3((n + BA_EPW - 1) / BA_EPW), dim3(64), 0, (hipStream_t)stream, A, root, dofs, nudot, n, acc);
-  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_body_accelerations: launch failed");
+  WbCall c("wbc_sim_body_accelerations", s, stream);
+  if (!s) return c.no_sim();
+  if (!acc) return c.fail(-1, "acc is NULL");
+  if (((uintptr_t)nudot | (uintptr_t)acc) & 3u) return c.fail(-1, "nudot / acc must be 4-byte aligned");
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
+  BaConst A;
+  if (ba_const_fill(c.hc->model, A, A) != 0) return c.no_tree();
+  hipLaunchKernelGGL(wbc_body_accel_kernel, dim3((c.n + BA_EPW - 1) / BA_EPW), dim3(64), 0, (hipStream_t)stream, A, c.root, c.dofs, nudot, c.n, acc);
+  return c.launched();
 }
 
 // Workspace layout (floats): the right-hand-side block [N, 3 nb + 1, 26], the mass solve's output of the same shape, gamma [N, 16].
@@ -1243,29 +1179,28 @@ extern "C" size_t wbc_sim_constrained_dynamics_workspace_floats(int num_envs, in
 extern "C" int wbc_sim_constrained_dynamics(wbc_sim* s, const int32_t* rigid_bodies, int nbodies, const uint8_t* active, const float* tau,
                                             const float* acc_des, float damping, int flags, float* nudot, float* lambda, float* workspace,
                                             void* stream) {
-  StreamDeviceGuard sdg(stream);
-  const char* who = "wbc_sim_constrained_dynamics";
-  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: sim is NULL");
-  if (!rigid_bodies || !nudot || !workspace) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: rigid_bodies / nudot / workspace is NULL");
-  if (nbodies < 1 || nbodies > WBC_CONSTR_MAX_BODIES) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: nbodies must be 1..WBC_CONSTR_MAX_BODIES");
-  if (!(damping >= 0.f) || !(damping <= 3.4e38f)) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: damping must be finite and >= 0");
-  if (flags & ~WBC_SOLVE_ARMATURE) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: unknown flag bits");
+  WbCall c("wbc_sim_constrained_dynamics", s, stream);
+  if (!s) return c.no_sim();
+  if (!rigid_bodies || !nudot || !workspace) return c.fail(-1, "rigid_bodies / nudot / workspace is NULL");
+  if (nbodies < 1 || nbodies > WBC_CONSTR_MAX_BODIES) return c.fail(-1, "nbodies must be 1..WBC_CONSTR_MAX_BODIES");
+  if (!(damping >= 0.f) || !(damping <= 3.4e38f)) return c.fail(-1, "damping must be finite and >= 0");
+  if (flags & ~WBC_SOLVE_ARMATURE) return c.fail(-1, "unknown flag bits");
   if (((uintptr_t)tau | (uintptr_t)acc_des | (uintptr_t)nudot | (uintptr_t)lambda | (uintptr_t)workspace) & 3u)
-    return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: tau / acc_des / nudot / lambda / workspace must be 4-byte aligned");
-  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: no sim state");
+    return c.fail(-1, "tau / acc_des / nudot / lambda / workspace must be 4-byte aligned");
+  if (!c.have) return c.no_state();
   for (int k = 0; k < nbodies; ++k)
-    if (rigid_bodies[k] < 0 || rigid_bodies[k] >= WBC_NRB) return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: rigid-body index outside 0..WBC_NRB-1");
-  CdConst C; IdConst K;
-  if (ba_const_fill(hc, C.A, K) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_constrained_dynamics: the model's tree is not one the kernel walks");
+    if (rigid_bodies[k] < 0 || rigid_bodies[k] >= WBC_NRB) return c.fail(-1, "rigid-body index outside 0..WBC_NRB-1");
+  CdConst C;
+  if (ba_const_fill(c.hc->model, C, C) != 0) return c.no_tree();
   for (int k = 0; k < nbodies; ++k)
     for (int l = 0; l < k; ++l)
-      if (C.A.rb_body[rigid_bodies[k]] == C.A.rb_body[rigid_bodies[l]])
-        return wbc_sim_internal_fail(-1, "wbc_sim_constrained_dynamics: two listed rigid bodies ride on the same moving body (dependent rows)");
+      if (C.rb_body[rigid_bodies[k]] == C.rb_body[rigid_bodies[l]])
+        return c.fail(-1, "two listed rigid bodies ride on the same moving body (dependent rows)");
+  const int n = c.n;
   if (n <= 0) return 0;
+  tree_cols_fill(c.hc->model, C);
   uint32_t live_cols = 63u;
-  for (int d = 0; d < WBC_NDOF; ++d) { C.col_body[d] = K.col_body[d]; if (K.col_body[d] >= 0) live_cols |= 1u << (6 + d); }
-  for (int b = 0; b < WBC_NB; ++b) C.anc[b] = K.anc[b];
+  for (int d = 0; d < WBC_NDOF; ++d) if (C.col_body[d] >= 0) live_cols |= 1u << (6 + d);
   C.nb = nbodies;
   for (int k = 0; k < WBC_CONSTR_MAX_BODIES; ++k) C.rb[k] = rigid_bodies[k < nbodies ? k : 0];
   float* h = nullptr;
@@ -1275,13 +1210,13 @@ extern "C" int wbc_sim_constrained_dynamics(wbc_sim* s, const int32_t* rigid_bod
   int rc = wbc_sim_inverse_dynamics(s, nullptr, h, nullptr, stream);
   if (rc != 0) return rc;
   const dim3 grid((n + BA_EPW - 1) / BA_EPW);
-  hipLaunchKernelGGL(wbc_constraint_rhs_kernel, grid, dim3(64), 0, (hipStream_t)stream, C, root, dofs, active, tau, (const float*)h, n, blk, gamma);
-  if (hipGetLastError() != hipSuccess) return wbc_sim_internal_fail(-2, "wbc_sim_constrained_dynamics: launch failed");
-  rc = mass_solve_launch(s, who, blk, (int64_t)nrow * BD_NCOL, nrow, nullptr, Y, flags, stream);
+  hipLaunchKernelGGL(wbc_constraint_rhs_kernel, grid, dim3(64), 0, (hipStream_t)stream, C, c.root, c.dofs, active, tau, (const float*)h, n, blk, gamma);
+  if ((rc = c.launched()) != 0) return rc;
+  rc = mass_solve_launch(c, blk, (int64_t)nrow * BD_NCOL, nrow, nullptr, Y, flags, stream);
   if (rc != 0) return rc;
   hipLaunchKernelGGL(wbc_constraint_solve_kernel, grid, dim3(64), 0, (hipStream_t)stream, (const float*)blk, (const float*)Y, (const float*)gamma, active,
                      acc_des, damping, nbodies, live_cols, n, nudot, lambda);
-  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_constrained_dynamics: launch failed");
+  return c.launched();
 }
 
 // ---- centre of mass, centroidal momentum and its matrix (include/wbc_sim.h: wbc_sim_centroidal) ----------------------------------------
@@ -1289,8 +1224,9 @@ extern "C" int wbc_sim_constrained_dynamics(wbc_sim* s, const int32_t* rigid_bod
 //     h_G = (m v_com ; sum I_b w_b + m_b d_b x v_cb),   hdot_G = (m a_com ; sum I_b al_b + w_b x I_b w_b + m_b d_b x a_cb),
 //     I_G = sum I_b + m_b (|d_b|^2 1 - d_b d_b^T).
 // sum m_b d_b x X vanishes for any X common to all bodies, so the walk carries each body's velocity and classical acceleration RELATIVE
-// to the root origin's linear motion (v_root and nudot[0:3] never enter it) at the body's own origin, as ba_walk does; no angular row
-// then holds a term that grows with |v_root| or |nudot[0:3]|, and the linear rows add m v_root and m nudot[0:3] at the end.
+// to the root origin's linear motion (v_root and nudot[0:3] never enter it) at the body's own origin: ba_walk's step (tree_accel_step)
+// with the origin's velocity carried too. No angular row then holds a term that grows with |v_root| or |nudot[0:3]|, and the linear rows
+// add m v_root and m nudot[0:3] at the end.
 // CM_EPW envs per 64-lane workgroup, one per lane group, three LDS hand-overs:
 //  1) lane b = moving body b walks root -> b in registers and leaves (m, c_b - its origin, its origin, its joint axis, I_b about c_b)
 //     in LDS;
@@ -1313,7 +1249,7 @@ static_assert(CM_EPW == 1 || CM_EPW == 2, "one env per 64 lanes or one per 32-la
 #define CM_INR 7
 static_assert(WBC_NB <= 64 / CM_EPW && BD_NCOL <= 64 / CM_EPW && CM_NS + 4 <= 64 / CM_EPW, "lanes");
 
-extern "C" __global__ void __launch_bounds__(64) wbc_centroidal_kernel(IdConst K, const float* __restrict__ root, const float* __restrict__ dofs,
+extern "C" __global__ void __launch_bounds__(64) wbc_centroidal_kernel(TreeConst K, const float* __restrict__ root, const float* __restrict__ dofs,
                                                                       const float* __restrict__ body_params,
                                                                       const float* __restrict__ nudot, int n, float* __restrict__ com,
                                                                       float* __restrict__ mom, float* __restrict__ cmm,
@@ -1335,55 +1271,27 @@ extern "C" __global__ void __launch_bounds__(64) wbc_centroidal_kernel(IdConst K
     f3 p = mk3(0.f, 0.f, 0.f), Sw = p, vo = p, ao = p, aw = p;
     f3 w = ld3(root + e * 26 + 10);
     if (nudot) aw = ld3(nudot + e * BD_NCOL + 3);
+#pragma unroll                                     // fully unrolled, as the compiler chose to while the step was written out here
     for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
       const int a = K.path[b][k];
       if (a < 0) break;
-      const int ax = K.axis[a], d = K.dof[a];
-      const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
-      float s, c;
-      sincosf(dofs[e * (2 * WBC_NDOF) + 2 * d], &s, &c);
-      const float t = 1.f - c;
-      const float Q[9] = {c + t * ux * ux, t * ux * uy - s * uz, t * ux * uz + s * uy,
-                          t * uy * ux + s * uz, c + t * uy * uy, t * uy * uz - s * ux,
-                          t * uz * ux - s * uy, t * uz * uy + s * ux, c + t * uz * uz};
-      const f3 r = mat_mul(E, mk3(K.joint_xyz[a][0], K.joint_xyz[a][1], K.joint_xyz[a][2]));    // (E, p) <- (E Rot_a, p + E xyz_a)
-      p = p + r;
-      vo = vo + cross(w, r);                                   // the parent's w and aw carry its origin's motion to the joint
-      ao = ao + cross(aw, r) + cross(w, cross(w, r));
-      float En[9];
-#pragma unroll
-      for (int r_ = 0; r_ < 3; ++r_)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) En[r_ * 3 + j] = E[r_ * 3] * Q[j] + E[r_ * 3 + 1] * Q[3 + j] + E[r_ * 3 + 2] * Q[6 + j];
-#pragma unroll
-      for (int j = 0; j < 9; ++j) E[j] = En[j];
-      Sw = mat_mul(E, mk3(ux, uy, uz));
-      const float qd = dofs[e * (2 * WBC_NDOF) + 2 * d + 1], qdd = nudot ? nudot[e * BD_NCOL + 6 + d] : 0.f;
-      const f3 jw = Sw * qd;                                   // aw += S qdd + w x (S qd), then w += S qd
-      aw = aw + Sw * qdd + cross(w, jw);
-      w = w + jw;
+      Sw = tree_accel_step(K, a, e, dofs, nudot, E, p, w, aw, ao, &vo);
     }
-    // the per-env root composite and gripper body (body_params), the model's otherwise
     float m = K.mass[b], cm[3] = {K.com[b][0], K.com[b][1], K.com[b][2]}, I6[6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) I6[j] = K.inertia[b][j];
-    const int slot = b == 0 ? 0 : (b == K.gripper_body ? 10 : -1);
+    const int slot = b == 0 ? TREE_BP_ROOT : (b == K.gripper_body ? TREE_BP_GRIPPER : -1);
     if (slot >= 0) {
-      const float* bp = body_params + e * 20 + slot;
+      const float* bp = body_params + e * TREE_BP_STRIDE + slot;
       m = bp[0];
 #pragma unroll
       for (int j = 0; j < 3; ++j) cm[j] = bp[1 + j];
 #pragma unroll
       for (int j = 0; j < 6; ++j) I6[j] = bp[4 + j];
     }
-    const float Ib[9] = {I6[0], I6[3], I6[4], I6[3], I6[1], I6[5], I6[4], I6[5], I6[2]};
-    float EI[9];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) EI[r * 3 + k] = E[r * 3] * Ib[k] + E[r * 3 + 1] * Ib[3 + k] + E[r * 3 + 2] * Ib[6 + k];
-    auto ibar = [&](int r, int k) { return EI[r * 3] * E[k * 3] + EI[r * 3 + 1] * E[k * 3 + 1] + EI[r * 3 + 2] * E[k * 3 + 2]; };
-    const float Iw[9] = {ibar(0, 0), ibar(0, 1), ibar(0, 2), ibar(0, 1), ibar(1, 1), ibar(1, 2), ibar(0, 2), ibar(1, 2), ibar(2, 2)};
+    float Iw6[6];
+    tree_rotate_inertia(E, I6, Iw6);
+    const float Iw[9] = {Iw6[0], Iw6[3], Iw6[4], Iw6[3], Iw6[1], Iw6[5], Iw6[4], Iw6[5], Iw6[2]};
     const f3 rc = mat_mul(E, mk3(cm[0], cm[1], cm[2]));
     vc = vo + cross(w, rc);
     ac = ao + cross(aw, rc) + cross(w, cross(w, rc));
@@ -1391,7 +1299,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_centroidal_kernel(IdConst K
     Nw = mat_mul(Iw, aw) + cross(w, Lw);
     float* o = B[b];
     o[0] = m; st3(o + 1, rc); st3(o + 4, p); st3(o + 7, Sw);
-    o[10] = Iw[0]; o[11] = Iw[4]; o[12] = Iw[8]; o[13] = Iw[1]; o[14] = Iw[2]; o[15] = Iw[5];
+    o[10] = Iw6[0]; o[11] = Iw6[1]; o[12] = Iw6[2]; o[13] = Iw6[3]; o[14] = Iw6[4]; o[15] = Iw6[5];
   }
   __syncthreads();
 
@@ -1477,19 +1385,18 @@ extern "C" __global__ void __launch_bounds__(64) wbc_centroidal_kernel(IdConst K
 // nudot (device f32 [N,26] or NULL = zeros); com [N,9], mom [N,12], cmm [N,6,26], inertia [N,7] (device f32, caller-owned, any may be NULL,
 // not all): include/wbc_sim.h.
 extern "C" int wbc_sim_centroidal(wbc_sim* s, const float* nudot, float* com, float* mom, float* cmm, float* inertia, void* stream) {
-  StreamDeviceGuard sdg(stream);
-  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_centroidal: sim is NULL");
-  if (!com && !mom && !cmm && !inertia) return wbc_sim_internal_fail(-1, "wbc_sim_centroidal: com, mom, cmm and inertia are all NULL");
+  WbCall c("wbc_sim_centroidal", s, stream);
+  if (!s) return c.no_sim();
+  if (!com && !mom && !cmm && !inertia) return c.fail(-1, "com, mom, cmm and inertia are all NULL");
   if (((uintptr_t)nudot | (uintptr_t)com | (uintptr_t)mom | (uintptr_t)cmm | (uintptr_t)inertia) & 3u)
-    return wbc_sim_internal_fail(-1, "wbc_sim_centroidal: nudot / com / mom / cmm / inertia must be 4-byte aligned");
-  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_centroidal: no sim state");
-  if (n <= 0) return 0;
-  IdConst K;
-  if (id_const_fill(hc, K) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_centroidal: the model's tree is not one the kernel walks");
-  hipLaunchKernelGGL(wbc_centroidal_kernel, dim3((n + CM_EPW - 1) / CM_EPW), dim3(64), 0, (hipStream_t)stream, K, root, dofs, bp, nudot, n, com, mom,
-                     cmm, inertia);
-  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_centroidal: launch failed");
+    return c.fail(-1, "nudot / com / mom / cmm / inertia must be 4-byte aligned");
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
+  TreeConst K;
+  if (tree_const_fill(c.hc->model, K) != 0) return c.no_tree();
+  hipLaunchKernelGGL(wbc_centroidal_kernel, dim3((c.n + CM_EPW - 1) / CM_EPW), dim3(64), 0, (hipStream_t)stream, K, c.root, c.dofs, c.bp, nudot, c.n,
+                     com, mom, cmm, inertia);
+  return c.launched();
 }
 
 // ---- analytic derivatives of inverse and forward dynamics (include/wbc_sim.h: wbc_sim_inverse_dynamics_derivatives) ----------------------
@@ -1556,43 +1463,31 @@ extern "C" __global__ void __launch_bounds__(64) wbc_dynamics_derivatives_kernel
       const f3 phi = matT_mul(R, mk3(u == 0 ? 1.f : 0.f, u == 1 ? 1.f : 0.f, u == 2 ? 1.f : 0.f));
       const float rot = t < 3 ? 1.f : 0.f, omg = t >= 3 && t < 6 ? 1.f : 0.f;
       const d3 g = mkd3(gF, cross(gF, phi) * rot);
-      // angular velocity, angular acceleration and the CLASSICAL acceleration of the body's own origin, in F's axes (the shape of ba_walk):
+      // angular velocity, angular acceleration and the CLASSICAL acceleration of the body's own origin, in F's axes (tree_accel_step, paired with its tangent):
       // every later lever is then a link offset or a centre-of-mass offset, never the distance to the base origin
       d3 vw = mkd3(w0, cross(w0, phi) * rot + phi * omg);
       d3 aw = mkd3(al0, cross(al0, phi) * rot), ao = mkd3(a0, cross(a0, phi) * rot);
       float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, dE[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       d3 p = mkd3(zero, zero), Sw = p;
+#pragma nounroll                                  // kept a loop, as the compiler chose to while the step was written out here
       for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
         const int a = K.path[b][k];
         if (a < 0) break;
-        const int ax = K.axis[a], d = K.dof[a];
-        const float ux = ax == 0 ? 1.f : 0.f, uy = ax == 1 ? 1.f : 0.f, uz = ax == 2 ? 1.f : 0.f;
+        const int d = K.dof[a];
         const float dq = t == 6 + k ? 1.f : 0.f;
-        float s, c;
-        sincosf(dofs[e * (2 * WBC_NDOF) + 2 * d], &s, &c);
-        const float tc = 1.f - c, ds = c * dq, dc = -s * dq, dt = s * dq;
-        const float Q[9] = {c + tc * ux * ux, tc * ux * uy - s * uz, tc * ux * uz + s * uy,
-                            tc * uy * ux + s * uz, c + tc * uy * uy, tc * uy * uz - s * ux,
-                            tc * uz * ux - s * uy, tc * uz * uy + s * ux, c + tc * uz * uz};
-        const float dQ[9] = {dc + dt * ux * ux, dt * ux * uy - ds * uz, dt * ux * uz + ds * uy,
-                             dt * uy * ux + ds * uz, dc + dt * uy * uy, dt * uy * uz - ds * ux,
-                             dt * uz * ux - ds * uy, dt * uz * uy + ds * ux, dc + dt * uz * uz};
+        float s, c, Q[9], dQ[9];
+        const f3 uu = tree_joint_rot(K.axis[a], dofs[e * (2 * WBC_NDOF) + 2 * d], Q, s, c);
+        tree_rodrigues(uu, c * dq, -s * dq, s * dq, dQ);          // d(sin, cos, 1 - cos) along the lane's direction
         const f3 xyz = mk3(K.joint_xyz[a][0], K.joint_xyz[a][1], K.joint_xyz[a][2]);
         const d3 r = mkd3(mat_mul(E, xyz), mat_mul(dE, xyz));   // a_o <- a_o + alpha x r + w x (w x r) with the parent's alpha, w; (E, p) <- (E Rot_a, p + E xyz_a)
         ao = ao + cross(aw, r) + cross(vw, cross(vw, r));
         p = p + r;
-        float En[9], dEn[9];
+        float En[9], dEQ[9], EdQ[9];                           // (E, dE) <- (E Q, dE Q + E dQ)
+        tree_frame_mul(E, Q, En);
+        tree_frame_mul(dE, Q, dEQ);
+        tree_frame_mul(E, dQ, EdQ);
 #pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {
-            En[r * 3 + j] = E[r * 3] * Q[j] + E[r * 3 + 1] * Q[3 + j] + E[r * 3 + 2] * Q[6 + j];
-            dEn[r * 3 + j] = (dE[r * 3] * Q[j] + dE[r * 3 + 1] * Q[3 + j] + dE[r * 3 + 2] * Q[6 + j]) +
-                             (E[r * 3] * dQ[j] + E[r * 3 + 1] * dQ[3 + j] + E[r * 3 + 2] * dQ[6 + j]);
-          }
-#pragma unroll
-        for (int j = 0; j < 9; ++j) { E[j] = En[j]; dE[j] = dEn[j]; }
-        const f3 uu = mk3(ux, uy, uz);
+        for (int j = 0; j < 9; ++j) { E[j] = En[j]; dE[j] = dEQ[j] + EdQ[j]; }
         Sw = mkd3(mat_mul(E, uu), mat_mul(dE, uu));
         du qd;
         qd.v = dofs[e * (2 * WBC_NDOF) + 2 * d + 1];
@@ -1605,9 +1500,9 @@ extern "C" __global__ void __launch_bounds__(64) wbc_dynamics_derivatives_kernel
       float m = K.mass[b], com[3] = {K.com[b][0], K.com[b][1], K.com[b][2]}, I6[6];
 #pragma unroll
       for (int j = 0; j < 6; ++j) I6[j] = K.inertia[b][j];
-      const int slot = b == 0 ? 0 : (b == K.gripper_body ? 10 : -1);
+      const int slot = b == 0 ? TREE_BP_ROOT : (b == K.gripper_body ? TREE_BP_GRIPPER : -1);
       if (slot >= 0) {
-        const float* bp = body_params + e * 20 + slot;
+        const float* bp = body_params + e * TREE_BP_STRIDE + slot;
         m = bp[0];
 #pragma unroll
         for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
@@ -1616,7 +1511,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_dynamics_derivatives_kernel
       }
       // as wbc_inverse_dynamics_kernel: the body's own joint sees the body's own force and weight through the lever in BODY axes
       const int axb = K.axis[b];
-      const f3 cm = mk3(com[0], com[1], com[2]), ub = mk3(axb == 0 ? 1.f : 0.f, axb == 1 ? 1.f : 0.f, axb == 2 ? 1.f : 0.f);
+      const f3 cm = mk3(com[0], com[1], com[2]), ub = tree_axis(axb);
       const f3 lev = cross(cm, ub);
       const d3 cmd = mkd3(cm, zero), ubd = mkd3(ub, zero), levd = mkd3(lev, zero);
       const d3 rc = mat_mul(E, dE, cmd), Cc = p + rc;
@@ -1736,30 +1631,24 @@ static int dd_const_fill(const DevConst* hc, DdConst& C) {
   return 0;
 }
 
-static int derivatives_launch(wbc_sim* s, const char* who, const float* nudot, float* dq, float* dnu, float* eye, int transposed, int negate,
-                              void* stream) {
-  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
-  char msg[160];
-  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) { snprintf(msg, sizeof msg, "%s: no sim state", who); return wbc_sim_internal_fail(-1, msg); }
-  if (n <= 0) return 0;
+static int derivatives_launch(const WbCall& c, const float* nudot, float* dq, float* dnu, float* eye, int transposed, int negate, void* stream) {
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
   DdConst C;
-  if (dd_const_fill(hc, C) != 0) { snprintf(msg, sizeof msg, "%s: the model's tree is not one the kernel walks", who); return wbc_sim_internal_fail(-3, msg); }
-  hipLaunchKernelGGL(wbc_dynamics_derivatives_kernel, dim3(dq || dnu ? n : 1), dim3(64), 0, (hipStream_t)stream, C, root, dofs, bp, nudot, n, dq, dnu,
-                     eye, transposed, negate);
-  if (hipGetLastError() == hipSuccess) return 0;
-  snprintf(msg, sizeof msg, "%s: launch failed", who);
-  return wbc_sim_internal_fail(-2, msg);
+  if (dd_const_fill(c.hc, C) != 0) return c.no_tree();
+  hipLaunchKernelGGL(wbc_dynamics_derivatives_kernel, dim3(dq || dnu ? c.n : 1), dim3(64), 0, (hipStream_t)stream, C, c.root, c.dofs, c.bp, nudot, c.n,
+                     dq, dnu, eye, transposed, negate);
+  return c.launched();
 }
 
 // nudot (device f32 [N,26] or NULL = zeros); dtau_dq / dtau_dnu (device f32 [N,26,26], caller-owned, either may be NULL): include/wbc_sim.h.
 extern "C" int wbc_sim_inverse_dynamics_derivatives(wbc_sim* s, const float* nudot, float* dtau_dq, float* dtau_dnu, int flags, void* stream) {
-  StreamDeviceGuard sdg(stream);
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics_derivatives: sim is NULL");
-  if (!dtau_dq && !dtau_dnu) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics_derivatives: dtau_dq and dtau_dnu are both NULL");
-  if (flags & ~WBC_DERIV_TRANSPOSED) return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics_derivatives: unknown flag bits");
-  if (((uintptr_t)nudot | (uintptr_t)dtau_dq | (uintptr_t)dtau_dnu) & 3u)
-    return wbc_sim_internal_fail(-1, "wbc_sim_inverse_dynamics_derivatives: nudot / dtau_dq / dtau_dnu must be 4-byte aligned");
-  return derivatives_launch(s, "wbc_sim_inverse_dynamics_derivatives", nudot, dtau_dq, dtau_dnu, nullptr, (flags & WBC_DERIV_TRANSPOSED) ? 1 : 0, 0, stream);
+  WbCall c("wbc_sim_inverse_dynamics_derivatives", s, stream);
+  if (!s) return c.no_sim();
+  if (!dtau_dq && !dtau_dnu) return c.fail(-1, "dtau_dq and dtau_dnu are both NULL");
+  if (flags & ~WBC_DERIV_TRANSPOSED) return c.fail(-1, "unknown flag bits");
+  if (((uintptr_t)nudot | (uintptr_t)dtau_dq | (uintptr_t)dtau_dnu) & 3u) return c.fail(-1, "nudot / dtau_dq / dtau_dnu must be 4-byte aligned");
+  return derivatives_launch(c, nudot, dtau_dq, dtau_dnu, nullptr, (flags & WBC_DERIV_TRANSPOSED) ? 1 : 0, 0, stream);
 }
 
 // Workspace: -dtau/dq^T and -dtau/dnu^T (the solves' right-hand sides), three solve results awaiting their transpose, one 26 x 26 identity.
@@ -1770,16 +1659,15 @@ extern "C" size_t wbc_sim_forward_dynamics_derivatives_workspace_floats(int num_
 // tau (device f32 [N,26] or NULL), nudot [N,26], dnudot_dq / dnudot_dnu / minv [N,26,26] (any may be NULL, not all): include/wbc_sim.h.
 extern "C" int wbc_sim_forward_dynamics_derivatives(wbc_sim* s, const float* tau, float* nudot, float* dnudot_dq, float* dnudot_dnu, float* minv,
                                                     int flags, float* workspace, void* stream) {
-  StreamDeviceGuard sdg(stream);
-  const char* who = "wbc_sim_forward_dynamics_derivatives";
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: sim is NULL");
-  if (!nudot || !workspace) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: nudot / workspace is NULL");
-  if (!dnudot_dq && !dnudot_dnu && !minv) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: dnudot_dq, dnudot_dnu and minv are all NULL");
-  if (flags & ~(WBC_SOLVE_ARMATURE | WBC_DERIV_TRANSPOSED)) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: unknown flag bits");
+  WbCall c("wbc_sim_forward_dynamics_derivatives", s, stream);
+  if (!s) return c.no_sim();
+  if (!nudot || !workspace) return c.fail(-1, "nudot / workspace is NULL");
+  if (!dnudot_dq && !dnudot_dnu && !minv) return c.fail(-1, "dnudot_dq, dnudot_dnu and minv are all NULL");
+  if (flags & ~(WBC_SOLVE_ARMATURE | WBC_DERIV_TRANSPOSED)) return c.fail(-1, "unknown flag bits");
   if (((uintptr_t)tau | (uintptr_t)nudot | (uintptr_t)dnudot_dq | (uintptr_t)dnudot_dnu | (uintptr_t)minv | (uintptr_t)workspace) & 3u)
-    return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: tau / nudot / dnudot_dq / dnudot_dnu / minv / workspace must be 4-byte aligned");
-  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
-  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_forward_dynamics_derivatives: no sim state");
+    return c.fail(-1, "tau / nudot / dnudot_dq / dnudot_dnu / minv / workspace must be 4-byte aligned");
+  if (!c.have) return c.no_state();
+  const int n = c.n;
   if (n <= 0) return 0;
   const int solve_flags = flags & WBC_SOLVE_ARMATURE;
   const bool tr = flags & WBC_DERIV_TRANSPOSED;
@@ -1789,18 +1677,18 @@ extern "C" int wbc_sim_forward_dynamics_derivatives(wbc_sim* s, const float* tau
   float* rq = dnudot_dq ? workspace : nullptr;
   float* rn = dnudot_dnu ? workspace + blk : nullptr;
   float* eye = minv ? workspace + 5 * blk : nullptr;
-  rc = derivatives_launch(s, who, nudot, rq, rn, eye, 1, 1, stream);
+  rc = derivatives_launch(c, nudot, rq, rn, eye, 1, 1, stream);
   if (rc != 0) return rc;
   // one direction's 26 values are one right-hand side: the solves write the transposed layout, straight into the caller's tensors if asked
   float* xq = tr ? dnudot_dq : workspace + 2 * blk;
   float* xn = tr ? dnudot_dnu : workspace + 3 * blk;
   float* xm = tr ? minv : workspace + 4 * blk;
-  if (dnudot_dq && (rc = mass_solve_launch(s, who, rq, DD_MENV, BD_NCOL, nullptr, xq, solve_flags, stream)) != 0) return rc;
-  if (dnudot_dnu && (rc = mass_solve_launch(s, who, rn, DD_MENV, BD_NCOL, nullptr, xn, solve_flags, stream)) != 0) return rc;
-  if (minv && (rc = mass_solve_launch(s, who, eye, 0, BD_NCOL, nullptr, xm, solve_flags, stream)) != 0) return rc;
+  if (dnudot_dq && (rc = mass_solve_launch(c, rq, DD_MENV, BD_NCOL, nullptr, xq, solve_flags, stream)) != 0) return rc;
+  if (dnudot_dnu && (rc = mass_solve_launch(c, rn, DD_MENV, BD_NCOL, nullptr, xn, solve_flags, stream)) != 0) return rc;
+  if (minv && (rc = mass_solve_launch(c, eye, 0, BD_NCOL, nullptr, xm, solve_flags, stream)) != 0) return rc;
   if (!tr) {
     hipLaunchKernelGGL(wbc_derivatives_transpose_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, xq, dnudot_dq, xn, dnudot_dnu, xm, minv);
-    if (hipGetLastError() != hipSuccess) return wbc_sim_internal_fail(-2, "wbc_sim_forward_dynamics_derivatives: launch failed");
+    return c.launched();
   }
   return 0;
 }
@@ -1827,10 +1715,7 @@ extern "C" int wbc_sim_forward_dynamics_derivatives(wbc_sim* s, const float* tau
 #define TI_QG 3                                  // row groups of the reflections: lane = group * TI_NC + column
 static_assert(TI_MAXRHS <= WBC_SOLVE_MAX_RHS && WBC_NB + WBC_TASKID_MAX_STANCE + WBC_TASKID_MAX_TASKS <= BA_LPE && TI_MAXS <= CD_GSTRIDE &&
               TI_QG * TI_NC <= 64 && WBC_TASKID_MAX_STANCE <= WBC_CONSTR_MAX_BODIES, "lanes");
-struct TiConst {
-  BaConst A;
-  int32_t col_body[WBC_NDOF];
-  uint32_t anc[WBC_NB];                        // as BodyConst::anc
+struct TiConst : TreeWalk, TreeRigid, TreeCols {
   int32_t ns, nt, srb[WBC_TASKID_MAX_STANCE], trb[WBC_TASKID_MAX_TASKS];   // the listed stance and task rigid bodies
   int32_t jcol[TI_NJ];                         // column (of 26) of joint torque j
 };
@@ -1854,16 +1739,15 @@ extern "C" __global__ void __launch_bounds__(64) wbc_taskid_rhs_kernel(TiConst C
   if (lane < WBC_NB + ns + nt) {
     const bool body = lane < WBC_NB;
     const int k = body ? 0 : lane - WBC_NB;
-    const int r = body ? 0 : (k < ns ? C.srb[k] : C.trb[k - ns]), b = body ? lane : C.A.rb_body[r];
+    const int r = body ? 0 : (k < ns ? C.srb[k] : C.trb[k - ns]), b = body ? lane : C.rb_body[r];
     float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
     f3 p, w, aw, ao;
-    ba_walk(C.A, b, e, R, root, dofs, nullptr, E, p, w, aw, ao);
+    ba_walk(C, b, e, R, root, dofs, nullptr, E, p, w, aw, ao);
     if (body) {
-      const int ax = C.A.axis[b];                            // -1 for the root: no joint axis
-      st3(sJ[half][b], mat_mul(E, mk3(ax == 0 ? 1.f : 0.f, ax == 1 ? 1.f : 0.f, ax == 2 ? 1.f : 0.f)));
+      st3(sJ[half][b], mat_mul(E, tree_axis(C.axis[b])));    // -1 for the root: no joint axis
       st3(sJ[half][b] + 3, p);
     } else {
-      const f3 xo = mat_mul(E, mk3(C.A.rb_offset[r][0], C.A.rb_offset[r][1], C.A.rb_offset[r][2]));
+      const f3 xo = mat_mul(E, mk3(C.rb_offset[r][0], C.rb_offset[r][1], C.rb_offset[r][2]));
       st3(sX[half][k], p + xo);
       const f3 lin = mat_mul(R, ao + cross(aw, xo) + cross(w, cross(w, xo)));
       if (live) {
@@ -1884,7 +1768,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_taskid_rhs_kernel(TiConst C
       if (act) {
         if (c < 3) lin = ej;                                 // v_root: identity
         else if (c < 6) lin = cross(ej, mat_mul(R, x));      // omega_root: e_j x (origin relative to the root, world axes)
-        else if (b >= 0 && ((C.anc[C.A.rb_body[C.srb[k]]] >> b) & 1u)) lin = mat_mul(R, cross(ld3(sJ[half][b]), x - ld3(sJ[half][b] + 3)));
+        else if (b >= 0 && ((C.anc[C.rb_body[C.srb[k]]] >> b) & 1u)) lin = mat_mul(R, cross(ld3(sJ[half][b]), x - ld3(sJ[half][b] + 3)));
       }
       o[(3 * k) * BD_NCOL] = lin.x; o[(3 * k + 1) * BD_NCOL] = lin.y; o[(3 * k + 2) * BD_NCOL] = lin.z;
     }
@@ -1896,7 +1780,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_taskid_rhs_kernel(TiConst C
       f3 lin = mk3(0.f, 0.f, 0.f), ang = lin;
       if (c < 3) lin = ej;
       else if (c < 6) { lin = cross(ej, mat_mul(R, x)); ang = ej; }
-      else if (b >= 0 && ((C.anc[C.A.rb_body[C.trb[k]]] >> b) & 1u)) {
+      else if (b >= 0 && ((C.anc[C.rb_body[C.trb[k]]] >> b) & 1u)) {
         const f3 a = ld3(sJ[half][b]);
         lin = mat_mul(R, cross(a, x - ld3(sJ[half][b] + 3)));
         ang = mat_mul(R, a);
@@ -2127,52 +2011,49 @@ extern "C" int wbc_sim_task_inverse_dynamics(wbc_sim* s, const int32_t* stance_b
                                              const int32_t* task_bodies, int ntasks, const float* task_acc, const float* task_weight,
                                              const float* nudot_ref, const wbc_taskid_weights* weights, int flags, float* tau, float* nudot,
                                              float* lambda, float* workspace, void* stream) {
-  StreamDeviceGuard sdg(stream);
-  const char* who = "wbc_sim_task_inverse_dynamics";
-  const DevConst* hc; const float *root, *dofs, *bp, *mp; int n;
-  if (!s) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: sim is NULL");
-  if (!tau || !workspace || !weights) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: tau / workspace / weights is NULL");
-  if (nstance < 0 || nstance > WBC_TASKID_MAX_STANCE) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: nstance must be 0..WBC_TASKID_MAX_STANCE");
-  if (ntasks < 0 || ntasks > WBC_TASKID_MAX_TASKS) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: ntasks must be 0..WBC_TASKID_MAX_TASKS");
+  WbCall c("wbc_sim_task_inverse_dynamics", s, stream);
+  if (!s) return c.no_sim();
+  if (!tau || !workspace || !weights) return c.fail(-1, "tau / workspace / weights is NULL");
+  if (nstance < 0 || nstance > WBC_TASKID_MAX_STANCE) return c.fail(-1, "nstance must be 0..WBC_TASKID_MAX_STANCE");
+  if (ntasks < 0 || ntasks > WBC_TASKID_MAX_TASKS) return c.fail(-1, "ntasks must be 0..WBC_TASKID_MAX_TASKS");
   if ((nstance > 0 && !stance_bodies) || (ntasks > 0 && (!task_bodies || !task_acc)))
-    return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: stance_bodies / task_bodies / task_acc is NULL with a count above 0");
+    return c.fail(-1, "stance_bodies / task_bodies / task_acc is NULL with a count above 0");
   auto fin_ge0 = [](float x) { return x >= 0.f && x <= 3.402823466e38f; };   // finite: up to FLT_MAX
-  if (!(weights->torque > 0.f) || !fin_ge0(weights->torque)) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: weights.torque must be finite and > 0");
+  if (!(weights->torque > 0.f) || !fin_ge0(weights->torque)) return c.fail(-1, "weights.torque must be finite and > 0");
   if (!fin_ge0(weights->posture) || !fin_ge0(weights->force) || !fin_ge0(weights->damping))
-    return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: weights.posture / force / damping must be finite and >= 0");
-  if (flags & ~WBC_SOLVE_ARMATURE) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: unknown flag bits");
+    return c.fail(-1, "weights.posture / force / damping must be finite and >= 0");
+  if (flags & ~WBC_SOLVE_ARMATURE) return c.fail(-1, "unknown flag bits");
   if (((uintptr_t)stance_acc | (uintptr_t)task_acc | (uintptr_t)task_weight | (uintptr_t)nudot_ref | (uintptr_t)tau | (uintptr_t)nudot | (uintptr_t)lambda |
        (uintptr_t)workspace) & 3u)
-    return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: stance_acc / task_acc / task_weight / nudot_ref / tau / nudot / lambda / workspace must be 4-byte aligned");
-  if (wbc_sim_internal_arm_inputs(s, &hc, &root, &dofs, &bp, &mp, &n) != 0) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: no sim state");
+    return c.fail(-1, "stance_acc / task_acc / task_weight / nudot_ref / tau / nudot / lambda / workspace must be 4-byte aligned");
+  if (!c.have) return c.no_state();
   for (int k = 0; k < nstance; ++k)
-    if (stance_bodies[k] < 0 || stance_bodies[k] >= WBC_NRB) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: rigid-body index outside 0..WBC_NRB-1");
+    if (stance_bodies[k] < 0 || stance_bodies[k] >= WBC_NRB) return c.fail(-1, "rigid-body index outside 0..WBC_NRB-1");
   for (int k = 0; k < ntasks; ++k)
-    if (task_bodies[k] < 0 || task_bodies[k] >= WBC_NRB) return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: rigid-body index outside 0..WBC_NRB-1");
-  TiConst C; IdConst K;
-  if (ba_const_fill(hc, C.A, K) != 0) return wbc_sim_internal_fail(-3, "wbc_sim_task_inverse_dynamics: the model's tree is not one the kernel walks");
+    if (task_bodies[k] < 0 || task_bodies[k] >= WBC_NRB) return c.fail(-1, "rigid-body index outside 0..WBC_NRB-1");
+  TiConst C;
+  if (ba_const_fill(c.hc->model, C, C) != 0) return c.no_tree();
   for (int k = 0; k < nstance; ++k)
     for (int l = 0; l < k; ++l)
-      if (C.A.rb_body[stance_bodies[k]] == C.A.rb_body[stance_bodies[l]])
-        return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: two stance bodies ride on the same moving body (dependent rows)");
+      if (C.rb_body[stance_bodies[k]] == C.rb_body[stance_bodies[l]])
+        return c.fail(-1, "two stance bodies ride on the same moving body (dependent rows)");
   for (int k = 0; k < ntasks; ++k)
     for (int l = 0; l < k; ++l)
-      if (C.A.rb_body[task_bodies[k]] == C.A.rb_body[task_bodies[l]])
-        return wbc_sim_internal_fail(-1, "wbc_sim_task_inverse_dynamics: two task bodies ride on the same moving body (dependent rows)");
+      if (C.rb_body[task_bodies[k]] == C.rb_body[task_bodies[l]])
+        return c.fail(-1, "two task bodies ride on the same moving body (dependent rows)");
+  tree_cols_fill(c.hc->model, C);
   TsConst T;
   int nj = 0;
-  for (int d = 0; d < WBC_NDOF; ++d) {
-    C.col_body[d] = K.col_body[d];
-    if (K.col_body[d] >= 0) { if (nj < TI_NJ) C.jcol[nj] = 6 + d; ++nj; }
-  }
-  if (nj != TI_NJ) return wbc_sim_internal_fail(-3, "wbc_sim_task_inverse_dynamics: the model's tree is not one the kernel walks");
+  for (int d = 0; d < WBC_NDOF; ++d)
+    if (C.col_body[d] >= 0) { if (nj < TI_NJ) C.jcol[nj] = 6 + d; ++nj; }
+  if (nj != TI_NJ) return c.no_tree();
+  const int n = c.n;
   if (n <= 0) return 0;
-  for (int b = 0; b < WBC_NB; ++b) C.anc[b] = K.anc[b];
   C.ns = nstance; C.nt = ntasks;
   for (int k = 0; k < WBC_TASKID_MAX_STANCE; ++k) C.srb[k] = nstance > 0 ? stance_bodies[k < nstance ? k : 0] : 0;
   for (int k = 0; k < WBC_TASKID_MAX_TASKS; ++k) C.trb[k] = ntasks > 0 ? task_bodies[k < ntasks ? k : 0] : 0;
   for (int q = 0; q < TI_NJ; ++q) { T.jcol[q] = C.jcol[q]; T.lcol[6 + q] = C.jcol[q]; }
-  for (int c = 0; c < 6; ++c) T.lcol[c] = c;
+  for (int q = 0; q < 6; ++q) T.lcol[q] = q;
   T.sp = sqrtf(weights->posture); T.sf = sqrtf(weights->force); T.st = sqrtf(weights->torque); T.damping = weights->damping;
   float* h = nullptr;
   if (wbc_sim_internal_fd_scratch(s, &h) != 0) return -1;
@@ -2181,12 +2062,12 @@ extern "C" int wbc_sim_task_inverse_dynamics(wbc_sim* s, const int32_t* stance_b
         *gt = jt + (size_t)n * 6 * ntasks * BD_NCOL;
   int rc = wbc_sim_inverse_dynamics(s, nullptr, h, nullptr, stream);
   if (rc != 0) return rc;
-  hipLaunchKernelGGL(wbc_taskid_rhs_kernel, dim3((n + BA_EPW - 1) / BA_EPW), dim3(64), 0, (hipStream_t)stream, C, root, dofs, active, (const float*)h, n,
-                     blk, gamma, jt, gt);
-  if (hipGetLastError() != hipSuccess) return wbc_sim_internal_fail(-2, "wbc_sim_task_inverse_dynamics: launch failed");
-  rc = mass_solve_launch(s, who, blk, (int64_t)nr * BD_NCOL, nr, nullptr, Y, flags, stream);
+  hipLaunchKernelGGL(wbc_taskid_rhs_kernel, dim3((n + BA_EPW - 1) / BA_EPW), dim3(64), 0, (hipStream_t)stream, C, c.root, c.dofs, active, (const float*)h,
+                     n, blk, gamma, jt, gt);
+  if ((rc = c.launched()) != 0) return rc;
+  rc = mass_solve_launch(c, blk, (int64_t)nr * BD_NCOL, nr, nullptr, Y, flags, stream);
   if (rc != 0) return rc;
   hipLaunchKernelGGL(wbc_taskid_solve_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, T, (const float*)blk, (const float*)Y, (const float*)gamma,
                      (const float*)jt, (const float*)gt, active, stance_acc, task_acc, task_weight, nudot_ref, nstance, ntasks, n, tau, nudot, lambda);
-  return hipGetLastError() == hipSuccess ? 0 : wbc_sim_internal_fail(-2, "wbc_sim_task_inverse_dynamics: launch failed");
+  return c.launched();
 }

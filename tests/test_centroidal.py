@@ -27,9 +27,6 @@ absolute velocities would leave C / 16 on the fast family; the relative form doe
 """
 import ctypes as C
 import functools
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -37,11 +34,10 @@ import torch
 
 import centroidal_reference as cr
 import inverse_dynamics_reference as idr
+import arm_codegen
 import whole_body_reference as wb
 from wbc_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 EPS, FAMILIES = cr.EPS, cr.FAMILIES
 FINGERS = [6 + 18, 6 + 19]
 SENTINEL = 12345.0
@@ -93,23 +89,11 @@ def test_null_arguments_are_rejected_without_a_device():
     assert b"NULL" in L.wbc_last_error()
 
 
-def test_centroidal_kernel_codegen(tmp_path):
+def test_centroidal_kernel_codegen():
     """The code object's metadata alone: no scratch, the launch's workgroup size, static LDS small enough for 16 workgroups per CU."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    import sys
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    out = str(tmp_path / "arm.s")
-    flags = [f for f in g.COMMON_FLAGS if f != "-fPIC"] + g.EXTRA_FLAGS.get("wbc_arm_kernel.hip", [])
-    subprocess.check_call([HIPCC] + flags + ["-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"), "-o", out,
-                           os.path.join(ROOT, "deep-whole-body-control_amd", "csrc", "wbc_arm_kernel.hip")], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    entries = text[text.index("amdhsa.kernels:"):].split("\n  - .agpr_count")
-    meta = next(e for e in entries if re.search(r"\.name:\s+wbc_centroidal_kernel\n", e))
-    assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0
-    assert int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", meta).group(1)) == 64
-    assert int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", meta).group(1)) <= 160 * 1024 // 16
+    assert arm_codegen.meta("wbc_centroidal_kernel", "private_segment_fixed_size") == 0
+    assert arm_codegen.meta("wbc_centroidal_kernel", "max_flat_workgroup_size") == 64
+    assert arm_codegen.meta("wbc_centroidal_kernel", "group_segment_fixed_size") <= 160 * 1024 // 16
 
 
 def test_reference_matrix_is_the_mass_matrix_moved_to_the_centre_of_mass():

@@ -30,9 +30,6 @@ of each body's own origin, so that every lever is a link or centre-of-mass offse
 """
 import ctypes as C
 import functools
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -42,10 +39,9 @@ import dynamics_derivatives_reference as ddr
 import inverse_dynamics_reference as idr
 import mass_solve_reference as msr
 import test_centroidal as tc
+import arm_codegen
 import whole_body_reference as wb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 EPS, NCOL = ddr.EPS, ddr.NCOL
 FINGERS, LIVE = ddr.FINGERS, ddr.LIVE
 SENTINEL = 12345.0
@@ -256,23 +252,11 @@ def test_null_arguments_are_rejected_without_a_device():
     assert L.wbc_sim_forward_dynamics_derivatives_workspace_floats(13) == 13 * MENV * 5 + MENV
 
 
-def test_dynamics_derivatives_kernel_codegen(tmp_path):
+def test_dynamics_derivatives_kernel_codegen():
     """The code object's metadata alone: no scratch, the launch's workgroup size, static LDS within 20 KB (8 workgroups per CU)."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    import sys
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    out = str(tmp_path / "arm.s")
-    flags = [f for f in g.COMMON_FLAGS if f != "-fPIC"] + g.EXTRA_FLAGS.get("wbc_arm_kernel.hip", [])
-    subprocess.check_call([HIPCC] + flags + ["-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"), "-o", out,
-                           os.path.join(ROOT, "deep-whole-body-control_amd", "csrc", "wbc_arm_kernel.hip")], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    entries = text[text.index("amdhsa.kernels:"):].split("\n  - .agpr_count")
-    meta = next(e for e in entries if re.search(r"\.name:\s+wbc_dynamics_derivatives_kernel\n", e))
-    assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0
-    assert int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", meta).group(1)) == 64
-    assert int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", meta).group(1)) <= 20480
+    assert arm_codegen.meta("wbc_dynamics_derivatives_kernel", "private_segment_fixed_size") == 0
+    assert arm_codegen.meta("wbc_dynamics_derivatives_kernel", "max_flat_workgroup_size") == 64
+    assert arm_codegen.meta("wbc_dynamics_derivatives_kernel", "group_segment_fixed_size") <= 20480
 
 
 # ------------------------------------------------------------------------------------------------------------ GPU

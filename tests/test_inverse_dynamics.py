@@ -8,20 +8,17 @@ the absolute values of the terms that make up row k). C_ID and C_MM follow the l
 to a power of two) and may not exceed 4096; the measured ratios stand next to the constants."""
 import copy
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import inverse_dynamics_reference as idr
+import arm_codegen
 import whole_body_reference as wb
 from wbc_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FINGERS = [6 + 18, 6 + 19]
 LIVE = [c for c in range(wb.NCOL) if c not in FINGERS]
 EPS = 2.0 ** -24
@@ -185,25 +182,12 @@ def test_null_arguments_are_rejected_without_a_device():
     assert b"NULL" in L.wbc_last_error()
 
 
-def test_inverse_dynamics_kernel_codegen(tmp_path):
+def test_inverse_dynamics_kernel_codegen():
     """No scratch, no flat memory instructions, and static LDS small enough for 16 workgroups (of 64 lanes: 32 envs) per CU."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    import sys
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    out = str(tmp_path / "arm.s")
-    flags = [f for f in g.COMMON_FLAGS if f != "-fPIC"] + g.EXTRA_FLAGS.get("wbc_arm_kernel.hip", [])
-    subprocess.check_call([HIPCC] + flags + ["-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"), "-o", out,
-                           os.path.join(ROOT, "deep-whole-body-control_amd", "csrc", "wbc_arm_kernel.hip")], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    entries = text[text.index("amdhsa.kernels:"):].split("\n  - .agpr_count")
-    meta = next(e for e in entries if re.search(r"\.name:\s+wbc_inverse_dynamics_kernel\n", e))
-    assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0
-    assert int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", meta).group(1)) == 64
-    assert int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", meta).group(1)) <= 160 * 1024 // 16
-    body = text[text.index("\nwbc_inverse_dynamics_kernel:"):]
-    body = body[:body.index(".Lfunc_end")]                      # the whole function, out-of-line blocks included
+    assert arm_codegen.meta("wbc_inverse_dynamics_kernel", "private_segment_fixed_size") == 0
+    assert arm_codegen.meta("wbc_inverse_dynamics_kernel", "max_flat_workgroup_size") == 64
+    assert arm_codegen.meta("wbc_inverse_dynamics_kernel", "group_segment_fixed_size") <= 160 * 1024 // 16
+    body = arm_codegen.body("wbc_inverse_dynamics_kernel")
     assert "s_endpgm" in body and re.search(r"\bglobal_store_dword\b", body)
     assert not re.search(r"\bflat_", body) and "scratch_" not in body
 

@@ -18,9 +18,7 @@ round trip ID(FD(tau)) 0.042, against the oracle's ABA 0.0043 (armature) and 0.0
 import copy
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -28,11 +26,10 @@ import torch
 
 import inverse_dynamics_reference as idr
 import mass_solve_reference as msr
+import arm_codegen
 import whole_body_reference as wb
 from wbc_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FINGERS, LIVE, EPS, C_S = msr.FINGERS, msr.LIVE, msr.EPS, msr.C_S
 # The allowances of the two sibling kernels, restated from tests/test_inverse_dynamics.py (where their derivation stands):
 # |h_kernel - h_ref|_k <= C_ID 2^-24 mag_k, and the mass-matrix kernel's share C_MM 2^-24 (|mm| |x|)_k of a product mm @ x.
@@ -69,25 +66,12 @@ def test_null_arguments_are_rejected_without_a_device():
     assert b"NULL" in L.wbc_last_error()
 
 
-def test_mass_solve_kernel_codegen(tmp_path):
+def test_mass_solve_kernel_codegen():
     """No scratch, no flat memory instructions, the launch's workgroup size, static LDS small enough for 16 workgroups per CU."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    import sys
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    out = str(tmp_path / "arm.s")
-    flags = [f for f in g.COMMON_FLAGS if f != "-fPIC"] + g.EXTRA_FLAGS.get("wbc_arm_kernel.hip", [])
-    subprocess.check_call([HIPCC] + flags + ["-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"), "-o", out,
-                           os.path.join(ROOT, "deep-whole-body-control_amd", "csrc", "wbc_arm_kernel.hip")], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    entries = text[text.index("amdhsa.kernels:"):].split("\n  - .agpr_count")
-    meta = next(e for e in entries if re.search(r"\.name:\s+wbc_mass_solve_kernel\n", e))
-    assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0
-    assert int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", meta).group(1)) == 64
-    assert int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", meta).group(1)) <= 160 * 1024 // 16
-    body = text[text.index("\nwbc_mass_solve_kernel:"):]
-    body = body[:body.index(".Lfunc_end")]                      # the whole function, out-of-line blocks included
+    assert arm_codegen.meta("wbc_mass_solve_kernel", "private_segment_fixed_size") == 0
+    assert arm_codegen.meta("wbc_mass_solve_kernel", "max_flat_workgroup_size") == 64
+    assert arm_codegen.meta("wbc_mass_solve_kernel", "group_segment_fixed_size") <= 160 * 1024 // 16
+    body = arm_codegen.body("wbc_mass_solve_kernel")
     assert "s_endpgm" in body
     assert not re.search(r"\bflat_", body) and "scratch_" not in body
 

@@ -32,9 +32,7 @@ The largest condition number of the diagonally scaled Delassus matrix is 96.9 ov
 """
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -44,11 +42,10 @@ import constrained_dynamics_reference as cdr
 import inverse_dynamics_reference as idr
 import mass_solve_reference as msr
 import task_inverse_dynamics_reference as tir
+import arm_codegen
 import whole_body_reference as wb
 from wbc_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FINGERS, LIVE, JOINTS, EPS = tir.FINGERS, tir.LIVE, tir.JOINTS, tir.EPS
 C_ID, C_A = tir.C_ID, tir.C_A
 C_TIER = {"root": tir.C_ROOT, "joint": tir.C_JOINT, "stance": tir.C_STANCE, "grad": tir.C_GRAD}
@@ -139,26 +136,13 @@ def test_abi_refusals_without_a_device():
     assert ws(0, 4, 6) == 0 and ws(10, 5, 6) == 0 and ws(10, -1, 6) == 0 and ws(10, 4, 7) == 0 and ws(10, 4, -1) == 0
 
 
-def test_new_kernels_codegen(tmp_path):
+def test_new_kernels_codegen():
     """No scratch, no flat memory instructions, the launch's workgroup size, static LDS within the 20 kB the derivatives kernel lives under."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    import sys
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    out = str(tmp_path / "arm.s")
-    flags = [f for f in g.COMMON_FLAGS if f != "-fPIC"] + g.EXTRA_FLAGS.get("wbc_arm_kernel.hip", [])
-    subprocess.check_call([HIPCC] + flags + ["-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"), "-o", out,
-                           os.path.join(ROOT, "deep-whole-body-control_amd", "csrc", "wbc_arm_kernel.hip")], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    entries = text[text.index("amdhsa.kernels:"):].split("\n  - .agpr_count")
     for kernel in ("wbc_taskid_rhs_kernel", "wbc_taskid_solve_kernel"):
-        meta = next(e for e in entries if re.search(r"\.name:\s+%s\n" % kernel, e))
-        assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0, kernel
-        assert int(re.search(r"\.max_flat_workgroup_size:\s+(\d+)", meta).group(1)) == 64, kernel
-        assert int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", meta).group(1)) <= LDS_CAP, kernel
-        body = text[text.index("\n%s:" % kernel):]
-        body = body[:body.index(".Lfunc_end")]                      # the whole function, out-of-line blocks included
+        assert arm_codegen.meta(kernel, "private_segment_fixed_size") == 0, kernel
+        assert arm_codegen.meta(kernel, "max_flat_workgroup_size") == 64, kernel
+        assert arm_codegen.meta(kernel, "group_segment_fixed_size") <= LDS_CAP, kernel
+        body = arm_codegen.body(kernel)
         assert "s_endpgm" in body and re.search(r"\bglobal_store_dword", body), kernel
         assert not re.search(r"\bflat_", body) and "scratch_" not in body, kernel
 

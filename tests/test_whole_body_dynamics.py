@@ -3,20 +3,17 @@ include/wbc_sim.h). The CPU tests pin the fp64 restatement tests/whole_body_refe
 rigid-body velocities and to the arm restatement oracle/arm_osc_oracle.py; the GPU tests hold the kernel to that restatement, to
 the step kernel's rigid-body state and to wbc_sim_arm_dynamics, through the reference's own slicing expressions."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import arm_codegen
 import arm_osc_oracle as ao
 import whole_body_reference as wb
 from wbc_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FINGERS = [6 + 18, 6 + 19]
 LIVE = [c for c in range(wb.NCOL) if c not in FINGERS]
 
@@ -135,25 +132,12 @@ def test_reference_mass_matrix_properties_and_arm_block():
         np.testing.assert_allclose(wb.jacobian(m, pos, quat, q)[gripper_rb, :, -8:-2], Ja, atol=1e-12)
 
 
-def test_body_dynamics_kernel_codegen(tmp_path):
+def test_body_dynamics_kernel_codegen():
     """No scratch, no flat memory instructions, and every global store is a 16-byte-per-lane store (the sweeps' coalesced rows)."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    import sys
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as g
-    out = str(tmp_path / "arm.s")
-    flags = [f for f in g.COMMON_FLAGS if f != "-fPIC"] + g.EXTRA_FLAGS.get("wbc_arm_kernel.hip", [])
-    subprocess.check_call([HIPCC] + flags + ["-S", "--cuda-device-only", "-I" + os.path.join(ROOT, "include"), "-o", out,
-                           os.path.join(ROOT, "deep-whole-body-control_amd", "csrc", "wbc_arm_kernel.hip")], stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    entries = text[text.index("amdhsa.kernels:"):].split("\n  - .agpr_count")
-    meta = next(e for e in entries if re.search(r"\.name:\s+wbc_body_dynamics_kernel\n", e))
-    assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1)) == 0
+    assert arm_codegen.meta("wbc_body_dynamics_kernel", "private_segment_fixed_size") == 0
     # static LDS (+ 5.6 KB dynamic for the J chunk when J is written): 15 envs per CU either way
-    assert int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", meta).group(1)) + 9 * 156 * 4 <= 160 * 1024 // 15
-    body = text[text.index("\nwbc_body_dynamics_kernel:"):]
-    body = body[:body.index("s_endpgm")]
+    assert arm_codegen.meta("wbc_body_dynamics_kernel", "group_segment_fixed_size") + 9 * 156 * 4 <= 160 * 1024 // 15
+    body = arm_codegen.body("wbc_body_dynamics_kernel", end="s_endpgm")
     assert not re.search(r"\bflat_(load|store)", body) and "scratch_" not in body
     stores = re.findall(r"\bglobal_store_\w+", body)
     assert stores and set(stores) == {"global_store_dwordx4"}

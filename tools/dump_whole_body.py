@@ -1,0 +1,116 @@
+"""Every output of every entry point of csrc/wbc_arm_kernel.hip at seeded states, saved to one .npz. A change that must leave those
+kernels' results bit-identical is checked by dumping once per library build (WBC_AMD_LIB selects the library; each dump in a process of
+its own) and comparing the two files as raw 32-bit integers.
+
+  WBC_AMD_LIB=/path/libwbc_amd.so python tools/dump_whole_body.py OUT.npz      dump
+  python tools/dump_whole_body.py --compare A.npz B.npz                         exit status 1 unless every array is equal, bit for bit
+
+Envs n = 1, 13, 64 (13: the idle half-workgroup of the two-envs-per-workgroup kernels is live); states and body parameters from the
+generators of tests/test_mass_solve.py.
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+if sys.argv[1:2] == ["--compare"]:
+    A, B = np.load(sys.argv[2]), np.load(sys.argv[3])
+    bad = sorted(set(A.files) ^ set(B.files))
+    for k in sorted(set(A.files) & set(B.files)):
+        a, b = A[k], B[k]
+        if a.shape != b.shape or not np.array_equal(a.view(np.uint32), b.view(np.uint32)):
+            bad.append(k)
+            if a.shape == b.shape:
+                print(f"{k}: {int((a.view(np.uint32) != b.view(np.uint32)).sum())} of {a.size} words differ, largest |difference| {np.nanmax(np.abs(a - b)):.3g}")
+    print(f"{len(A.files)} arrays, {sum(A[k].size for k in A.files)} words: " + ("every array bit-identical" if not bad else f"DIFFERENT: {bad}"))
+    sys.exit(1 if bad else 0)
+
+for d in ("deep-whole-body-control_amd", "oracle", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, d))
+import torch  # noqa: E402
+
+import test_mass_solve as tms  # noqa: E402
+from wbc_amd.config import WidowGo1RoughCfg  # noqa: E402
+from wbc_amd.envs import WidowGo1  # noqa: E402
+
+out = {}
+
+
+def keep(name, *tensors):
+    torch.cuda.synchronize()
+    for i, t in enumerate(tensors):
+        a = t.detach().cpu().numpy()
+        assert a.dtype == np.float32, name
+        if not np.isfinite(a).all():
+            print(f"{name}.{i}: {int((~np.isfinite(a)).sum())} non-finite values")
+        out[f"{name}.{i}"] = a
+
+
+for n in (1, 13, 64):
+    cfg = WidowGo1RoughCfg(); cfg.env.num_envs = n; cfg.terrain.mesh_type = "plane"
+    env = WidowGo1(cfg, sim_device="cuda:0", seed=5)
+    sim, m, dev = env.sim, env.robot_model, "cuda"
+    root, dof = sim.tensor("ROOT_STATES").clone(), sim.tensor("DOF_STATE").clone()
+    bps = []
+    for e in range(n):
+        rng = np.random.default_rng(1000 * n + e)
+        pos, quat, q, nu = tms._random_state(rng)
+        bps.append(tms._random_body_params(m, rng))
+        root[e, 0] = torch.tensor(np.concatenate([pos, quat, nu[0:6]]), dtype=torch.float32)
+        dof[e] = torch.tensor(np.stack([q, nu[6:]], -1), dtype=torch.float32)
+    sim.set_root_state(root.contiguous()); sim.set_dof_state(dof.contiguous())
+    sim.tensor("BODY_PARAMS").copy_(torch.tensor(np.array(bps), dtype=torch.float32))
+    g = torch.Generator(device=dev); g.manual_seed(n)
+    rnd = lambda *shape, scale=1.0: ((torch.rand(*shape, device=dev, generator=g) * 2 - 1) * scale).contiguous()  # noqa: E731
+    nudot = rnd(n, 26, scale=20.0)
+    tau = rnd(n, 26, scale=10.0)
+    feet, grip = [int(i) for i in env.feet_indices.tolist()], int(env.gripper_idx)
+    T = f"n{n}."
+
+    keep(T + "arm", *sim.arm_dynamics(env._arm_link_rb, m.rb_mass[-9:]))
+    jac, mm = torch.empty(n, 27, 6, 26, device=dev), torch.empty(n, 26, 26, device=dev)
+    sim.body_dynamics(jac=jac, mm=mm); keep(T + "body", jac, mm)
+    mm1 = torch.empty_like(mm); sim.body_dynamics(mm=mm1); keep(T + "body.mm_only", mm1)
+    for tag, nd in (("nudot", nudot), ("null", None)):
+        t, gv = torch.empty(n, 26, device=dev), torch.empty(n, 26, device=dev)
+        sim.inverse_dynamics(nudot=nd, tau=t, grav=gv); keep(T + "id." + tag, t, gv)
+        keep(T + "accel." + tag, sim.body_accelerations(nd))
+        keep(T + "centroidal." + tag, *sim.centroidal(nudot=nd))
+        for tr in (False, True):
+            keep(T + f"idd.{tag}.t{int(tr)}", *sim.inverse_dynamics_derivatives(nudot=nd, transposed=tr))
+    gv = torch.empty(n, 26, device=dev); sim.inverse_dynamics(grav=gv); keep(T + "id.grav_only", gv)
+    cm = torch.empty(n, 9, device=dev)
+    check = sim.L.wbc_sim_centroidal(sim.h, None, cm.data_ptr(), None, None, None, sim._stream())
+    assert check == 0
+    keep(T + "centroidal.com_only", cm)
+    dq = torch.empty(n, 26, 26, device=dev)
+    assert sim.L.wbc_sim_inverse_dynamics_derivatives(sim.h, nudot.data_ptr(), dq.data_ptr(), None, 0, sim._stream()) == 0
+    keep(T + "idd.dq_only", dq)
+    for arm in (False, True):
+        A = f".a{int(arm)}"
+        keep(T + "solve1" + A, sim.mass_solve(tau, armature=arm))
+        keep(T + "solve32" + A, sim.mass_solve(rnd(n, 32, 26, scale=5.0), armature=arm))
+        keep(T + "solve.jac_view" + A, sim.mass_solve(jac[:, grip], armature=arm))
+        keep(T + "fd" + A, sim.forward_dynamics(tau, armature=arm))
+        keep(T + "fd.null" + A, sim.forward_dynamics(None, armature=arm))
+        for tr in (False, True):
+            keep(T + f"fdd.t{int(tr)}" + A, *sim.forward_dynamics_derivatives(tau=tau, armature=arm, transposed=tr))
+        act = (torch.rand(n, 4, device=dev, generator=g) < 0.6)
+        ades = rnd(n, 4, 3, scale=3.0)
+        keep(T + "cd.1" + A, *sim.constrained_dynamics([grip], tau=tau, armature=arm))
+        keep(T + "cd.4" + A, *sim.constrained_dynamics(feet, tau=tau, active=act, acc_des=ades, damping=1e-3, armature=arm))
+        keep(T + "cd.5" + A, *sim.constrained_dynamics(feet + [grip], tau=None, damping=1e-4, armature=arm))
+        keep(T + "tid.0_0" + A, *sim.task_inverse_dynamics(armature=arm))
+        tasks = [0, grip] + feet
+        w = torch.ones(n, 6, 6, device=dev); w[:, 2:] = 0.0
+        keep(T + "tid.4_6" + A, *sim.task_inverse_dynamics(feet, tasks, rnd(n, 6, 6, scale=2.0), w, active=act, stance_acc=ades,
+                                                         nudot_ref=rnd(n, 26), damping=1e-4, armature=arm))
+        keep(T + "tid.4_6.plain" + A, *sim.task_inverse_dynamics(feet, tasks, rnd(n, 6, 6, scale=2.0), armature=arm))
+    md = torch.empty(n, 26, 26, device=dev)
+    fd = sim.forward_dynamics_derivatives(tau=None, minv=md)
+    keep(T + "fdd.tau_null", *fd)
+
+np.savez(sys.argv[1], **out)
+print(f"{len(out)} arrays, {sum(a.size for a in out.values())} words -> {sys.argv[1]}")
