@@ -2006,19 +2006,489 @@ extern "C" size_t wbc_sim_task_inverse_dynamics_workspace_floats(int num_envs, i
   return (size_t)num_envs * (2 * (size_t)(3 * nstance + 1 + TI_NJ) * BD_NCOL + CD_GSTRIDE + (size_t)6 * ntasks * BD_NCOL + TI_MAXT);
 }
 
-// Four launches on `stream`. Arguments and conventions: include/wbc_sim.h.
-extern "C" int wbc_sim_task_inverse_dynamics(wbc_sim* s, const int32_t* stance_bodies, int nstance, const uint8_t* active, const float* stance_acc,
-                                             const int32_t* task_bodies, int ntasks, const float* task_acc, const float* task_weight,
-                                             const float* nudot_ref, const wbc_taskid_weights* weights, int flags, float* tau, float* nudot,
-                                             float* lambda, float* workspace, void* stream) {
-  WbCall c("wbc_sim_task_inverse_dynamics", s, stream);
+// ---- the same problem with torque limits and friction pyramids (include/wbc_sim.h: wbc_sim_task_inverse_dynamics_qp) ------------------
+// Launches 1-3 are the sibling's. wbc_taskqp_solve_kernel repeats its steps 1-3 (same statements, same order: where no inequality binds
+// the outputs are the sibling's bit for bit), keeps [G_lambda | lambda_0] from before the force rows are scaled, and with R, c of the
+// reflected stack solves
+//     min 1/2 |R x + c|^2   s.t.  |x_j| <= lim_j,  a_i . (lambda_0 + G_lambda x) >= b_i  (five rows per active stance body)
+// by the dual active-set method of Goldfarb and Idnani in the variable y = R x + c, where the objective is 1/2 |y|^2, the unconstrained
+// optimum is y = 0 and row i reads d_i . y >= beta_i with d_i = R^-T n_i, beta_i = b_i + d_i . c. One lane per row (36 + 5 ns <= 56).
+// The working set W (at most 18 independent rows) is carried as D_W = Q T, Q orthonormal [18, q] and T upper triangular, built column
+// by column by twice-applied Gram-Schmidt from the ORIGINAL d_i: a column depends on the columns before it alone, so adding a row
+// appends one column, dropping row l rebuilds the columns after l, and the factor never drifts (it is what a rebuild from scratch gives).
+// After every accepted row the iterate and the multipliers are REBUILT from W, never accumulated:
+//     v = T^-T beta_W,  y = Q v,  u = T^-1 v,  x = R^-1 (y - c).
+// A candidate p that depends on W (|z|^2 <= TQ_DEP2 |d_p|^2, z = d_p - Q Q^T d_p; always so at q = 18) takes the method's dual step: no
+// primal move, u -= t r, u_p += t with r = T^-1 Q^T d_p, and the blocking row leaves W; with no blocking row the rows admit no point.
+// A dependent candidate whose slack as W implies it, sum_j r_j b_j - b_p, is no violation is set aside until W changes: the rounding
+// of x alone made it look violated (the fourth and fifth row of a pyramid whose apex is the optimum), and swapping it in would cycle.
+// Between accepted rows only the candidate's slack s_p (+= t |z|^2) and the multipliers move. Slacks are evaluated in x: lambda(x) and
+// the sum of its absolute terms per stance row, then each row's value and scale; a contact row counts as violated below -TQ_TOL scale, a box row below 0.
+#define TQ_NROW (2 * TI_NJ + 5 * WBC_TASKID_MAX_STANCE)    // 56 rows at most: bit = lane = row
+#define TQ_C0 (2 * TI_NJ)                        // first contact row
+#define TQ_PITCH (TI_NJ + 1)                     // LDS pitch of the 18-vectors (odd)
+#define TQ_TOL 1.52587891e-5f                    // 256 x 2^-24 of a row's scale: an fp32 evaluation of a row at the rebuilt x is off by 100-300 x
+                                                 // 2^-24 of it, and a tolerance below that level makes the five rows of a pyramid's apex cycle
+#define TQ_DEP2 1e-8f                            // |z|^2 / |d_p|^2 at or below which p depends on W
+#define TQ_DEFAULT_ITER 100
+static_assert(TQ_NROW <= 64 && TQ_NROW * TQ_PITCH <= (TI_MAXROWS - TI_NJ) * TI_NC && WBC_TASKQP_MAX_ITER >= TQ_DEFAULT_ITER, "rows");
+struct TqConst {
+  TsConst s;
+  float lim[TI_NJ];                              // wbc_task_cfg.torque_limits of joint torque j
+  float mu, fn_min;
+  int32_t max_iter;
+};
+
+extern "C" __global__ void __launch_bounds__(64) wbc_taskqp_solve_kernel(TqConst Cq, const float* __restrict__ rhs, const float* __restrict__ Y,
+                                                                        const float* __restrict__ gamma, const float* __restrict__ jt,
+                                                                        const float* __restrict__ gt, const uint8_t* __restrict__ active,
+                                                                        const float* __restrict__ stance_acc, const float* __restrict__ task_acc,
+                                                                        const float* __restrict__ task_weight, const float* __restrict__ nudot_ref,
+                                                                        const float* __restrict__ tau_limit, const float* __restrict__ normal,
+                                                                        const float* __restrict__ mu, int ns, int nt, int n,
+                                                                        float* __restrict__ tau, float* __restrict__ nudot, float* __restrict__ lambda,
+                                                                        int32_t* __restrict__ status_out, int64_t* __restrict__ set_out,
+                                                                        int32_t* __restrict__ iter_out) {
+  __shared__ float sY[TI_MAXRHS][CD_LD], sJc[TI_MAXS][CD_LD], sJt[TI_MAXT][CD_LD];
+  __shared__ float sS[TI_MAXROWS * TI_NC];         // the stack, row-major, pitch 19; after the reflections rows 18.. hold the d_i
+  __shared__ float sA[TI_MAXS][TI_MAXS + 1];       // lower triangle: A, then L
+  __shared__ float sD[TI_MAXS + 1], sV[TI_MAXS + 1];   // 1 / L_jj; the value handed round
+  __shared__ float sP[TI_QG][TI_NC], sDiag[TI_NJ], sTau[TI_NJ], sAf[BD_NCOL];
+  __shared__ float sG[TI_MAXS][TI_NC];             // [G_lambda | lambda_0], unscaled
+  __shared__ float sQ[TI_NJ][TQ_PITCH], sT[TI_NJ][TQ_PITCH];   // sQ[j]: column j of Q; sT[a][b], a <= b
+  __shared__ float sBeta[64], sB[64], sKey[64], sSl[64], sSc[64];   // beta_i, b_i; the key of a search over the lanes; the rows' slacks, scales
+  __shared__ float sLam[TI_MAXS], sMag[TI_MAXS];   // lambda(x) and the sum of its absolute terms
+  __shared__ float sX0[TI_NJ], sU[TI_NJ + 1], sR[TI_NJ], sW[TI_NJ], sW1[TI_NJ], sZ[TI_NJ], sH[TI_NJ + 1];
+  __shared__ int32_t sRow[TI_NJ + 1];              // the rows of W, in the order of Q's columns
+  const TsConst& C = Cq.s;
+  const int lane = threadIdx.x;
+  if ((int)blockIdx.x >= n) return;
+  const size_t e = blockIdx.x;
+  const int m = 3 * ns, mt = 6 * nt, nr = m + 1 + TI_NJ;
+  const int F0 = TI_NL, T0 = F0 + m, Q0 = T0 + mt, nrow = Q0 + TI_NJ;
+  const float *rp = rhs + e * (size_t)(nr * BD_NCOL), *yp = Y + e * (size_t)(nr * BD_NCOL), *jp = jt + e * (size_t)(mt * BD_NCOL);
+  for (int t = lane; t < nr * BD_NCOL; t += 64) {
+    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+    sY[r][c] = yp[t];
+    if (r < m) sJc[r][c] = rp[t];
+  }
+  for (int t = lane; t < mt * BD_NCOL; t += 64) {
+    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+    sJt[r][c] = jp[t];
+  }
+  uint32_t act = 0;                                // bit i: row i belongs to an active stance body
+  for (int k = 0; k < ns; ++k)
+    if (!active || active[e * ns + k]) act |= 7u << (3 * k);
+  __syncthreads();
+
+  // 1) the Delassus matrix and the 19 right-hand sides of its factor
+  for (int t = lane; t < m * (m + 1) / 2; t += 64) {
+    int i = (int)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);              // t = i (i + 1) / 2 + j, j <= i
+    i = i * (i + 1) / 2 > t ? i - 1 : ((i + 1) * (i + 2) / 2 <= t ? i + 1 : i);
+    const int j = t - i * (i + 1) / 2;
+    float a = 0.f;
+    for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * sY[j][c];
+    const bool on = ((act >> i) & 1u) && ((act >> j) & 1u);
+    sA[i][j] = on ? (i == j ? a + C.damping : a) : (i == j ? 1.f : 0.f);
+  }
+  for (int t = lane; t < m * TI_NC; t += 64) {
+    const int i = t / TI_NC, j = t - i * TI_NC;
+    float v = 0.f;
+    if ((act >> i) & 1u) {
+      const float* y = sY[j < TI_NJ ? m + 1 + j : m];
+      float a = 0.f;
+      for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * y[c];
+      v = j < TI_NJ ? 0.f - a : ((stance_acc ? stance_acc[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
+    }
+    sS[(F0 + i) * TI_NC + j] = v;
+  }
+  {
+    const int i = lane;
+    const bool row = i < m;
+    for (int j = 0; j < m; ++j) {
+      __syncthreads();
+      float d = sA[j][j];
+      for (int k = 0; k < j; ++k) d -= sA[j][k] * sA[j][k];
+      const float id = 1.f / __fsqrt_rn(d);
+      if (row && i > j) {
+        float s = sA[i][j];
+        for (int k = 0; k < j; ++k) s -= sA[i][k] * sA[j][k];
+        sA[i][j] = s * id;
+      }
+      if (i == j) sD[j] = id;
+    }
+  }
+  __syncthreads();
+  if (lane < TI_NC) {                              // L L^T x = column `lane`, in place
+    float* x = sS + F0 * TI_NC + lane;
+    for (int i = 0; i < m; ++i) {
+      float s = x[i * TI_NC];
+      for (int k = 0; k < i; ++k) s -= sA[i][k] * x[k * TI_NC];
+      x[i * TI_NC] = s * sD[i];
+    }
+    for (int i = m - 1; i >= 0; --i) {
+      float s = x[i * TI_NC];
+      for (int k = i + 1; k < m; ++k) s -= sA[k][i] * x[k * TI_NC];
+      x[i * TI_NC] = s * sD[i];
+    }
+  }
+  __syncthreads();
+  for (int t = lane; t < m * TI_NC; t += 64) sG[t / TI_NC][t % TI_NC] = sS[F0 * TI_NC + t];
+
+  // 2) the stack
+  for (int t = lane; t < TI_NL * TI_NC; t += 64) {
+    const int s = t / TI_NC, j = t - s * TI_NC, c = C.lcol[s];
+    float a = sY[j < TI_NJ ? m + 1 + j : m][c];
+    for (int k = 0; k < m; ++k) a += sY[k][c] * sS[(F0 + k) * TI_NC + j];
+    sS[t] = a;
+  }
+  __syncthreads();
+  for (int t = lane; t < mt * TI_NC; t += 64) {
+    const int r = t / TI_NC, j = t - r * TI_NC;
+    const float w = task_weight ? task_weight[e * mt + r] : 1.f;
+    float v = 0.f;
+    if (w > 0.f) {
+      float a = 0.f;
+      for (int s = 0; s < TI_NL; ++s) a += sJt[r][C.lcol[s]] * sS[s * TI_NC + j];
+      if (j == TI_NJ) a += gt[e * TI_MAXT + r] - task_acc[e * mt + r];
+      v = __fsqrt_rn(w) * a;
+    }
+    sS[(T0 + r) * TI_NC + j] = v;
+  }
+  __syncthreads();
+  for (int t = lane; t < TI_NL * TI_NC; t += 64) {
+    const int s = t / TI_NC, j = t - s * TI_NC;
+    const float ref = (j == TI_NJ && nudot_ref) ? nudot_ref[e * BD_NCOL + C.lcol[s]] : 0.f;
+    sS[t] = C.sp * (sS[t] - ref);
+  }
+  for (int t = lane; t < m * TI_NC; t += 64) sS[F0 * TI_NC + t] *= C.sf;
+  for (int t = lane; t < TI_NJ * TI_NC; t += 64) {
+    const int i = t / TI_NC, j = t - i * TI_NC;
+    sS[Q0 * TI_NC + t] = i == j ? C.st : 0.f;
+  }
+  __syncthreads();
+
+  // 3) Householder reflections
+  {
+    const int g = lane / TI_NC, j = lane - g * TI_NC;
+    const bool mine = g < TI_QG;
+    for (int k = 0; k < TI_NJ; ++k) {
+      if (mine) {
+        float part = 0.f;
+        if (j >= k)
+          for (int r = k + g; r < nrow; r += TI_QG) part += sS[r * TI_NC + k] * sS[r * TI_NC + j];
+        sP[g][j] = part;
+      }
+      __syncthreads();
+      const float skk = (sP[0][k] + sP[1][k]) + sP[2][k], akk = sS[k * TI_NC + k];
+      const float nrm = __fsqrt_rn(skk), alpha = akk >= 0.f ? 0.f - nrm : nrm, vk = akk - alpha;
+      float tj = 0.f;                              // 2 (v . a_j) / (v . v), v = a_k - alpha e_k: v . v = -2 alpha v_k
+      if (mine && j > k) tj = (((sP[0][j] + sP[1][j]) + sP[2][j]) - alpha * sS[k * TI_NC + j]) * (-1.f / (alpha * vk));
+      __syncthreads();
+      if (mine && j > k)
+        for (int r = k + g; r < nrow; r += TI_QG) sS[r * TI_NC + j] -= tj * (r == k ? vk : sS[r * TI_NC + k]);
+      if (lane == k) sDiag[k] = alpha;
+      __syncthreads();
+    }
+  }
+
+  // 4) the unconstrained optimum: R x = -(Q^T b)
+  for (int k = TI_NJ - 1; k >= 0; --k) {
+    float x = 0.f - sS[k * TI_NC + TI_NJ];
+    for (int j = k + 1; j < TI_NJ; ++j) x -= sS[k * TI_NC + j] * sTau[j];
+    if (lane == 0) sTau[k] = x / sDiag[k];
+    __syncthreads();
+  }
+
+  // 5) the rows: lane j < 18: x_j <= lim_j; lane 18 + j: x_j >= -lim_j; lane 36 + 5 k + t: row t of active stance body k
+  float* sDm = sS + TI_NJ * TI_NC;                 // d_i = R^-T n_i at sDm[i * TQ_PITCH + 0..17]
+  const int jl = lane < TI_NJ ? lane : lane - TI_NJ, rc = lane - TQ_C0, kf = rc >= 0 ? rc / 5 : 0, tf = rc - 5 * kf;
+  const bool box = lane < TQ_C0, valid = box || (rc < 5 * ns && ((act >> (3 * kf)) & 1u));
+  float lim = 0.f, bq = 0.f, mu0 = Cq.mu;
+  asm volatile("" : "+s"(mu0));                 // the host scalar as a value: a select between its address and `mu` would be a flat load
+  f3 ar = mk3(0.f, 0.f, 0.f);                      // a contact row in force space: a . lambda_k >= bq
+  if (box) {
+    for (int q = 0; q < TI_NJ; ++q) lim = q == jl ? Cq.lim[q] : lim;
+    if (tau_limit) lim = tau_limit[e * TI_NJ + jl];
+  } else if (valid) {
+    f3 nn = mk3(0.f, 0.f, 1.f), t1 = mk3(1.f, 0.f, 0.f), t2 = mk3(0.f, 1.f, 0.f);
+    if (normal) {
+      nn = ld3(normal + (e * ns + kf) * 3);
+      nn = nn * (1.f / __fsqrt_rn(dot(nn, nn)));
+      t1 = cross(nn, fabsf(nn.x) > 0.9f ? mk3(0.f, 1.f, 0.f) : mk3(1.f, 0.f, 0.f));
+      t1 = t1 * (1.f / __fsqrt_rn(dot(t1, t1)));
+      t2 = cross(nn, t1);
+    }
+    float mk = mu0;
+    if (mu) mk = mu[e * ns + kf];
+    const f3 tg = tf < 3 ? t1 : t2;
+    ar = tf == 0 ? nn : ((tf & 1) ? mk * nn - tg : mk * nn + tg);
+    bq = tf == 0 ? Cq.fn_min : 0.f;
+  }
+  for (int j = lane; j < TI_NJ; j += 64) sX0[j] = sTau[j];
+  // lambda(x) = lambda_0 + G_lambda x with the sum of its absolute terms, then every row's slack and its key: the violation in units
+  // of |d_i| (the distance in y) where it exceeds TQ_TOL of the row's scale and the row is not in W, else 0
+  uint64_t inW = 0, skip = 0;                      // rows in W; rows that W implies (set aside until W changes)
+  float inv_d = 1.f;                               // 1 / |d_i| once the d_i exist
+  auto slacks = [&]() {
+    __syncthreads();
+    if (lane < m) {
+      float l = sG[lane][TI_NJ], g = fabsf(l);
+      for (int j = 0; j < TI_NJ; ++j) { const float t = sG[lane][j] * sTau[j]; l += t; g += fabsf(t); }
+      sLam[lane] = l; sMag[lane] = g;
+    }
+    __syncthreads();
+    float s = 0.f, sc = 0.f;
+    if (box) { const float x = sTau[jl]; s = lane < TI_NJ ? lim - x : lim + x; sc = lim + fabsf(x); }
+    else if (valid) {
+      s = ((ar.x * sLam[3 * kf] + ar.y * sLam[3 * kf + 1]) + ar.z * sLam[3 * kf + 2]) - bq;
+      sc = ((fabsf(ar.x) * sMag[3 * kf] + fabsf(ar.y) * sMag[3 * kf + 1]) + fabsf(ar.z) * sMag[3 * kf + 2]) + fabsf(bq);
+    }
+    // a box row has no tolerance (lim -+ x is exact in sign): with no row violated every torque is inside its limit exactly
+    const bool viol = valid && !(((inW | skip) >> lane) & 1ull) && s < (box ? 0.f : 0.f - TQ_TOL * sc);
+    sSl[lane] = s; sSc[lane] = sc;
+    sKey[lane] = viol ? (0.f - s) * inv_d : 0.f;
+    __syncthreads();
+  };
+  slacks();
+  const bool any = __any(sKey[lane] > 0.f) != 0;   // no row violated at the unconstrained optimum: the solve ends here with the sibling's result
+  int status = 0, iters = 0;
+  if (any) {
+    // d_i = R^-T n_i (R^T is lower triangular: forward substitution, one lane per row) and beta_i = b_i + d_i . c
+    if (valid) {
+      float* d = sDm + lane * TQ_PITCH;
+      float dc = 0.f, dd = 0.f;
+      for (int k = 0; k < TI_NJ; ++k) {
+        float s;
+        if (box) s = k == jl ? (lane < TI_NJ ? -1.f : 1.f) : 0.f;
+        else s = (ar.x * sG[3 * kf][k] + ar.y * sG[3 * kf + 1][k]) + ar.z * sG[3 * kf + 2][k];
+        for (int j = 0; j < k; ++j) s -= sS[j * TI_NC + k] * d[j];
+        s = s / sDiag[k];
+        d[k] = s;
+        dc += s * sS[k * TI_NC + TI_NJ];
+        dd += s * s;
+      }
+      const float b = box ? 0.f - lim : bq - ((ar.x * sG[3 * kf][TI_NJ] + ar.y * sG[3 * kf + 1][TI_NJ]) + ar.z * sG[3 * kf + 2][TI_NJ]);
+      sBeta[lane] = b + dc; sB[lane] = b;
+      inv_d = 1.f / __fsqrt_rn(dd);
+    }
+    int q = 0, p = -1;                             // |W|; the candidate row
+    float sp = 0.f;                                // the candidate's slack; its multiplier is rebuilt with W's when it joins
+    const int max_iter = Cq.max_iter;
+    // Gram-Schmidt, twice, of d_row against the first nq columns of Q: sW = Q^T d, sZ = the rest; returns |z|^2 and |d|^2
+    auto orth = [&](int row, int nq, float& dd) -> float {
+      const float* d = sDm + row * TQ_PITCH;
+      __syncthreads();
+      if (lane < nq) { float a = 0.f; for (int i = 0; i < TI_NJ; ++i) a += sQ[lane][i] * d[i]; sW1[lane] = a; }
+      __syncthreads();
+      if (lane < TI_NJ) {
+        float z = d[lane];
+        for (int j = 0; j < TI_NJ; ++j) { if (j >= nq) break; z -= sW1[j] * sQ[j][lane]; }
+        sZ[lane] = z;
+      }
+      __syncthreads();
+      if (lane < nq) { float a = 0.f; for (int i = 0; i < TI_NJ; ++i) a += sQ[lane][i] * sZ[i]; sW[lane] = a; }
+      __syncthreads();
+      float z = 0.f;
+      if (lane < TI_NJ) {
+        z = sZ[lane];
+        for (int j = 0; j < TI_NJ; ++j) { if (j >= nq) break; z -= sW[j] * sQ[j][lane]; }
+      }
+      __syncthreads();
+      if (lane < TI_NJ) sZ[lane] = z;
+      if (lane < nq) sW[lane] += sW1[lane];
+      __syncthreads();
+      float zz = 0.f;
+      dd = 0.f;
+      for (int i = 0; i < TI_NJ; ++i) { zz += sZ[i] * sZ[i]; dd += d[i] * d[i]; }
+      return zz;
+    };
+    // column nq of Q and T from orth's result
+    auto append = [&](int row, int nq, float zz) {
+      const float rho = __fsqrt_rn(zz);
+      if (lane < TI_NJ) sQ[nq][lane] = sZ[lane] / rho;
+      if (lane < nq) sT[lane][nq] = sW[lane];
+      if (lane == 0) { sT[nq][nq] = rho; sRow[nq] = row; }
+    };
+    for (int it = 0; it <= WBC_TASKQP_MAX_ITER; ++it) {
+      if (p < 0) {
+        slacks();
+        float best = 0.f;
+        for (int i = 0; i < TQ_NROW; ++i) { const float k = sKey[i]; if (k > best) { best = k; p = i; } }
+        if (p < 0) break;                          // optimal
+        sp = sSl[p];
+      }
+      if (it >= max_iter) { status = 1; break; }
+      iters = it + 1;
+      float dd;
+      const float zz = orth(p, q, dd);
+      const bool dep = q >= TI_NJ || !(zz > TQ_DEP2 * dd);
+      // r = T^-1 Q^T d_p, then the blocking row: the smallest u_j / r_j over r_j > 0
+      {
+        float s = lane < q ? sW[lane] : 0.f;
+        for (int b = TI_NJ - 1; b >= 0; --b) {
+          if (b >= q) continue;
+          if (lane == b) sH[b] = s / sT[b][b];
+          __syncthreads();
+          if (lane < b) s -= sT[lane][b] * sH[b];
+        }
+        if (lane < q) sR[lane] = sH[lane];
+        __syncthreads();
+      }
+      float t1 = 3.402823466e38f;
+      int l = -1;
+      for (int j = 0; j < TI_NJ; ++j) {
+        if (j >= q) break;
+        const float r = sR[j];
+        if (r > 0.f) { const float t = fmaxf(sU[j], 0.f) / r; if (t < t1) { t1 = t; l = j; } }
+      }
+      if (dep && q > 0) {
+        // n_p = sum_j r_j n_j, so with W's rows tight the slack of p is sum_j r_j b_j - b_p whatever x is: the rounding of x says
+        // nothing about it. Where that is no violation (the fourth and fifth row at a pyramid's apex) p is set aside, not swapped in
+        float si = 0.f, sa = 0.f;
+        for (int j = 0; j < TI_NJ; ++j) { if (j >= q) break; const float t = sR[j] * sB[sRow[j]]; si += t; sa += fabsf(t); }
+        if (si - sB[p] >= 0.f - TQ_TOL * ((sa + fabsf(sB[p])) + sSc[p])) { skip |= 1ull << p; p = -1; continue; }
+      }
+      if (!dep && !(l >= 0 && t1 * zz < 0.f - sp)) {
+        // the full step: p joins W; x, y and u are rebuilt from W
+        append(p, q, zz);
+        inW |= 1ull << p; skip = 0;
+        ++q; p = -1;
+        __syncthreads();
+        float s = lane < q ? sBeta[sRow[lane]] : 0.f;                     // v = T^-T beta_W
+        for (int a = 0; a < TI_NJ; ++a) {
+          if (a >= q) break;
+          if (lane == a) sH[a] = s / sT[a][a];
+          __syncthreads();
+          if (lane > a && lane < q) s -= sT[a][lane] * sH[a];
+        }
+        float yv = 0.f;
+        if (lane < TI_NJ) {                                               // y = Q v, then s = y - c
+          for (int j = 0; j < TI_NJ; ++j) { if (j >= q) break; yv += sQ[j][lane] * sH[j]; }
+          yv -= sS[lane * TI_NC + TI_NJ];
+        }
+        s = lane < q ? sH[lane] : 0.f;                                    // u = T^-1 v
+        __syncthreads();
+        for (int b = TI_NJ - 1; b >= 0; --b) {
+          if (b >= q) continue;
+          if (lane == b) sU[b] = s / sT[b][b];
+          __syncthreads();
+          if (lane < b) s -= sT[lane][b] * sU[b];
+        }
+        for (int j = TI_NJ - 1; j >= 0; --j) {                            // x = R^-1 (y - c)
+          if (lane == j) sTau[j] = yv / sDiag[j];
+          __syncthreads();
+          if (lane < j) yv -= sS[lane * TI_NC + j] * sTau[j];
+        }
+        continue;
+      }
+      if (l < 0) { status = 2; break; }            // p depends on W and nothing blocks: the rows admit no point
+      // the partial step: the multipliers move by t1, row l leaves W, the columns after l are rebuilt
+      if (!dep) sp += t1 * zz;
+      __syncthreads();
+      float un = 0.f;
+      int rn = 0;
+      if (lane < q) { un = sU[lane] - t1 * sR[lane]; if (lane >= l && lane + 1 < q) { un = sU[lane + 1] - t1 * sR[lane + 1]; rn = sRow[lane + 1]; } }
+      inW &= ~(1ull << sRow[l]); skip = 0;
+      __syncthreads();
+      if (lane < q - 1) { sU[lane] = un; if (lane >= l) sRow[lane] = rn; }
+      --q;
+      __syncthreads();
+      for (int j = 0; j < TI_NJ; ++j) {
+        if (j < l) continue;
+        if (j >= q) break;
+        float d2;
+        const int row = sRow[j];
+        const float z2 = orth(row, j, d2);
+        append(row, j, fmaxf(z2, 1e-30f * d2));
+      }
+      __syncthreads();
+    }
+  }
+
+  // 6) tau_j: a joint whose limit row is in W sits on the limit exactly; every joint inside the box. Status 1, 2: the unconstrained
+  //    optimum clamped to the box. Then (nudot, lambda) of constrained forward dynamics with it, as the sibling
+  __syncthreads();
+  if (lane < TI_NJ) {
+    const float lj = lim;                          // lane j < 18 is joint j's upper row
+    float x = status == 0 ? sTau[lane] : sX0[lane];
+    if (status == 0 && ((inW >> lane) & 1ull)) x = lj;
+    if (status == 0 && ((inW >> (lane + TI_NJ)) & 1ull)) x = 0.f - lj;
+    if (any) x = fminf(fmaxf(x, 0.f - lj), lj);    // !any: no box row is violated, by any amount, at the unconstrained optimum
+    sTau[lane] = x;
+  }
+  if (lane == 0) {
+    if (status_out) status_out[e] = status;
+    if (set_out) set_out[e] = status == 0 ? (int64_t)inW : 0;
+    if (iter_out) iter_out[e] = iters;
+  }
+  __syncthreads();
+  int jq = -1;                                     // lane c < 26: the joint torque that drives column c
+  for (int q = 0; q < TI_NJ; ++q) jq = C.jcol[q] == lane ? q : jq;
+  if (lane < BD_NCOL) {
+    float a = sY[m][lane];
+    for (int q = 0; q < TI_NJ; ++q) a += sY[m + 1 + q][lane] * sTau[q];
+    sAf[lane] = a;
+  }
+  __syncthreads();
+  const int i = lane;
+  const bool row = i < m, on = row && ((act >> i) & 1u);
+  float ci = 0.f;
+  if (on) {
+    float a = 0.f;
+    for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * sAf[c];
+    ci = ((stance_acc ? stance_acc[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
+  }
+  for (int j = 0; j < m; ++j) {                    // L y = c
+    if (i == j) sV[j] = ci * sD[j];
+    __syncthreads();
+    const float yj = sV[j];
+    if (i == j) ci = yj;
+    else if (row && i > j) ci -= sA[i][j] * yj;
+  }
+  for (int j = m - 1; j >= 0; --j) {               // L^T lambda = y
+    __syncthreads();
+    if (i == j) sV[j] = ci * sD[j];
+    __syncthreads();
+    const float lj = sV[j];
+    if (row && i < j) ci -= sA[j][i] * lj;
+  }
+  __syncthreads();
+  if (lambda && row) lambda[e * m + i] = on ? sV[i] : 0.f;
+  if (lane < BD_NCOL) {
+    tau[e * BD_NCOL + lane] = jq >= 0 ? sTau[jq] : 0.f;
+    if (nudot) {
+      float a = sAf[lane];
+      for (int k = 0; k < m; ++k) a += sY[k][lane] * sV[k];
+      nudot[e * BD_NCOL + lane] = (lane < 6 || jq >= 0) ? a : 0.f;
+    }
+  }
+}
+
+// The four launches of both entry points on `stream`: the body of wbc_sim_task_inverse_dynamics, moved here when the second entry point
+// came; qp false: the sibling without inequalities (the arguments after `qp` are not read).
+static int taskid_launch(const char* who, wbc_sim* s, const int32_t* stance_bodies, int nstance, const uint8_t* active, const float* stance_acc,
+                         const int32_t* task_bodies, int ntasks, const float* task_acc, const float* task_weight, const float* nudot_ref,
+                         const wbc_taskid_weights* weights, int flags, float* tau, float* nudot, float* lambda, float* workspace, void* stream,
+                         bool qp, const wbc_taskqp_limits* limits, const float* tau_limit, const float* normal, const float* mu, int32_t* status,
+                         int64_t* active_set, int32_t* iterations) {
+  WbCall c(who, s, stream);
+  auto fin_ge0 = [](float x) { return x >= 0.f && x <= 3.402823466e38f; };   // finite: up to FLT_MAX
+  // the new entry point's own arguments first: they need no sim, so a binding can be checked without a device
+  if (qp) {
+    if (!limits) return c.fail(-1, "limits is NULL");
+    if (!(limits->mu > 0.f) || !fin_ge0(limits->mu)) return c.fail(-1, "limits.mu must be finite and > 0");
+    if (!fin_ge0(fabsf(limits->fn_min))) return c.fail(-1, "limits.fn_min must be finite");
+    if (limits->max_iter < 0 || limits->max_iter > WBC_TASKQP_MAX_ITER) return c.fail(-1, "limits.max_iter must be 0 (the default) or 1..WBC_TASKQP_MAX_ITER");
+    if ((((uintptr_t)tau_limit | (uintptr_t)normal | (uintptr_t)mu | (uintptr_t)status | (uintptr_t)iterations) & 3u) || ((uintptr_t)active_set & 7u))
+      return c.fail(-1, "tau_limit / normal / mu / status / iterations must be 4-byte aligned and active_set 8-byte aligned");
+  }
   if (!s) return c.no_sim();
   if (!tau || !workspace || !weights) return c.fail(-1, "tau / workspace / weights is NULL");
   if (nstance < 0 || nstance > WBC_TASKID_MAX_STANCE) return c.fail(-1, "nstance must be 0..WBC_TASKID_MAX_STANCE");
   if (ntasks < 0 || ntasks > WBC_TASKID_MAX_TASKS) return c.fail(-1, "ntasks must be 0..WBC_TASKID_MAX_TASKS");
   if ((nstance > 0 && !stance_bodies) || (ntasks > 0 && (!task_bodies || !task_acc)))
     return c.fail(-1, "stance_bodies / task_bodies / task_acc is NULL with a count above 0");
-  auto fin_ge0 = [](float x) { return x >= 0.f && x <= 3.402823466e38f; };   // finite: up to FLT_MAX
   if (!(weights->torque > 0.f) || !fin_ge0(weights->torque)) return c.fail(-1, "weights.torque must be finite and > 0");
   if (!fin_ge0(weights->posture) || !fin_ge0(weights->force) || !fin_ge0(weights->damping))
     return c.fail(-1, "weights.posture / force / damping must be finite and >= 0");
@@ -2042,7 +2512,8 @@ extern "C" int wbc_sim_task_inverse_dynamics(wbc_sim* s, const int32_t* stance_b
       if (C.rb_body[task_bodies[k]] == C.rb_body[task_bodies[l]])
         return c.fail(-1, "two task bodies ride on the same moving body (dependent rows)");
   tree_cols_fill(c.hc->model, C);
-  TsConst T;
+  TqConst Q;
+  TsConst& T = Q.s;
   int nj = 0;
   for (int d = 0; d < WBC_NDOF; ++d)
     if (C.col_body[d] >= 0) { if (nj < TI_NJ) C.jcol[nj] = 6 + d; ++nj; }
@@ -2067,7 +2538,42 @@ extern "C" int wbc_sim_task_inverse_dynamics(wbc_sim* s, const int32_t* stance_b
   if ((rc = c.launched()) != 0) return rc;
   rc = mass_solve_launch(c, blk, (int64_t)nr * BD_NCOL, nr, nullptr, Y, flags, stream);
   if (rc != 0) return rc;
-  hipLaunchKernelGGL(wbc_taskid_solve_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, T, (const float*)blk, (const float*)Y, (const float*)gamma,
-                     (const float*)jt, (const float*)gt, active, stance_acc, task_acc, task_weight, nudot_ref, nstance, ntasks, n, tau, nudot, lambda);
+  if (!qp) {
+    hipLaunchKernelGGL(wbc_taskid_solve_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, T, (const float*)blk, (const float*)Y, (const float*)gamma,
+                       (const float*)jt, (const float*)gt, active, stance_acc, task_acc, task_weight, nudot_ref, nstance, ntasks, n, tau, nudot, lambda);
+    return c.launched();
+  }
+  for (int q = 0; q < TI_NJ; ++q) Q.lim[q] = c.hc->cfg.torque_limits[C.jcol[q] - 6];
+  Q.mu = limits->mu; Q.fn_min = limits->fn_min; Q.max_iter = limits->max_iter > 0 ? limits->max_iter : TQ_DEFAULT_ITER;
+  hipLaunchKernelGGL(wbc_taskqp_solve_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, Q, (const float*)blk, (const float*)Y, (const float*)gamma,
+                     (const float*)jt, (const float*)gt, active, stance_acc, task_acc, task_weight, nudot_ref, tau_limit, normal, mu, nstance, ntasks, n,
+                     tau, nudot, lambda, status, active_set, iterations);
   return c.launched();
+}
+
+// Four launches on `stream`. Arguments and conventions: include/wbc_sim.h.
+extern "C" int wbc_sim_task_inverse_dynamics(wbc_sim* s, const int32_t* stance_bodies, int nstance, const uint8_t* active, const float* stance_acc,
+                                             const int32_t* task_bodies, int ntasks, const float* task_acc, const float* task_weight,
+                                             const float* nudot_ref, const wbc_taskid_weights* weights, int flags, float* tau, float* nudot,
+                                             float* lambda, float* workspace, void* stream) {
+  return taskid_launch("wbc_sim_task_inverse_dynamics", s, stance_bodies, nstance, active, stance_acc, task_bodies, ntasks, task_acc, task_weight,
+                       nudot_ref, weights, flags, tau, nudot, lambda, workspace, stream, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       nullptr);
+}
+
+// The sibling's workspace: the solve kernel keeps everything else in LDS.
+extern "C" size_t wbc_sim_task_inverse_dynamics_qp_workspace_floats(int num_envs, int nstance, int ntasks) {
+  return wbc_sim_task_inverse_dynamics_workspace_floats(num_envs, nstance, ntasks);
+}
+
+// Four launches on `stream`, the last one wbc_taskqp_solve_kernel. Arguments and conventions: include/wbc_sim.h.
+extern "C" int wbc_sim_task_inverse_dynamics_qp(wbc_sim* s, const int32_t* stance_bodies, int nstance, const uint8_t* active, const float* stance_acc,
+                                                const int32_t* task_bodies, int ntasks, const float* task_acc, const float* task_weight,
+                                                const float* nudot_ref, const wbc_taskid_weights* weights, const wbc_taskqp_limits* limits,
+                                                const float* tau_limit, const float* normal, const float* mu, int flags, float* tau, float* nudot,
+                                                float* lambda, int32_t* status, int64_t* active_set, int32_t* iterations, float* workspace,
+                                                void* stream) {
+  return taskid_launch("wbc_sim_task_inverse_dynamics_qp", s, stance_bodies, nstance, active, stance_acc, task_bodies, ntasks, task_acc,
+                       task_weight, nudot_ref, weights, flags, tau, nudot, lambda, workspace, stream, true, limits, tau_limit, normal, mu, status,
+                       active_set, iterations);
 }

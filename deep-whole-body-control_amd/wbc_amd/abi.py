@@ -105,6 +105,14 @@ class WbcTaskIdWeights(C.Structure):
     _fields_ = [("posture", f32), ("force", f32), ("torque", f32), ("damping", f32)]
 
 
+TASKQP_MAX_ITER = 128     # WBC_TASKQP_MAX_ITER
+
+
+class WbcTaskQpLimits(C.Structure):
+    """wbc_taskqp_limits (include/wbc_sim.h): the host scalars of wbc_sim_task_inverse_dynamics_qp; max_iter 0 = the default."""
+    _fields_ = [("mu", f32), ("fn_min", f32), ("max_iter", i32)]
+
+
 # enum wbc_tensor_id, same order as the header
 TENSOR_IDS = [
     "ROOT_STATES", "DOF_STATE", "NET_CONTACT_FORCE", "RIGID_BODY_STATE", "FORCE_SENSOR", "TORQUES", "OBS_BUF",

@@ -546,8 +546,16 @@ class WidowGo1(LeggedRobot):
         four) stay put. A task that is None carries no weight; a foot's task weight is 0 where it stands, so swing_acc needs a
         stance mask (it is refused with stance=None, where every foot stands). qdd_ref [N, 26]: the
         posture term's target for nudot (None: zeros). weights: dict with any of base, ee, swing (task weights, default 1), posture,
-        force, torque, damping (defaults of WbcSim.task_inverse_dynamics). No friction cones or torque limits: clamp the result.
+        force, torque, damping (defaults of WbcSim.task_inverse_dynamics). No friction cones or torque limits: clamp the result, or
+        call whole_body_controller, which solves with them.
         Returns (torques [N, 20] for sim.set_dof_forces, nudot [N, 26], foot_forces [N, 4, 3])."""
+        acc, w, scalars = self._whole_body_tasks(base_acc, ee_acc, swing_acc, stance, weights)
+        tau, nudot, lam = self.sim.task_inverse_dynamics(self._feet_list, [0, int(self.gripper_idx)] + self._feet_list, acc, w,
+                                                         active=stance, nudot_ref=qdd_ref, armature=armature, **scalars)
+        return tau[:, 6:].contiguous(), nudot, lam
+
+    def _whole_body_tasks(self, base_acc, ee_acc, swing_acc, stance, weights):
+        """(acc [N, 6, 6], w [N, 6, 6], scalar weights) of the trunk, gripper and four foot tasks of the whole-body calls."""
         if self.__dict__.get("_feet_list") is None:
             self._feet_list = [int(i) for i in self.feet_indices.tolist()]
         n, dev = self.num_envs, self.device
@@ -563,10 +571,21 @@ class WidowGo1(LeggedRobot):
             assert stance is not None, "swing_acc needs a stance mask: with stance=None all four feet stand and no foot has a swing task"
             acc[:, 2:, 0:3] = swing_acc
             w[:, 2:, 0:3] = float(wts["swing"]) * (~stance.bool()).float().unsqueeze(-1)
-        scalars = {k: float(wts[k]) for k in ("posture", "force", "torque", "damping") if k in wts}
-        tau, nudot, lam = self.sim.task_inverse_dynamics(self._feet_list, [0, int(self.gripper_idx)] + self._feet_list, acc, w,
-                                                         active=stance, nudot_ref=qdd_ref, armature=armature, **scalars)
-        return tau[:, 6:].contiguous(), nudot, lam
+        return acc, w, {k: float(wts[k]) for k in ("posture", "force", "torque", "damping") if k in wts}
+
+    def whole_body_controller(self, base_acc: torch.Tensor = None, ee_acc: torch.Tensor = None, swing_acc: torch.Tensor = None,
+                              stance: torch.Tensor = None, qdd_ref: torch.Tensor = None, weights: dict = None, armature: bool = False,
+                              mu=0.5, fn_min: float = 0.0, tau_limit: torch.Tensor = None, normal: torch.Tensor = None, max_iter: int = 0):
+        """whole_body_inverse_dynamics with the limits a robot has (include/wbc_sim.h: wbc_sim_task_inverse_dynamics_qp): the same tasks
+        and weights, solved subject to |torque| <= tau_limit [N, 18] (None: the config's torque_limits) and, for every stance foot, a
+        normal force of at least fn_min and a friction pyramid of coefficient mu (a float or [N, 4]) about normal [N, 4, 3] (None: world
+        z). Returns (torques [N, 20] for sim.set_dof_forces, nudot [N, 26], foot_forces [N, 4, 3], info) with info["status"] (0 optimal;
+        1, 2: the unconstrained optimum clamped to the torque limits), info["active_set"] and info["iterations"]."""
+        acc, w, scalars = self._whole_body_tasks(base_acc, ee_acc, swing_acc, stance, weights)
+        tau, nudot, lam, info = self.sim.task_inverse_dynamics_qp(self._feet_list, [0, int(self.gripper_idx)] + self._feet_list, acc, w,
+                                                                  active=stance, nudot_ref=qdd_ref, armature=armature, mu=mu, fn_min=fn_min,
+                                                                  tau_limit=tau_limit, normal=normal, max_iter=max_iter, **scalars)
+        return tau[:, 6:].contiguous(), nudot, lam, info
 
     # ---- centre of mass and centroidal momentum (no counterpart in the reference): one launch, include/wbc_sim.h: wbc_sim_centroidal ----
     def centre_of_mass(self):

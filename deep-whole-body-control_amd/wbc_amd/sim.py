@@ -312,7 +312,8 @@ class WbcSim:
         indices) the accelerations task_acc [N, T, 6] (linear, angular; per-row weights task_weight [N, T, 6] >= 0, None: ones) while
         the origins of stance_bodies (0..4 indices) keep the linear accelerations stance_acc [N, K, 3] (None: zeros) where active
         [N, K] (bool or uint8; None: all), in the weighted least-squares sense of include/wbc_sim.h with the scalar weights posture
-        (towards nudot_ref [N, 26], None: zeros), force, torque (> 0) and the Delassus damping. No inequalities: clamp the result.
+        (towards nudot_ref [N, 26], None: zeros), force, torque (> 0) and the Delassus damping. No inequalities: clamp the result, or
+        call task_inverse_dynamics_qp, which solves with torque limits and friction pyramids.
         Returns (tau [N, 26], nudot [N, 26], lam [N, K, 3]): tau[:, 6:] is what set_dof_forces takes, rows 0:6 and the fingers are
         exactly 0. out: an optional (tau, nudot, lam) triple to fill. The workspace is cached per (K, T)."""
         n, ncol = self.num_envs, 6 + abi.NDOF
@@ -348,6 +349,62 @@ class WbcSim:
                                                    C.byref(w), 1 if armature else 0, tau.data_ptr(), nudot.data_ptr(), ptr(lam),
                                                    cache[(k, t)].data_ptr(), self._stream()), "wbc_sim_task_inverse_dynamics")
         return tau, nudot, lam
+
+    # ---- the same with torque limits and friction pyramids (include/wbc_sim.h: wbc_sim_task_inverse_dynamics_qp) -----------------------
+    def task_inverse_dynamics_qp(self, stance_bodies=(), task_bodies=(), task_acc: Optional[torch.Tensor] = None,
+                                 task_weight: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,
+                                 stance_acc: Optional[torch.Tensor] = None, nudot_ref: Optional[torch.Tensor] = None,
+                                 posture: float = 1e-2, force: float = 1e-4, torque: float = 1e-3, damping: float = 0.0,
+                                 armature: bool = False, mu=0.5, fn_min: float = 0.0, tau_limit: Optional[torch.Tensor] = None,
+                                 normal: Optional[torch.Tensor] = None, max_iter: int = 0, out=None):
+        """wbc_sim_task_inverse_dynamics_qp on the current stream: task_inverse_dynamics' problem and arguments, further subject to
+        |tau_j| <= tau_limit [N, 18] (None: the config's torque_limits of the 18 revolute joints, in the order of tau[:, 6:24]) and, per
+        active stance body, normal force >= fn_min and the friction pyramid |t . lam| <= mu n . lam along two tangents (mu: a float, or
+        a tensor [N, K]; normal [N, K, 3], None: world z; tangent rule in include/wbc_sim.h). max_iter: 0 = the default, at most
+        abi.TASKQP_MAX_ITER. Returns (tau [N, 26], nudot [N, 26], lam [N, K, 3], info): info["status"] int32 [N] (0 optimal, 1 the
+        iteration cap, 2 no point satisfies the rows; 1 and 2 carry the unconstrained optimum clamped to the box), info["active_set"]
+        int64 [N] (bits: header) and info["iterations"] int32 [N]. out: an optional (tau, nudot, lam, status, active_set, iterations)
+        tuple to fill. The workspace is cached per (K, T) and shared with nothing else."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        srb = [int(r) for r in (stance_bodies.tolist() if isinstance(stance_bodies, torch.Tensor) else stance_bodies)]
+        trb = [int(r) for r in (task_bodies.tolist() if isinstance(task_bodies, torch.Tensor) else task_bodies)]
+        k, t = len(srb), len(trb)
+        assert 0 <= k <= 4 and 0 <= t <= 6, (k, t)
+        assert t == 0 or task_acc is not None, "task_acc is needed with task bodies"
+        tau, nudot, lam, status, aset, iters = out if out is not None else (None,) * 6
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.device)
+        tau = new((n, ncol), torch.float32) if tau is None else tau
+        nudot = new((n, ncol), torch.float32) if nudot is None else nudot
+        lam = new((n, k, 3), torch.float32) if lam is None else lam
+        status = new((n,), torch.int32) if status is None else status
+        aset = new((n,), torch.int64) if aset is None else aset
+        iters = new((n,), torch.int32) if iters is None else iters
+        mu_t = mu if isinstance(mu, torch.Tensor) else None
+        for x, shape, dtype in ((task_acc, (n, t, 6), torch.float32), (task_weight, (n, t, 6), torch.float32), (stance_acc, (n, k, 3), torch.float32),
+                                (nudot_ref, (n, ncol), torch.float32), (tau, (n, ncol), torch.float32), (nudot, (n, ncol), torch.float32),
+                                (lam, (n, k, 3), torch.float32), (tau_limit, (n, abi.NJ), torch.float32), (normal, (n, k, 3), torch.float32),
+                                (mu_t, (n, k), torch.float32), (status, (n,), torch.int32), (aset, (n,), torch.int64), (iters, (n,), torch.int32)):
+            if x is not None:
+                assert x.device == self.arena.device and x.dtype == dtype and x.is_contiguous() and tuple(x.shape) == shape, tuple(x.shape)
+        if active is not None:
+            assert active.device == self.arena.device and active.dtype in (torch.bool, torch.uint8) and tuple(active.shape) == (n, k)
+            active = active.contiguous()
+            if active.dtype == torch.bool:
+                active = active.view(torch.uint8)
+        cache = self.__dict__.setdefault("_taskqp_ws", {})
+        if (k, t) not in cache:
+            cache[(k, t)] = torch.empty(int(self.L.wbc_sim_task_inverse_dynamics_qp_workspace_floats(n, k, t)), dtype=torch.float32,
+                                        device=self.device)
+        ptr = lambda x: x.data_ptr() if x is not None and x.numel() > 0 else None
+        w = abi.WbcTaskIdWeights(float(posture), float(force), float(torque), float(damping))
+        lim = abi.WbcTaskQpLimits(1.0 if mu_t is not None else float(mu), float(fn_min), int(max_iter))
+        check(self.L.wbc_sim_task_inverse_dynamics_qp(self.h, (C.c_int32 * max(k, 1))(*srb), k, ptr(active), ptr(stance_acc),
+                                                      (C.c_int32 * max(t, 1))(*trb), t, ptr(task_acc), ptr(task_weight), ptr(nudot_ref),
+                                                      C.byref(w), C.byref(lim), ptr(tau_limit), ptr(normal), ptr(mu_t), 1 if armature else 0,
+                                                      tau.data_ptr(), nudot.data_ptr(), ptr(lam), status.data_ptr(), aset.data_ptr(),
+                                                      iters.data_ptr(), cache[(k, t)].data_ptr(), self._stream()),
+              "wbc_sim_task_inverse_dynamics_qp")
+        return tau, nudot, lam, {"status": status, "active_set": aset, "iterations": iters}
 
     # ---- centre of mass, centroidal momentum and its matrix (include/wbc_sim.h: wbc_sim_centroidal) ----------------------------------
     def centroidal(self, nudot: Optional[torch.Tensor] = None, com: Optional[torch.Tensor] = None, mom: Optional[torch.Tensor] = None,

@@ -717,7 +717,7 @@ int wbc_sim_constrained_dynamics(wbc_sim* sim, const int32_t* rigid_bodies /* ho
  *         J_r nudot + (Jdot nu)_r = stance_acc_r - damping lambda_r      for every ACTIVE stance body r (three linear rows)
  * tau_j are the 18 revolute joint torques; the locked fingers' entries are exactly 0 everywhere. torque > 0 makes the solution unique
  * for every stance pattern. NO INEQUALITIES are offered: no friction cones, no unilateral contact and no torque limits -- a caller
- * clamps the result, or raises `force` / `torque`.
+ * clamps the result, or raises `force` / `torque`, or calls wbc_sim_task_inverse_dynamics_qp below, which solves with them.
  * stance_bodies  HOST array of nstance (0..WBC_TASKID_MAX_STANCE) rigid-body indices, e.g. the four feet.
  * active      device u8 [N, nstance] or NULL (= all active). An inactive body contributes no constraint, its lambda is exactly 0 and
  *             its stance_acc is never read (a NaN there does not spread).
@@ -757,6 +757,45 @@ int wbc_sim_task_inverse_dynamics(wbc_sim* sim, const int32_t* stance_bodies /* 
                                   const float* stance_acc, const int32_t* task_bodies /* host */, int ntasks, const float* task_acc,
                                   const float* task_weight, const float* nudot_ref, const wbc_taskid_weights* weights /* host */,
                                   int flags, float* tau, float* nudot, float* lambda, float* workspace, void* stream);
+
+/* wbc_sim_task_inverse_dynamics with torque limits and friction pyramids: the problem, arguments, conventions, launches 1-3 and the
+ * workspace rules are that call's (the size comes from wbc_sim_task_inverse_dynamics_qp_workspace_floats); per env the minimisation is
+ * further subject to
+ *     |tau_j| <= tau_limit[j]                                            the 18 revolute joints, in the order of tau[:, 6:24]
+ *     n_k . lambda_k >= fn_min                                           for every ACTIVE stance body k, lambda_k the force applied TO
+ *     +-t1_k . lambda_k <= mu_k n_k . lambda_k                           the robot: a friction pyramid, and unilateral contact for
+ *     +-t2_k . lambda_k <= mu_k n_k . lambda_k                           fn_min >= 0
+ * tau_limit  device f32 [N, 18] or NULL (= wbc_task_cfg.torque_limits of those DoFs).
+ * normal     device f32 [N, nstance, 3], normalised by the kernel, or NULL (= world z). mu: device f32 [N, nstance] or NULL (=
+ *            limits.mu). TANGENTS: with a NULL normal t1 = world x, t2 = world y; otherwise t1 = normalise(n x e) with e = world x, or
+ *            world y where |n_x| > 0.9, and t2 = n x t1. An inactive stance body has no rows; its mu and normal are never read.
+ * limits     HOST struct: mu > 0 and finite; fn_min finite; max_iter 1..WBC_TASKQP_MAX_ITER, 0 = the default (100).
+ * tau, nudot, lambda  as in the sibling: after the solve (nudot, lambda) are recomputed from tau_j by constrained forward dynamics.
+ *            |tau_j| <= tau_limit[j] holds exactly in fp32, and a joint reported at a limit equals that limit bit for bit.
+ * status     device i32 [N] or NULL: 0 optimal; 1 the iteration cap was reached; 2 the inequalities admit no point.
+ * active_set device i64 [N] or NULL, for status 0: bit j: tau_j at +limit; bit 18 + j: tau_j at -limit; bit 36 + 5 k + {0: the normal
+ *            row, 1: +t1, 2: -t1, 3: +t2, 4: -t2} of stance body k. iterations: device i32 [N] or NULL: the steps taken (a row
+ *            added, a row dropped, or a dependent candidate set aside).
+ * Status 1 or 2: tau_j is the unconstrained optimum clamped to the box (what a caller of the sibling is told to do), (nudot, lambda)
+ * are recomputed from it and active_set is 0. Where no row is violated at the unconstrained optimum the outputs are the sibling's bit
+ * for bit, status 0, active_set 0, iterations 0.
+ * Method (wbc_taskqp_solve_kernel, the fourth launch, one env per 64-lane workgroup): with R, c of the sibling's reflected stack,
+ * min 1/2 |R tau_j + c|^2 over the rows above (linear in tau_j through lambda = lambda_0 + G_lambda tau_j) by the dual active-set
+ * method of Goldfarb and Idnani started from the unconstrained optimum; the iterate and the multipliers are rebuilt from the working
+ * set after every accepted row. Every loop has a compile-time bound.
+ * Non-finite or non-positive tau_limit or mu, or a zero normal, of an env: that env's outputs are unspecified, no other env is affected.
+ * -1 with a message in wbc_last_error(), nothing written: everything the sibling refuses; a NULL limits; a limits field out of range; a
+ * tau_limit / normal / mu / status / iterations that is not 4-byte aligned or an active_set that is not 8-byte aligned.
+ * flags: 0 or WBC_SOLVE_ARMATURE. Out of scope: warm starts, second-order cones, a largest normal force, limits on accelerations. */
+#define WBC_TASKQP_MAX_ITER 128
+typedef struct { float mu, fn_min; int32_t max_iter; } wbc_taskqp_limits;
+size_t wbc_sim_task_inverse_dynamics_qp_workspace_floats(int num_envs, int nstance, int ntasks);
+int wbc_sim_task_inverse_dynamics_qp(wbc_sim* sim, const int32_t* stance_bodies /* host */, int nstance, const uint8_t* active,
+                                     const float* stance_acc, const int32_t* task_bodies /* host */, int ntasks, const float* task_acc,
+                                     const float* task_weight, const float* nudot_ref, const wbc_taskid_weights* weights /* host */,
+                                     const wbc_taskqp_limits* limits /* host */, const float* tau_limit, const float* normal, const float* mu,
+                                     int flags, float* tau, float* nudot, float* lambda, int32_t* status, int64_t* active_set,
+                                     int32_t* iterations, float* workspace, void* stream);
 
 /* Centre of mass, centroidal momentum, its rate, the centroidal momentum matrix and the locked centroidal inertia of the robot, in the
  * coordinates of wbc_sim_body_dynamics (nu = (v_root, omega_root, qd), world axes, 26 columns) with the inertias of the per-env
