@@ -9,6 +9,7 @@
 #include <cstdio>
 
 #include "wbc_device.h"
+#include "wbc_delassus.h"
 #include "wbc_stream_guard.h"
 #include "wbc_tree.h"
 
@@ -1012,6 +1013,39 @@ struct CdConst : TreeWalk, TreeRigid, TreeCols {
   int32_t nb, rb[WBC_CONSTR_MAX_BODIES];       // the listed rigid bodies
 };
 
+// The walk phase of the two right-hand-side kernels, one lane (W and B: the bases of the kernel's argument struct): lane b < 19 = moving
+// body b leaves its joint axis and origin (F) in sJ[b]; a lane past them walks to listed body k (rigid body r), leaves its origin in
+// sX[k] and returns true with the body's Jdot nu in world axes: lin of its origin, ang.
+__device__ __forceinline__ bool rhs_walk_lane(const TreeWalk& W, const TreeRigid& B, int lane, int k, int r, size_t e, const float* R,
+                                              const float* __restrict__ root, const float* __restrict__ dofs, float (*sJ)[6], float (*sX)[3],
+                                              f3& lin, f3& ang) {
+  const bool body = lane < WBC_NB;
+  const int b = body ? lane : B.rb_body[r];
+  float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+  f3 p, w, aw, ao;
+  ba_walk(W, b, e, R, root, dofs, nullptr, E, p, w, aw, ao);
+  if (body) {
+    st3(sJ[b], mat_mul(E, tree_axis(W.axis[b])));    // -1 for the root: no joint axis
+    st3(sJ[b] + 3, p);
+    return false;
+  }
+  const f3 xo = mat_mul(E, mk3(B.rb_offset[r][0], B.rb_offset[r][1], B.rb_offset[r][2]));
+  st3(sX[k], p + xo);
+  lin = mat_mul(R, ao + cross(aw, xo) + cross(w, cross(w, xo)));
+  ang = mat_mul(R, aw);
+  return true;
+}
+
+// Column c's entry of the three linear Jacobian rows of a rigid body that rides on moving body lb with its origin at x (F): b the moving
+// body column c drives (-1: none), ej the unit vector of a root column.
+__device__ __forceinline__ f3 rhs_jac_lin(const TreeCols& C, int c, int b, int lb, f3 ej, const float* R, f3 x, const float (*sJ)[6]) {
+  f3 lin = mk3(0.f, 0.f, 0.f);
+  if (c < 3) lin = ej;                                   // v_root: identity
+  else if (c < 6) lin = cross(ej, mat_mul(R, x));        // omega_root: e_j x (origin relative to the root, world axes)
+  else if (b >= 0 && ((C.anc[lb] >> b) & 1u)) lin = mat_mul(R, cross(ld3(sJ[b]), x - ld3(sJ[b] + 3)));
+  return lin;
+}
+
 // The right-hand-side block of the solve, [N, 3 nb + 1, 26]: rows 3k..3k+2 the linear Jacobian rows of listed body k (zeros where it
 // is inactive), the last row tau - h; and gamma [N, CD_GSTRIDE] = (Jdot nu) of those rows. Lane b < 19 = moving body b leaves its joint
 // axis and origin (F) in LDS, lane 19 + k walks to listed body k and leaves its origin; then lane c = column c writes its entry of
@@ -1031,34 +1065,19 @@ extern "C" __global__ void __launch_bounds__(64) wbc_constraint_rhs_kernel(CdCon
   float R[9];
   quat_to_mat(root + e * 26 + 3, R);
   if (lane < WBC_NB + nb) {
-    const bool body = lane < WBC_NB;
-    const int k = body ? 0 : lane - WBC_NB, r = C.rb[k], b = body ? lane : C.rb_body[r];
-    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-    f3 p, w, aw, ao;
-    ba_walk(C, b, e, R, root, dofs, nullptr, E, p, w, aw, ao);
-    if (body) {
-      st3(sJ[half][b], mat_mul(E, tree_axis(C.axis[b])));    // -1 for the root: no joint axis
-      st3(sJ[half][b] + 3, p);
-    } else {
-      const f3 xo = mat_mul(E, mk3(C.rb_offset[r][0], C.rb_offset[r][1], C.rb_offset[r][2]));
-      st3(sX[half][k], p + xo);
-      if (live) st3(gamma + e * CD_GSTRIDE + 3 * k, mat_mul(R, ao + cross(aw, xo) + cross(w, cross(w, xo))));
-    }
+    const int k = lane < WBC_NB ? 0 : lane - WBC_NB;
+    f3 lin, ang;
+    if (rhs_walk_lane(C, C, lane, k, C.rb[k], e, R, root, dofs, sJ[half], sX[half], lin, ang) && live) st3(gamma + e * CD_GSTRIDE + 3 * k, lin);
   }
   __syncthreads();
   if (lane < BD_NCOL && live) {
     const int c = lane, b = c < 6 ? 0 : C.col_body[c - 6], j = c < 3 ? c : c - 3;
+    const f3 ej = mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f);
     float* o = rhs + e * (size_t)(nrow * BD_NCOL) + c;
     for (int k = 0; k < nb; ++k) {
       const bool act = active ? active[e * nb + k] != 0 : true;
-      const f3 x = ld3(sX[half][k]);
       f3 lin = mk3(0.f, 0.f, 0.f);
-      if (act) {
-        const f3 ej = mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f);
-        if (c < 3) lin = ej;                                 // v_root: identity
-        else if (c < 6) lin = cross(ej, mat_mul(R, x));      // omega_root: e_j x (origin relative to the root, world axes)
-        else if (b >= 0 && ((C.anc[C.rb_body[C.rb[k]]] >> b) & 1u)) lin = mat_mul(R, cross(ld3(sJ[half][b]), x - ld3(sJ[half][b] + 3)));
-      }
+      if (act) lin = rhs_jac_lin(C, c, b, C.rb_body[C.rb[k]], ej, R, ld3(sX[half][k]), sJ[half]);
       o[(3 * k) * BD_NCOL] = lin.x; o[(3 * k + 1) * BD_NCOL] = lin.y; o[(3 * k + 2) * BD_NCOL] = lin.z;
     }
     o[3 * nb * BD_NCOL] = b >= 0 ? (tau ? tau[e * BD_NCOL + c] : 0.f) - h[e * BD_NCOL + c] : 0.f;
@@ -1069,7 +1088,8 @@ extern "C" __global__ void __launch_bounds__(64) wbc_constraint_rhs_kernel(CdCon
 // A = J Y^T + damping I from its lower triangle (one entry per lane and round), identity rows and columns where a body is inactive;
 // c = a_des - gamma - J a_free; Cholesky A = L L^T in LDS, lane i = row i, one column per round (left-looking: row i meets row j only);
 // the two triangular solves with lane i holding entry i and the pivot's value handed round through LDS; nudot = a_free + Y^T lambda,
-// lane c = column c. A single-wavefront workgroup: the __syncthreads() order the LDS traffic and cost no barrier instruction.
+// lane c = column c. The fill, the factor and the solves are wbc_delassus.h's, on this half's views of the LDS arrays. A single-wavefront
+// workgroup: the __syncthreads() order the LDS traffic and cost no barrier instruction.
 extern "C" __global__ void __launch_bounds__(64) wbc_constraint_solve_kernel(const float* __restrict__ rhs, const float* __restrict__ Y,
                                                                             const float* __restrict__ gamma,
                                                                             const uint8_t* __restrict__ active,
@@ -1098,15 +1118,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_constraint_solve_kernel(con
     if (!active || active[e * nb + k]) act |= 7u << (3 * k);
   __syncthreads();
 
-  for (int t = lane; t < m * (m + 1) / 2; t += BA_LPE) {
-    int i = (int)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);              // t = i (i + 1) / 2 + j, j <= i
-    i = i * (i + 1) / 2 > t ? i - 1 : ((i + 1) * (i + 2) / 2 <= t ? i + 1 : i);
-    const int j = t - i * (i + 1) / 2;
-    float a = 0.f;
-    for (int c = 0; c < BD_NCOL; ++c) a += J[i][c] * Yt[j][c];
-    const bool on = ((act >> i) & 1u) && ((act >> j) & 1u);
-    A[i][j] = on ? (i == j ? a + damping : a) : (i == j ? 1.f : 0.f);
-  }
+  delassus_fill(J, Yt, A, m, act, damping, lane, BA_LPE);
   const int i = lane;
   const bool row = i < m, on = row && ((act >> i) & 1u);
   float ci = 0.f;
@@ -1115,33 +1127,8 @@ extern "C" __global__ void __launch_bounds__(64) wbc_constraint_solve_kernel(con
     for (int c = 0; c < BD_NCOL; ++c) a += J[i][c] * Yt[m][c];
     ci = ((acc_des ? acc_des[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
   }
-  for (int j = 0; j < m; ++j) {
-    __syncthreads();
-    float d = A[j][j];
-    for (int k = 0; k < j; ++k) d -= A[j][k] * A[j][k];
-    const float id = 1.f / __fsqrt_rn(d);
-    if (row && i > j) {
-      float s = A[i][j];
-      for (int k = 0; k < j; ++k) s -= A[i][k] * A[j][k];
-      A[i][j] = s * id;
-    }
-    if (i == j) D[j] = id;
-  }
-  for (int j = 0; j < m; ++j) {                    // L y = c
-    if (i == j) V[j] = ci * D[j];
-    __syncthreads();
-    const float yj = V[j];
-    if (i == j) ci = yj;
-    else if (row && i > j) ci -= A[i][j] * yj;
-  }
-  for (int j = m - 1; j >= 0; --j) {               // L^T lambda = y
-    __syncthreads();
-    if (i == j) V[j] = ci * D[j];
-    __syncthreads();
-    const float lj = V[j];
-    if (row && i < j) ci -= A[j][i] * lj;
-  }
-  __syncthreads();
+  delassus_cholesky(A, D, m, i);
+  delassus_lane_solve(A, D, V, m, i, ci);
   if (!live) return;
   if (lambda && row) lambda[e * m + i] = on ? V[i] : 0.f;
   if (lane < BD_NCOL) {
@@ -1738,22 +1725,11 @@ extern "C" __global__ void __launch_bounds__(64) wbc_taskid_rhs_kernel(TiConst C
   quat_to_mat(root + e * 26 + 3, R);
   if (lane < WBC_NB + ns + nt) {
     const bool body = lane < WBC_NB;
-    const int k = body ? 0 : lane - WBC_NB;
-    const int r = body ? 0 : (k < ns ? C.srb[k] : C.trb[k - ns]), b = body ? lane : C.rb_body[r];
-    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-    f3 p, w, aw, ao;
-    ba_walk(C, b, e, R, root, dofs, nullptr, E, p, w, aw, ao);
-    if (body) {
-      st3(sJ[half][b], mat_mul(E, tree_axis(C.axis[b])));    // -1 for the root: no joint axis
-      st3(sJ[half][b] + 3, p);
-    } else {
-      const f3 xo = mat_mul(E, mk3(C.rb_offset[r][0], C.rb_offset[r][1], C.rb_offset[r][2]));
-      st3(sX[half][k], p + xo);
-      const f3 lin = mat_mul(R, ao + cross(aw, xo) + cross(w, cross(w, xo)));
-      if (live) {
-        if (k < ns) st3(gamma + e * CD_GSTRIDE + 3 * k, lin);
-        else { st3(gt + e * TI_MAXT + 6 * (k - ns), lin); st3(gt + e * TI_MAXT + 6 * (k - ns) + 3, mat_mul(R, aw)); }
-      }
+    const int k = body ? 0 : lane - WBC_NB, r = body ? 0 : (k < ns ? C.srb[k] : C.trb[k - ns]);
+    f3 lin, ang;
+    if (rhs_walk_lane(C, C, lane, k, r, e, R, root, dofs, sJ[half], sX[half], lin, ang) && live) {
+      if (k < ns) st3(gamma + e * CD_GSTRIDE + 3 * k, lin);
+      else { st3(gt + e * TI_MAXT + 6 * (k - ns), lin); st3(gt + e * TI_MAXT + 6 * (k - ns) + 3, ang); }
     }
   }
   __syncthreads();
@@ -1763,13 +1739,8 @@ extern "C" __global__ void __launch_bounds__(64) wbc_taskid_rhs_kernel(TiConst C
     float* o = rhs + e * (size_t)(nr * BD_NCOL) + c;
     for (int k = 0; k < ns; ++k) {
       const bool act = active ? active[e * ns + k] != 0 : true;
-      const f3 x = ld3(sX[half][k]);
       f3 lin = mk3(0.f, 0.f, 0.f);
-      if (act) {
-        if (c < 3) lin = ej;                                 // v_root: identity
-        else if (c < 6) lin = cross(ej, mat_mul(R, x));      // omega_root: e_j x (origin relative to the root, world axes)
-        else if (b >= 0 && ((C.anc[C.rb_body[C.srb[k]]] >> b) & 1u)) lin = mat_mul(R, cross(ld3(sJ[half][b]), x - ld3(sJ[half][b] + 3)));
-      }
+      if (act) lin = rhs_jac_lin(C, c, b, C.rb_body[C.srb[k]], ej, R, ld3(sX[half][k]), sJ[half]);
       o[(3 * k) * BD_NCOL] = lin.x; o[(3 * k + 1) * BD_NCOL] = lin.y; o[(3 * k + 2) * BD_NCOL] = lin.z;
     }
     o[m * BD_NCOL] = b >= 0 ? 0.f - h[e * BD_NCOL + c] : 0.f;
@@ -1797,219 +1768,10 @@ struct TsConst {
   float sp, sf, st, damping;                   // sqrt of the posture, force and torque weights; the Delassus damping
 };
 
-// One env per 64-lane workgroup. With m = 3 ns, Y = (M^-1 [J_c^T | -h | S^T])^T the mass solve's output and S the stack in LDS:
-//  1) A = J_c Y_c^T + damping I (lower triangle, identity where inactive) and, in the stack's force rows, [-J_c Y_s^T | a_stance - gamma
-//     - J_c y_h]; Cholesky of A as wbc_constraint_solve_kernel; lane j = column j solves its column in place: [G_lambda | lambda_0];
-//  2) posture rows [G_a | a_0] = [Y_s^T | y_h] + Y_c^T [G_lambda | lambda_0] on the live coordinates; task rows sqrt(w) (J_t [G_a | a_0] +
-//     (0 | Jdot nu - acc)), zero where w = 0 (acc is not read there); then the posture rows lose nudot_ref and take sqrt(w_posture),
-//     the force rows sqrt(w_force), and the torque rows are sqrt(w_torque) I: w_torque > 0 gives the stack full column rank;
-//  3) 18 Householder reflections, lane = group * 19 + column: three groups share the rows of a column's dot product with the pivot
-//     column (rows k + group, step 3: 57 consecutive LDS words per read), partial sums meet in LDS. The pivot column is left as it
-//     is (its reflected value alpha goes to sDiag), so no lane writes what another reads;
-//  4) R tau_j = -(Q^T b) by back-substitution, then a_free = y_h + Y_s^T tau_j and the tail of wbc_constraint_solve_kernel.
-// A single-wavefront workgroup: the __syncthreads() order the LDS traffic and cost no barrier instruction.
-extern "C" __global__ void __launch_bounds__(64) wbc_taskid_solve_kernel(TsConst C, const float* __restrict__ rhs, const float* __restrict__ Y,
-                                                                        const float* __restrict__ gamma, const float* __restrict__ jt,
-                                                                        const float* __restrict__ gt, const uint8_t* __restrict__ active,
-                                                                        const float* __restrict__ stance_acc, const float* __restrict__ task_acc,
-                                                                        const float* __restrict__ task_weight, const float* __restrict__ nudot_ref,
-                                                                        int ns, int nt, int n, float* __restrict__ tau, float* __restrict__ nudot,
-                                                                        float* __restrict__ lambda) {
-  __shared__ float sY[TI_MAXRHS][CD_LD], sJc[TI_MAXS][CD_LD], sJt[TI_MAXT][CD_LD];
-  __shared__ float sS[TI_MAXROWS * TI_NC];         // the stack, row-major, pitch 19
-  __shared__ float sA[TI_MAXS][TI_MAXS + 1];       // lower triangle: A, then L
-  __shared__ float sD[TI_MAXS + 1], sV[TI_MAXS + 1];   // 1 / L_jj; the value handed round
-  __shared__ float sP[TI_QG][TI_NC], sDiag[TI_NJ], sTau[TI_NJ], sAf[BD_NCOL];
-  const int lane = threadIdx.x;
-  if ((int)blockIdx.x >= n) return;
-  const size_t e = blockIdx.x;
-  const int m = 3 * ns, mt = 6 * nt, nr = m + 1 + TI_NJ;
-  const int F0 = TI_NL, T0 = F0 + m, Q0 = T0 + mt, nrow = Q0 + TI_NJ;
-  const float *rp = rhs + e * (size_t)(nr * BD_NCOL), *yp = Y + e * (size_t)(nr * BD_NCOL), *jp = jt + e * (size_t)(mt * BD_NCOL);
-  for (int t = lane; t < nr * BD_NCOL; t += 64) {
-    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
-    sY[r][c] = yp[t];
-    if (r < m) sJc[r][c] = rp[t];
-  }
-  for (int t = lane; t < mt * BD_NCOL; t += 64) {
-    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
-    sJt[r][c] = jp[t];
-  }
-  uint32_t act = 0;                                // bit i: row i belongs to an active stance body
-  for (int k = 0; k < ns; ++k)
-    if (!active || active[e * ns + k]) act |= 7u << (3 * k);
-  __syncthreads();
-
-  // 1) the Delassus matrix and the 19 right-hand sides of its factor
-  for (int t = lane; t < m * (m + 1) / 2; t += 64) {
-    int i = (int)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);              // t = i (i + 1) / 2 + j, j <= i
-    i = i * (i + 1) / 2 > t ? i - 1 : ((i + 1) * (i + 2) / 2 <= t ? i + 1 : i);
-    const int j = t - i * (i + 1) / 2;
-    float a = 0.f;
-    for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * sY[j][c];
-    const bool on = ((act >> i) & 1u) && ((act >> j) & 1u);
-    sA[i][j] = on ? (i == j ? a + C.damping : a) : (i == j ? 1.f : 0.f);
-  }
-  for (int t = lane; t < m * TI_NC; t += 64) {
-    const int i = t / TI_NC, j = t - i * TI_NC;
-    float v = 0.f;
-    if ((act >> i) & 1u) {
-      const float* y = sY[j < TI_NJ ? m + 1 + j : m];
-      float a = 0.f;
-      for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * y[c];
-      v = j < TI_NJ ? 0.f - a : ((stance_acc ? stance_acc[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
-    }
-    sS[(F0 + i) * TI_NC + j] = v;
-  }
-  {
-    const int i = lane;
-    const bool row = i < m;
-    for (int j = 0; j < m; ++j) {
-      __syncthreads();
-      float d = sA[j][j];
-      for (int k = 0; k < j; ++k) d -= sA[j][k] * sA[j][k];
-      const float id = 1.f / __fsqrt_rn(d);
-      if (row && i > j) {
-        float s = sA[i][j];
-        for (int k = 0; k < j; ++k) s -= sA[i][k] * sA[j][k];
-        sA[i][j] = s * id;
-      }
-      if (i == j) sD[j] = id;
-    }
-  }
-  __syncthreads();
-  if (lane < TI_NC) {                              // L L^T x = column `lane`, in place
-    float* x = sS + F0 * TI_NC + lane;
-    for (int i = 0; i < m; ++i) {
-      float s = x[i * TI_NC];
-      for (int k = 0; k < i; ++k) s -= sA[i][k] * x[k * TI_NC];
-      x[i * TI_NC] = s * sD[i];
-    }
-    for (int i = m - 1; i >= 0; --i) {
-      float s = x[i * TI_NC];
-      for (int k = i + 1; k < m; ++k) s -= sA[k][i] * x[k * TI_NC];
-      x[i * TI_NC] = s * sD[i];
-    }
-  }
-  __syncthreads();
-
-  // 2) the stack
-  for (int t = lane; t < TI_NL * TI_NC; t += 64) {
-    const int s = t / TI_NC, j = t - s * TI_NC, c = C.lcol[s];
-    float a = sY[j < TI_NJ ? m + 1 + j : m][c];
-    for (int k = 0; k < m; ++k) a += sY[k][c] * sS[(F0 + k) * TI_NC + j];
-    sS[t] = a;
-  }
-  __syncthreads();
-  for (int t = lane; t < mt * TI_NC; t += 64) {
-    const int r = t / TI_NC, j = t - r * TI_NC;
-    const float w = task_weight ? task_weight[e * mt + r] : 1.f;
-    float v = 0.f;
-    if (w > 0.f) {
-      float a = 0.f;
-      for (int s = 0; s < TI_NL; ++s) a += sJt[r][C.lcol[s]] * sS[s * TI_NC + j];
-      if (j == TI_NJ) a += gt[e * TI_MAXT + r] - task_acc[e * mt + r];
-      v = __fsqrt_rn(w) * a;
-    }
-    sS[(T0 + r) * TI_NC + j] = v;
-  }
-  __syncthreads();
-  for (int t = lane; t < TI_NL * TI_NC; t += 64) {
-    const int s = t / TI_NC, j = t - s * TI_NC;
-    const float ref = (j == TI_NJ && nudot_ref) ? nudot_ref[e * BD_NCOL + C.lcol[s]] : 0.f;
-    sS[t] = C.sp * (sS[t] - ref);
-  }
-  for (int t = lane; t < m * TI_NC; t += 64) sS[F0 * TI_NC + t] *= C.sf;
-  for (int t = lane; t < TI_NJ * TI_NC; t += 64) {
-    const int i = t / TI_NC, j = t - i * TI_NC;
-    sS[Q0 * TI_NC + t] = i == j ? C.st : 0.f;
-  }
-  __syncthreads();
-
-  // 3) Householder reflections
-  {
-    const int g = lane / TI_NC, j = lane - g * TI_NC;
-    const bool mine = g < TI_QG;
-    for (int k = 0; k < TI_NJ; ++k) {
-      if (mine) {
-        float part = 0.f;
-        if (j >= k)
-          for (int r = k + g; r < nrow; r += TI_QG) part += sS[r * TI_NC + k] * sS[r * TI_NC + j];
-        sP[g][j] = part;
-      }
-      __syncthreads();
-      const float skk = (sP[0][k] + sP[1][k]) + sP[2][k], akk = sS[k * TI_NC + k];
-      const float nrm = __fsqrt_rn(skk), alpha = akk >= 0.f ? 0.f - nrm : nrm, vk = akk - alpha;
-      float tj = 0.f;                              // 2 (v . a_j) / (v . v), v = a_k - alpha e_k: v . v = -2 alpha v_k
-      if (mine && j > k) tj = (((sP[0][j] + sP[1][j]) + sP[2][j]) - alpha * sS[k * TI_NC + j]) * (-1.f / (alpha * vk));
-      __syncthreads();
-      if (mine && j > k)
-        for (int r = k + g; r < nrow; r += TI_QG) sS[r * TI_NC + j] -= tj * (r == k ? vk : sS[r * TI_NC + k]);
-      if (lane == k) sDiag[k] = alpha;
-      __syncthreads();
-    }
-  }
-
-  // 4) tau_j, then (nudot, lambda) of constrained forward dynamics with it
-  for (int k = TI_NJ - 1; k >= 0; --k) {
-    float x = 0.f - sS[k * TI_NC + TI_NJ];
-    for (int j = k + 1; j < TI_NJ; ++j) x -= sS[k * TI_NC + j] * sTau[j];
-    if (lane == 0) sTau[k] = x / sDiag[k];
-    __syncthreads();
-  }
-  int jq = -1;                                     // lane c < 26: the joint torque that drives column c
-  for (int q = 0; q < TI_NJ; ++q) jq = C.jcol[q] == lane ? q : jq;
-  if (lane < BD_NCOL) {
-    float a = sY[m][lane];
-    for (int q = 0; q < TI_NJ; ++q) a += sY[m + 1 + q][lane] * sTau[q];
-    sAf[lane] = a;
-  }
-  __syncthreads();
-  const int i = lane;
-  const bool row = i < m, on = row && ((act >> i) & 1u);
-  float ci = 0.f;
-  if (on) {
-    float a = 0.f;
-    for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * sAf[c];
-    ci = ((stance_acc ? stance_acc[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
-  }
-  for (int j = 0; j < m; ++j) {                    // L y = c
-    if (i == j) sV[j] = ci * sD[j];
-    __syncthreads();
-    const float yj = sV[j];
-    if (i == j) ci = yj;
-    else if (row && i > j) ci -= sA[i][j] * yj;
-  }
-  for (int j = m - 1; j >= 0; --j) {               // L^T lambda = y
-    __syncthreads();
-    if (i == j) sV[j] = ci * sD[j];
-    __syncthreads();
-    const float lj = sV[j];
-    if (row && i < j) ci -= sA[j][i] * lj;
-  }
-  __syncthreads();
-  if (lambda && row) lambda[e * m + i] = on ? sV[i] : 0.f;
-  if (lane < BD_NCOL) {
-    tau[e * BD_NCOL + lane] = jq >= 0 ? sTau[jq] : 0.f;
-    if (nudot) {
-      float a = sAf[lane];
-      for (int k = 0; k < m; ++k) a += sY[k][lane] * sV[k];
-      nudot[e * BD_NCOL + lane] = (lane < 6 || jq >= 0) ? a : 0.f;
-    }
-  }
-}
-
-// Workspace layout (floats): the right-hand-side block [N, 3 ns + 19, 26], the mass solve's output of the same shape, gamma [N, 16],
-// the task rows' Jacobian [N, 6 nt, 26] and their Jdot nu [N, 36].
-extern "C" size_t wbc_sim_task_inverse_dynamics_workspace_floats(int num_envs, int nstance, int ntasks) {
-  if (num_envs <= 0 || nstance < 0 || nstance > WBC_TASKID_MAX_STANCE || ntasks < 0 || ntasks > WBC_TASKID_MAX_TASKS) return 0;
-  return (size_t)num_envs * (2 * (size_t)(3 * nstance + 1 + TI_NJ) * BD_NCOL + CD_GSTRIDE + (size_t)6 * ntasks * BD_NCOL + TI_MAXT);
-}
-
 // ---- the same problem with torque limits and friction pyramids (include/wbc_sim.h: wbc_sim_task_inverse_dynamics_qp) ------------------
-// Launches 1-3 are the sibling's. wbc_taskqp_solve_kernel repeats its steps 1-3 (same statements, same order: where no inequality binds
-// the outputs are the sibling's bit for bit), keeps [G_lambda | lambda_0] from before the force rows are scaled, and with R, c of the
-// reflected stack solves
+// Launches 1-3 are the sibling's, and wbc_taskqp_solve_kernel is the sibling's body (ts_solve below) with tq_active_set between its
+// steps 4 and the recomputation of (nudot, lambda). It reads [G_lambda | lambda_0] as kept from before the force rows are scaled, and
+// with R, c of the reflected stack solves
 //     min 1/2 |R x + c|^2   s.t.  |x_j| <= lim_j,  a_i . (lambda_0 + G_lambda x) >= b_i  (five rows per active stance body)
 // by the dual active-set method of Goldfarb and Idnani in the variable y = R x + c, where the objective is 1/2 |y|^2, the unconstrained
 // optimum is y = 0 and row i reads d_i . y >= beta_i with d_i = R^-T n_i, beta_i = b_i + d_i . c. One lane per row (36 + 5 ns <= 56).
@@ -2038,168 +1800,26 @@ struct TqConst {
   float mu, fn_min;
   int32_t max_iter;
 };
+struct TqArgs {                                  // the QP kernel's own arguments, handed through the shared body
+  const TqConst& K;
+  const float *tau_limit, *normal, *mu;
+  int32_t *status_out, *iter_out;
+  int64_t* set_out;
+};
 
-extern "C" __global__ void __launch_bounds__(64) wbc_taskqp_solve_kernel(TqConst Cq, const float* __restrict__ rhs, const float* __restrict__ Y,
-                                                                        const float* __restrict__ gamma, const float* __restrict__ jt,
-                                                                        const float* __restrict__ gt, const uint8_t* __restrict__ active,
-                                                                        const float* __restrict__ stance_acc, const float* __restrict__ task_acc,
-                                                                        const float* __restrict__ task_weight, const float* __restrict__ nudot_ref,
-                                                                        const float* __restrict__ tau_limit, const float* __restrict__ normal,
-                                                                        const float* __restrict__ mu, int ns, int nt, int n,
-                                                                        float* __restrict__ tau, float* __restrict__ nudot, float* __restrict__ lambda,
-                                                                        int32_t* __restrict__ status_out, int64_t* __restrict__ set_out,
-                                                                        int32_t* __restrict__ iter_out) {
-  __shared__ float sY[TI_MAXRHS][CD_LD], sJc[TI_MAXS][CD_LD], sJt[TI_MAXT][CD_LD];
-  __shared__ float sS[TI_MAXROWS * TI_NC];         // the stack, row-major, pitch 19; after the reflections rows 18.. hold the d_i
-  __shared__ float sA[TI_MAXS][TI_MAXS + 1];       // lower triangle: A, then L
-  __shared__ float sD[TI_MAXS + 1], sV[TI_MAXS + 1];   // 1 / L_jj; the value handed round
-  __shared__ float sP[TI_QG][TI_NC], sDiag[TI_NJ], sTau[TI_NJ], sAf[BD_NCOL];
-  __shared__ float sG[TI_MAXS][TI_NC];             // [G_lambda | lambda_0], unscaled
+// Steps 5 and 6 of wbc_taskqp_solve_kernel, for env e with act its active-row mask: in, sTau the unconstrained optimum, sS the reflected
+// stack (R above the diagonal, c in the last column), sDiag R's diagonal and sG [G_lambda | lambda_0]; out, sTau the constrained optimum
+// (behind a barrier) and the env's status, active set and iteration count. Rows 18.. of sS are overwritten with the d_i.
+__device__ __forceinline__ void tq_active_set(const TqArgs& io, size_t e, int lane, int ns, uint32_t act, float* sS, const float (*sG)[TI_NC],
+                                              const float* sDiag, float* sTau) {
   __shared__ float sQ[TI_NJ][TQ_PITCH], sT[TI_NJ][TQ_PITCH];   // sQ[j]: column j of Q; sT[a][b], a <= b
   __shared__ float sBeta[64], sB[64], sKey[64], sSl[64], sSc[64];   // beta_i, b_i; the key of a search over the lanes; the rows' slacks, scales
   __shared__ float sLam[TI_MAXS], sMag[TI_MAXS];   // lambda(x) and the sum of its absolute terms
   __shared__ float sX0[TI_NJ], sU[TI_NJ + 1], sR[TI_NJ], sW[TI_NJ], sW1[TI_NJ], sZ[TI_NJ], sH[TI_NJ + 1];
   __shared__ int32_t sRow[TI_NJ + 1];              // the rows of W, in the order of Q's columns
-  const TsConst& C = Cq.s;
-  const int lane = threadIdx.x;
-  if ((int)blockIdx.x >= n) return;
-  const size_t e = blockIdx.x;
-  const int m = 3 * ns, mt = 6 * nt, nr = m + 1 + TI_NJ;
-  const int F0 = TI_NL, T0 = F0 + m, Q0 = T0 + mt, nrow = Q0 + TI_NJ;
-  const float *rp = rhs + e * (size_t)(nr * BD_NCOL), *yp = Y + e * (size_t)(nr * BD_NCOL), *jp = jt + e * (size_t)(mt * BD_NCOL);
-  for (int t = lane; t < nr * BD_NCOL; t += 64) {
-    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
-    sY[r][c] = yp[t];
-    if (r < m) sJc[r][c] = rp[t];
-  }
-  for (int t = lane; t < mt * BD_NCOL; t += 64) {
-    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
-    sJt[r][c] = jp[t];
-  }
-  uint32_t act = 0;                                // bit i: row i belongs to an active stance body
-  for (int k = 0; k < ns; ++k)
-    if (!active || active[e * ns + k]) act |= 7u << (3 * k);
-  __syncthreads();
-
-  // 1) the Delassus matrix and the 19 right-hand sides of its factor
-  for (int t = lane; t < m * (m + 1) / 2; t += 64) {
-    int i = (int)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);              // t = i (i + 1) / 2 + j, j <= i
-    i = i * (i + 1) / 2 > t ? i - 1 : ((i + 1) * (i + 2) / 2 <= t ? i + 1 : i);
-    const int j = t - i * (i + 1) / 2;
-    float a = 0.f;
-    for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * sY[j][c];
-    const bool on = ((act >> i) & 1u) && ((act >> j) & 1u);
-    sA[i][j] = on ? (i == j ? a + C.damping : a) : (i == j ? 1.f : 0.f);
-  }
-  for (int t = lane; t < m * TI_NC; t += 64) {
-    const int i = t / TI_NC, j = t - i * TI_NC;
-    float v = 0.f;
-    if ((act >> i) & 1u) {
-      const float* y = sY[j < TI_NJ ? m + 1 + j : m];
-      float a = 0.f;
-      for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * y[c];
-      v = j < TI_NJ ? 0.f - a : ((stance_acc ? stance_acc[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
-    }
-    sS[(F0 + i) * TI_NC + j] = v;
-  }
-  {
-    const int i = lane;
-    const bool row = i < m;
-    for (int j = 0; j < m; ++j) {
-      __syncthreads();
-      float d = sA[j][j];
-      for (int k = 0; k < j; ++k) d -= sA[j][k] * sA[j][k];
-      const float id = 1.f / __fsqrt_rn(d);
-      if (row && i > j) {
-        float s = sA[i][j];
-        for (int k = 0; k < j; ++k) s -= sA[i][k] * sA[j][k];
-        sA[i][j] = s * id;
-      }
-      if (i == j) sD[j] = id;
-    }
-  }
-  __syncthreads();
-  if (lane < TI_NC) {                              // L L^T x = column `lane`, in place
-    float* x = sS + F0 * TI_NC + lane;
-    for (int i = 0; i < m; ++i) {
-      float s = x[i * TI_NC];
-      for (int k = 0; k < i; ++k) s -= sA[i][k] * x[k * TI_NC];
-      x[i * TI_NC] = s * sD[i];
-    }
-    for (int i = m - 1; i >= 0; --i) {
-      float s = x[i * TI_NC];
-      for (int k = i + 1; k < m; ++k) s -= sA[k][i] * x[k * TI_NC];
-      x[i * TI_NC] = s * sD[i];
-    }
-  }
-  __syncthreads();
-  for (int t = lane; t < m * TI_NC; t += 64) sG[t / TI_NC][t % TI_NC] = sS[F0 * TI_NC + t];
-
-  // 2) the stack
-  for (int t = lane; t < TI_NL * TI_NC; t += 64) {
-    const int s = t / TI_NC, j = t - s * TI_NC, c = C.lcol[s];
-    float a = sY[j < TI_NJ ? m + 1 + j : m][c];
-    for (int k = 0; k < m; ++k) a += sY[k][c] * sS[(F0 + k) * TI_NC + j];
-    sS[t] = a;
-  }
-  __syncthreads();
-  for (int t = lane; t < mt * TI_NC; t += 64) {
-    const int r = t / TI_NC, j = t - r * TI_NC;
-    const float w = task_weight ? task_weight[e * mt + r] : 1.f;
-    float v = 0.f;
-    if (w > 0.f) {
-      float a = 0.f;
-      for (int s = 0; s < TI_NL; ++s) a += sJt[r][C.lcol[s]] * sS[s * TI_NC + j];
-      if (j == TI_NJ) a += gt[e * TI_MAXT + r] - task_acc[e * mt + r];
-      v = __fsqrt_rn(w) * a;
-    }
-    sS[(T0 + r) * TI_NC + j] = v;
-  }
-  __syncthreads();
-  for (int t = lane; t < TI_NL * TI_NC; t += 64) {
-    const int s = t / TI_NC, j = t - s * TI_NC;
-    const float ref = (j == TI_NJ && nudot_ref) ? nudot_ref[e * BD_NCOL + C.lcol[s]] : 0.f;
-    sS[t] = C.sp * (sS[t] - ref);
-  }
-  for (int t = lane; t < m * TI_NC; t += 64) sS[F0 * TI_NC + t] *= C.sf;
-  for (int t = lane; t < TI_NJ * TI_NC; t += 64) {
-    const int i = t / TI_NC, j = t - i * TI_NC;
-    sS[Q0 * TI_NC + t] = i == j ? C.st : 0.f;
-  }
-  __syncthreads();
-
-  // 3) Householder reflections
-  {
-    const int g = lane / TI_NC, j = lane - g * TI_NC;
-    const bool mine = g < TI_QG;
-    for (int k = 0; k < TI_NJ; ++k) {
-      if (mine) {
-        float part = 0.f;
-        if (j >= k)
-          for (int r = k + g; r < nrow; r += TI_QG) part += sS[r * TI_NC + k] * sS[r * TI_NC + j];
-        sP[g][j] = part;
-      }
-      __syncthreads();
-      const float skk = (sP[0][k] + sP[1][k]) + sP[2][k], akk = sS[k * TI_NC + k];
-      const float nrm = __fsqrt_rn(skk), alpha = akk >= 0.f ? 0.f - nrm : nrm, vk = akk - alpha;
-      float tj = 0.f;                              // 2 (v . a_j) / (v . v), v = a_k - alpha e_k: v . v = -2 alpha v_k
-      if (mine && j > k) tj = (((sP[0][j] + sP[1][j]) + sP[2][j]) - alpha * sS[k * TI_NC + j]) * (-1.f / (alpha * vk));
-      __syncthreads();
-      if (mine && j > k)
-        for (int r = k + g; r < nrow; r += TI_QG) sS[r * TI_NC + j] -= tj * (r == k ? vk : sS[r * TI_NC + k]);
-      if (lane == k) sDiag[k] = alpha;
-      __syncthreads();
-    }
-  }
-
-  // 4) the unconstrained optimum: R x = -(Q^T b)
-  for (int k = TI_NJ - 1; k >= 0; --k) {
-    float x = 0.f - sS[k * TI_NC + TI_NJ];
-    for (int j = k + 1; j < TI_NJ; ++j) x -= sS[k * TI_NC + j] * sTau[j];
-    if (lane == 0) sTau[k] = x / sDiag[k];
-    __syncthreads();
-  }
-
+  const TqConst& Cq = io.K;
+  const float *tau_limit = io.tau_limit, *normal = io.normal, *mu = io.mu;
+  const int m = 3 * ns;
   // 5) the rows: lane j < 18: x_j <= lim_j; lane 18 + j: x_j >= -lim_j; lane 36 + 5 k + t: row t of active stance body k
   float* sDm = sS + TI_NJ * TI_NC;                 // d_i = R^-T n_i at sDm[i * TQ_PITCH + 0..17]
   const int jl = lane < TI_NJ ? lane : lane - TI_NJ, rc = lane - TQ_C0, kf = rc >= 0 ? rc / 5 : 0, tf = rc - 5 * kf;
@@ -2407,7 +2027,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_taskqp_solve_kernel(TqConst
   }
 
   // 6) tau_j: a joint whose limit row is in W sits on the limit exactly; every joint inside the box. Status 1, 2: the unconstrained
-  //    optimum clamped to the box. Then (nudot, lambda) of constrained forward dynamics with it, as the sibling
+  //    optimum clamped to the box
   __syncthreads();
   if (lane < TI_NJ) {
     const float lj = lim;                          // lane j < 18 is joint j's upper row
@@ -2418,11 +2038,154 @@ extern "C" __global__ void __launch_bounds__(64) wbc_taskqp_solve_kernel(TqConst
     sTau[lane] = x;
   }
   if (lane == 0) {
-    if (status_out) status_out[e] = status;
-    if (set_out) set_out[e] = status == 0 ? (int64_t)inW : 0;
-    if (iter_out) iter_out[e] = iters;
+    if (io.status_out) io.status_out[e] = status;
+    if (io.set_out) io.set_out[e] = status == 0 ? (int64_t)inW : 0;
+    if (io.iter_out) io.iter_out[e] = iters;
   }
   __syncthreads();
+}
+
+// One env per 64-lane workgroup. With m = 3 ns, Y = (M^-1 [J_c^T | -h | S^T])^T the mass solve's output and S the stack in LDS:
+//  1) A = J_c Y_c^T + damping I (lower triangle, identity where inactive) and, in the stack's force rows, [-J_c Y_s^T | a_stance - gamma
+//     - J_c y_h]; Cholesky of A; lane j = column j solves its column in place: [G_lambda | lambda_0] (the pieces of wbc_delassus.h);
+//  2) posture rows [G_a | a_0] = [Y_s^T | y_h] + Y_c^T [G_lambda | lambda_0] on the live coordinates; task rows sqrt(w) (J_t [G_a | a_0] +
+//     (0 | Jdot nu - acc)), zero where w = 0 (acc is not read there); then the posture rows lose nudot_ref and take sqrt(w_posture),
+//     the force rows sqrt(w_force), and the torque rows are sqrt(w_torque) I: w_torque > 0 gives the stack full column rank;
+//  3) 18 Householder reflections, lane = group * 19 + column: three groups share the rows of a column's dot product with the pivot
+//     column (rows k + group, step 3: 57 consecutive LDS words per read), partial sums meet in LDS. The pivot column is left as it
+//     is (its reflected value alpha goes to sDiag), so no lane writes what another reads;
+//  4) R tau_j = -(Q^T b) by back-substitution;
+//  5, 6) with QP, tq_active_set between the two: it moves tau_j inside the limits and the friction pyramids;
+//  then a_free = y_h + Y_s^T tau_j, c = a_stance - gamma - J_c a_free, L L^T lambda = c and nudot = a_free + Y_c^T lambda.
+// The body of both solve kernels: one text, so where no inequality binds the QP kernel's outputs are its sibling's bit for bit. A
+// single-wavefront workgroup: the __syncthreads() order the LDS traffic and cost no barrier instruction.
+template <bool QP>
+__device__ __forceinline__ void ts_solve(const TsConst& C, const float* __restrict__ rhs, const float* __restrict__ Y,
+                                         const float* __restrict__ gamma, const float* __restrict__ jt, const float* __restrict__ gt,
+                                         const uint8_t* __restrict__ active, const float* __restrict__ stance_acc,
+                                         const float* __restrict__ task_acc, const float* __restrict__ task_weight,
+                                         const float* __restrict__ nudot_ref, int ns, int nt, int n, float* __restrict__ tau,
+                                         float* __restrict__ nudot, float* __restrict__ lambda, const TqArgs* io) {
+  __shared__ float sY[TI_MAXRHS][CD_LD], sJc[TI_MAXS][CD_LD], sJt[TI_MAXT][CD_LD];
+  __shared__ float sS[TI_MAXROWS * TI_NC];         // the stack, row-major, pitch 19
+  __shared__ float sA[TI_MAXS][TI_MAXS + 1];       // lower triangle: A, then L
+  __shared__ float sD[TI_MAXS + 1], sV[TI_MAXS + 1];   // 1 / L_jj; the value handed round
+  __shared__ float sP[TI_QG][TI_NC], sDiag[TI_NJ], sTau[TI_NJ], sAf[BD_NCOL];
+  __shared__ float sG[QP ? TI_MAXS : 1][TI_NC];    // QP: [G_lambda | lambda_0], unscaled
+  const int lane = threadIdx.x;
+  if ((int)blockIdx.x >= n) return;
+  const size_t e = blockIdx.x;
+  const int m = 3 * ns, mt = 6 * nt, nr = m + 1 + TI_NJ;
+  const int F0 = TI_NL, T0 = F0 + m, Q0 = T0 + mt, nrow = Q0 + TI_NJ;
+  const float *rp = rhs + e * (size_t)(nr * BD_NCOL), *yp = Y + e * (size_t)(nr * BD_NCOL), *jp = jt + e * (size_t)(mt * BD_NCOL);
+  for (int t = lane; t < nr * BD_NCOL; t += 64) {
+    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+    sY[r][c] = yp[t];
+    if (r < m) sJc[r][c] = rp[t];
+  }
+  for (int t = lane; t < mt * BD_NCOL; t += 64) {
+    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+    sJt[r][c] = jp[t];
+  }
+  uint32_t act = 0;                                // bit i: row i belongs to an active stance body
+  for (int k = 0; k < ns; ++k)
+    if (!active || active[e * ns + k]) act |= 7u << (3 * k);
+  __syncthreads();
+
+  // 1) the Delassus matrix and the 19 right-hand sides of its factor
+  delassus_fill(sJc, sY, sA, m, act, C.damping, lane, 64);
+  for (int t = lane; t < m * TI_NC; t += 64) {
+    const int i = t / TI_NC, j = t - i * TI_NC;
+    float v = 0.f;
+    if ((act >> i) & 1u) {
+      const float* y = sY[j < TI_NJ ? m + 1 + j : m];
+      float a = 0.f;
+      for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * y[c];
+      v = j < TI_NJ ? 0.f - a : ((stance_acc ? stance_acc[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
+    }
+    sS[(F0 + i) * TI_NC + j] = v;
+  }
+  delassus_cholesky(sA, sD, m, lane);
+  __syncthreads();
+  if (lane < TI_NC) delassus_column_solve(sA, sD, sS + F0 * TI_NC + lane, TI_NC, m);   // column `lane`, in place
+  __syncthreads();
+  if constexpr (QP)                                // [G_lambda | lambda_0] from before the force rows are scaled
+    for (int t = lane; t < m * TI_NC; t += 64) sG[t / TI_NC][t % TI_NC] = sS[F0 * TI_NC + t];
+
+  // 2) the stack
+  for (int t = lane; t < TI_NL * TI_NC; t += 64) {
+    const int s = t / TI_NC, j = t - s * TI_NC, c = C.lcol[s];
+    float a = sY[j < TI_NJ ? m + 1 + j : m][c];
+    for (int k = 0; k < m; ++k) a += sY[k][c] * sS[(F0 + k) * TI_NC + j];
+    sS[t] = a;
+  }
+  __syncthreads();
+  for (int t = lane; t < mt * TI_NC; t += 64) {
+    const int r = t / TI_NC, j = t - r * TI_NC;
+    const float w = task_weight ? task_weight[e * mt + r] : 1.f;
+    float v = 0.f;
+    if (w > 0.f) {
+      float a = 0.f;
+      for (int s = 0; s < TI_NL; ++s) a += sJt[r][C.lcol[s]] * sS[s * TI_NC + j];
+      if (j == TI_NJ) a += gt[e * TI_MAXT + r] - task_acc[e * mt + r];
+      v = __fsqrt_rn(w) * a;
+    }
+    sS[(T0 + r) * TI_NC + j] = v;
+  }
+  __syncthreads();
+  for (int t = lane; t < TI_NL * TI_NC; t += 64) {
+    const int s = t / TI_NC, j = t - s * TI_NC;
+    const float ref = (j == TI_NJ && nudot_ref) ? nudot_ref[e * BD_NCOL + C.lcol[s]] : 0.f;
+    sS[t] = C.sp * (sS[t] - ref);
+  }
+  for (int t = lane; t < m * TI_NC; t += 64) sS[F0 * TI_NC + t] *= C.sf;
+  for (int t = lane; t < TI_NJ * TI_NC; t += 64) {
+    const int i = t / TI_NC, j = t - i * TI_NC;
+    sS[Q0 * TI_NC + t] = i == j ? C.st : 0.f;
+  }
+  __syncthreads();
+
+  // 3) Householder reflections
+  {
+    const int g = lane / TI_NC, j = lane - g * TI_NC;
+    const bool mine = g < TI_QG;
+    // The two row loops of a reflection are 60 and 96 bytes of code with a taken branch per round, in a workgroup of one wavefront:
+    // their time depends on where they start in the 32-byte instruction-fetch windows (PERF_LOG.md: 204 to 216 us for the same
+    // instructions of wbc_taskid_solve_kernel, 444 to 464 for the QP call). Pinned from here, so that the steps above can change
+    // without moving them: the first loop starts 16 bytes into a window, where it stood when the reflections were written.
+    asm volatile(".p2align 5\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+    for (int k = 0; k < TI_NJ; ++k) {
+      if (mine) {
+        float part = 0.f;
+        if (j >= k)
+          for (int r = k + g; r < nrow; r += TI_QG) part += sS[r * TI_NC + k] * sS[r * TI_NC + j];
+        sP[g][j] = part;
+      }
+      __syncthreads();
+      const float skk = (sP[0][k] + sP[1][k]) + sP[2][k], akk = sS[k * TI_NC + k];
+      const float nrm = __fsqrt_rn(skk), alpha = akk >= 0.f ? 0.f - nrm : nrm, vk = akk - alpha;
+      float tj = 0.f;                              // 2 (v . a_j) / (v . v), v = a_k - alpha e_k: v . v = -2 alpha v_k
+      if (mine && j > k) tj = (((sP[0][j] + sP[1][j]) + sP[2][j]) - alpha * sS[k * TI_NC + j]) * (-1.f / (alpha * vk));
+      __syncthreads();
+      if (mine && j > k)
+        for (int r = k + g; r < nrow; r += TI_QG) sS[r * TI_NC + j] -= tj * (r == k ? vk : sS[r * TI_NC + k]);
+      if (lane == k) sDiag[k] = alpha;
+      __syncthreads();
+    }
+  }
+
+  // 4) the unconstrained optimum tau_j: R x = -(Q^T b)
+#pragma unroll                                     // all 18 steps written out, as the compiler chose while this stood in the kernels
+  for (int k = TI_NJ - 1; k >= 0; --k) {
+    float x = 0.f - sS[k * TI_NC + TI_NJ];
+#pragma unroll
+    for (int j = k + 1; j < TI_NJ; ++j) x -= sS[k * TI_NC + j] * sTau[j];
+    if (lane == 0) sTau[k] = x / sDiag[k];
+    __syncthreads();
+  }
+  if constexpr (QP) tq_active_set(*io, e, lane, ns, act, sS, sG, sDiag, sTau);
+
+  // (nudot, lambda) of constrained forward dynamics with tau_j
   int jq = -1;                                     // lane c < 26: the joint torque that drives column c
   for (int q = 0; q < TI_NJ; ++q) jq = C.jcol[q] == lane ? q : jq;
   if (lane < BD_NCOL) {
@@ -2439,21 +2202,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_taskqp_solve_kernel(TqConst
     for (int c = 0; c < BD_NCOL; ++c) a += sJc[i][c] * sAf[c];
     ci = ((stance_acc ? stance_acc[e * m + i] : 0.f) - gamma[e * CD_GSTRIDE + i]) - a;
   }
-  for (int j = 0; j < m; ++j) {                    // L y = c
-    if (i == j) sV[j] = ci * sD[j];
-    __syncthreads();
-    const float yj = sV[j];
-    if (i == j) ci = yj;
-    else if (row && i > j) ci -= sA[i][j] * yj;
-  }
-  for (int j = m - 1; j >= 0; --j) {               // L^T lambda = y
-    __syncthreads();
-    if (i == j) sV[j] = ci * sD[j];
-    __syncthreads();
-    const float lj = sV[j];
-    if (row && i < j) ci -= sA[j][i] * lj;
-  }
-  __syncthreads();
+  delassus_lane_solve(sA, sD, sV, m, i, ci);
   if (lambda && row) lambda[e * m + i] = on ? sV[i] : 0.f;
   if (lane < BD_NCOL) {
     tau[e * BD_NCOL + lane] = jq >= 0 ? sTau[jq] : 0.f;
@@ -2465,22 +2214,63 @@ extern "C" __global__ void __launch_bounds__(64) wbc_taskqp_solve_kernel(TqConst
   }
 }
 
-// The four launches of both entry points on `stream`: the body of wbc_sim_task_inverse_dynamics, moved here when the second entry point
-// came; qp false: the sibling without inequalities (the arguments after `qp` are not read).
+
+extern "C" __global__ void __launch_bounds__(64) wbc_taskid_solve_kernel(TsConst C, const float* __restrict__ rhs, const float* __restrict__ Y,
+                                                                        const float* __restrict__ gamma, const float* __restrict__ jt,
+                                                                        const float* __restrict__ gt, const uint8_t* __restrict__ active,
+                                                                        const float* __restrict__ stance_acc, const float* __restrict__ task_acc,
+                                                                        const float* __restrict__ task_weight, const float* __restrict__ nudot_ref,
+                                                                        int ns, int nt, int n, float* __restrict__ tau, float* __restrict__ nudot,
+                                                                        float* __restrict__ lambda) {
+  ts_solve<false>(C, rhs, Y, gamma, jt, gt, active, stance_acc, task_acc, task_weight, nudot_ref, ns, nt, n, tau, nudot, lambda, nullptr);
+}
+
+extern "C" __global__ void __launch_bounds__(64) wbc_taskqp_solve_kernel(TqConst Cq, const float* __restrict__ rhs, const float* __restrict__ Y,
+                                                                        const float* __restrict__ gamma, const float* __restrict__ jt,
+                                                                        const float* __restrict__ gt, const uint8_t* __restrict__ active,
+                                                                        const float* __restrict__ stance_acc, const float* __restrict__ task_acc,
+                                                                        const float* __restrict__ task_weight, const float* __restrict__ nudot_ref,
+                                                                        const float* __restrict__ tau_limit, const float* __restrict__ normal,
+                                                                        const float* __restrict__ mu, int ns, int nt, int n,
+                                                                        float* __restrict__ tau, float* __restrict__ nudot, float* __restrict__ lambda,
+                                                                        int32_t* __restrict__ status_out, int64_t* __restrict__ set_out,
+                                                                        int32_t* __restrict__ iter_out) {
+  const TqArgs io = {Cq, tau_limit, normal, mu, status_out, iter_out, set_out};
+  ts_solve<true>(Cq.s, rhs, Y, gamma, jt, gt, active, stance_acc, task_acc, task_weight, nudot_ref, ns, nt, n, tau, nudot, lambda, &io);
+}
+
+// Workspace layout (floats): the right-hand-side block [N, 3 ns + 19, 26], the mass solve's output of the same shape, gamma [N, 16],
+// the task rows' Jacobian [N, 6 nt, 26] and their Jdot nu [N, 36].
+extern "C" size_t wbc_sim_task_inverse_dynamics_workspace_floats(int num_envs, int nstance, int ntasks) {
+  if (num_envs <= 0 || nstance < 0 || nstance > WBC_TASKID_MAX_STANCE || ntasks < 0 || ntasks > WBC_TASKID_MAX_TASKS) return 0;
+  return (size_t)num_envs * (2 * (size_t)(3 * nstance + 1 + TI_NJ) * BD_NCOL + CD_GSTRIDE + (size_t)6 * ntasks * BD_NCOL + TI_MAXT);
+}
+
+// What wbc_sim_task_inverse_dynamics_qp takes beyond its sibling.
+struct TaskQpArgs {
+  const wbc_taskqp_limits* limits;
+  const float *tau_limit, *normal, *mu;
+  int32_t* status;
+  int64_t* active_set;
+  int32_t* iterations;
+};
+
+// The four launches of both entry points on `stream`; qp NULL: the sibling without inequalities.
 static int taskid_launch(const char* who, wbc_sim* s, const int32_t* stance_bodies, int nstance, const uint8_t* active, const float* stance_acc,
                          const int32_t* task_bodies, int ntasks, const float* task_acc, const float* task_weight, const float* nudot_ref,
                          const wbc_taskid_weights* weights, int flags, float* tau, float* nudot, float* lambda, float* workspace, void* stream,
-                         bool qp, const wbc_taskqp_limits* limits, const float* tau_limit, const float* normal, const float* mu, int32_t* status,
-                         int64_t* active_set, int32_t* iterations) {
+                         const TaskQpArgs* qp) {
   WbCall c(who, s, stream);
   auto fin_ge0 = [](float x) { return x >= 0.f && x <= 3.402823466e38f; };   // finite: up to FLT_MAX
   // the new entry point's own arguments first: they need no sim, so a binding can be checked without a device
   if (qp) {
+    const wbc_taskqp_limits* limits = qp->limits;
     if (!limits) return c.fail(-1, "limits is NULL");
     if (!(limits->mu > 0.f) || !fin_ge0(limits->mu)) return c.fail(-1, "limits.mu must be finite and > 0");
     if (!fin_ge0(fabsf(limits->fn_min))) return c.fail(-1, "limits.fn_min must be finite");
     if (limits->max_iter < 0 || limits->max_iter > WBC_TASKQP_MAX_ITER) return c.fail(-1, "limits.max_iter must be 0 (the default) or 1..WBC_TASKQP_MAX_ITER");
-    if ((((uintptr_t)tau_limit | (uintptr_t)normal | (uintptr_t)mu | (uintptr_t)status | (uintptr_t)iterations) & 3u) || ((uintptr_t)active_set & 7u))
+    if ((((uintptr_t)qp->tau_limit | (uintptr_t)qp->normal | (uintptr_t)qp->mu | (uintptr_t)qp->status | (uintptr_t)qp->iterations) & 3u) ||
+        ((uintptr_t)qp->active_set & 7u))
       return c.fail(-1, "tau_limit / normal / mu / status / iterations must be 4-byte aligned and active_set 8-byte aligned");
   }
   if (!s) return c.no_sim();
@@ -2544,10 +2334,10 @@ static int taskid_launch(const char* who, wbc_sim* s, const int32_t* stance_bodi
     return c.launched();
   }
   for (int q = 0; q < TI_NJ; ++q) Q.lim[q] = c.hc->cfg.torque_limits[C.jcol[q] - 6];
-  Q.mu = limits->mu; Q.fn_min = limits->fn_min; Q.max_iter = limits->max_iter > 0 ? limits->max_iter : TQ_DEFAULT_ITER;
+  Q.mu = qp->limits->mu; Q.fn_min = qp->limits->fn_min; Q.max_iter = qp->limits->max_iter > 0 ? qp->limits->max_iter : TQ_DEFAULT_ITER;
   hipLaunchKernelGGL(wbc_taskqp_solve_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, Q, (const float*)blk, (const float*)Y, (const float*)gamma,
-                     (const float*)jt, (const float*)gt, active, stance_acc, task_acc, task_weight, nudot_ref, tau_limit, normal, mu, nstance, ntasks, n,
-                     tau, nudot, lambda, status, active_set, iterations);
+                     (const float*)jt, (const float*)gt, active, stance_acc, task_acc, task_weight, nudot_ref, qp->tau_limit, qp->normal, qp->mu, nstance,
+                     ntasks, n, tau, nudot, lambda, qp->status, qp->active_set, qp->iterations);
   return c.launched();
 }
 
@@ -2557,8 +2347,7 @@ extern "C" int wbc_sim_task_inverse_dynamics(wbc_sim* s, const int32_t* stance_b
                                              const float* nudot_ref, const wbc_taskid_weights* weights, int flags, float* tau, float* nudot,
                                              float* lambda, float* workspace, void* stream) {
   return taskid_launch("wbc_sim_task_inverse_dynamics", s, stance_bodies, nstance, active, stance_acc, task_bodies, ntasks, task_acc, task_weight,
-                       nudot_ref, weights, flags, tau, nudot, lambda, workspace, stream, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       nullptr);
+                       nudot_ref, weights, flags, tau, nudot, lambda, workspace, stream, nullptr);
 }
 
 // The sibling's workspace: the solve kernel keeps everything else in LDS.
@@ -2573,7 +2362,7 @@ extern "C" int wbc_sim_task_inverse_dynamics_qp(wbc_sim* s, const int32_t* stanc
                                                 const float* tau_limit, const float* normal, const float* mu, int flags, float* tau, float* nudot,
                                                 float* lambda, int32_t* status, int64_t* active_set, int32_t* iterations, float* workspace,
                                                 void* stream) {
+  const TaskQpArgs qp = {limits, tau_limit, normal, mu, status, active_set, iterations};
   return taskid_launch("wbc_sim_task_inverse_dynamics_qp", s, stance_bodies, nstance, active, stance_acc, task_bodies, ntasks, task_acc,
-                       task_weight, nudot_ref, weights, flags, tau, nudot, lambda, workspace, stream, true, limits, tau_limit, normal, mu, status,
-                       active_set, iterations);
+                       task_weight, nudot_ref, weights, flags, tau, nudot, lambda, workspace, stream, &qp);
 }

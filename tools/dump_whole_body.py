@@ -6,7 +6,8 @@ its own) and comparing the two files as raw 32-bit integers.
   python tools/dump_whole_body.py --compare A.npz B.npz                         exit status 1 unless every array is equal, bit for bit
 
 Envs n = 1, 13, 64 (13: the idle half-workgroup of the two-envs-per-workgroup kernels is live); states and body parameters from the
-generators of tests/test_mass_solve.py.
+generators of tests/test_mass_solve.py. Every array is float32: of task_inverse_dynamics_qp's integer outputs, status and iterations are
+stored by value (exact below 2^24, asserted) and the int64 active_set as its two 32-bit words, reinterpreted and not converted.
 """
 import os
 import sys
@@ -46,6 +47,19 @@ def keep(name, *tensors):
         if not np.isfinite(a).all():
             print(f"{name}.{i}: {int((~np.isfinite(a)).sum())} non-finite values")
         out[f"{name}.{i}"] = a
+
+
+def keep_qp(name, tau, nudot, lam, info):
+    """The QP entry point's outputs; prints how many envs ended in each status and how many hold a torque-limit row."""
+    keep(name, tau, nudot, lam)
+    status, iters, aset = (info[k].cpu().numpy() for k in ("status", "iterations", "active_set"))
+    assert status.dtype == np.int32 and iters.dtype == np.int32 and aset.dtype == np.int64
+    for tag, a in (("status", status), ("iterations", iters)):
+        out[f"{name}.{tag}"] = a.astype(np.float32)
+        assert np.array_equal(out[f"{name}.{tag}"].astype(np.int32), a), tag
+    out[name + ".active_set"] = np.ascontiguousarray(aset).view(np.float32).reshape(-1, 2)        # the words' bits, not their values
+    print(f"{name}: status counts {np.bincount(status, minlength=3).tolist()}, box rows held in {int((aset & (2 ** 36 - 1) != 0).sum())} of "
+          f"{len(aset)} envs, contact rows in {int((aset >> 36 != 0).sum())}")
 
 
 for n in (1, 13, 64):
@@ -105,9 +119,18 @@ for n in (1, 13, 64):
         keep(T + "tid.0_0" + A, *sim.task_inverse_dynamics(armature=arm))
         tasks = [0, grip] + feet
         w = torch.ones(n, 6, 6, device=dev); w[:, 2:] = 0.0
-        keep(T + "tid.4_6" + A, *sim.task_inverse_dynamics(feet, tasks, rnd(n, 6, 6, scale=2.0), w, active=act, stance_acc=ades,
-                                                         nudot_ref=rnd(n, 26), damping=1e-4, armature=arm))
+        full = dict(stance_bodies=feet, task_bodies=tasks, task_acc=rnd(n, 6, 6, scale=2.0), task_weight=w, active=act, stance_acc=ades,
+                    nudot_ref=rnd(n, 26), damping=1e-4, armature=arm)
+        free = sim.task_inverse_dynamics(**full)
+        keep(T + "tid.4_6" + A, *free)
         keep(T + "tid.4_6.plain" + A, *sim.task_inverse_dynamics(feet, tasks, rnd(n, 6, 6, scale=2.0), armature=arm))
+        # the same problem with inequalities: the config's limits; limits at half of what the sibling asks for, so that box rows bind;
+        # no stance body (torque limits alone)
+        keep_qp(T + "tqp.4_6" + A, *sim.task_inverse_dynamics_qp(**full, mu=0.6, fn_min=2.0))
+        half = (0.5 * free[0][:, 6:24].abs() + 0.05).contiguous()
+        keep_qp(T + "tqp.4_6.box" + A, *sim.task_inverse_dynamics_qp(**full, mu=0.6, fn_min=2.0, tau_limit=half))
+        keep_qp(T + "tqp.0_6" + A, *sim.task_inverse_dynamics_qp((), tasks, full["task_acc"], w, nudot_ref=full["nudot_ref"], armature=arm,
+                                                                 tau_limit=half))
     md = torch.empty(n, 26, 26, device=dev)
     fd = sim.forward_dynamics_derivatives(tau=None, minv=md)
     keep(T + "fdd.tau_null", *fd)
