@@ -1162,11 +1162,12 @@ extern "C" size_t wbc_sim_constrained_dynamics_workspace_floats(int num_envs, in
 }
 
 // Four launches on `stream`: h (the existing inverse-dynamics kernel, into the sim's scratch), the right-hand-side block, the existing
-// mass solve with 3 nb + 1 right-hand sides, the constraint solve. Arguments and conventions: include/wbc_sim.h.
-extern "C" int wbc_sim_constrained_dynamics(wbc_sim* s, const int32_t* rigid_bodies, int nbodies, const uint8_t* active, const float* tau,
-                                            const float* acc_des, float damping, int flags, float* nudot, float* lambda, float* workspace,
-                                            void* stream) {
-  WbCall c("wbc_sim_constrained_dynamics", s, stream);
+// mass solve with 3 nb + 1 right-hand sides, the constraint solve. Arguments and conventions: include/wbc_sim.h. The body of
+// wbc_sim_constrained_dynamics and the first stage of wbc_sim_constrained_dynamics_derivatives (c.who names the entry point in a refusal);
+// C comes back filled for the caller that goes on.
+static int constrained_dynamics_run(const WbCall& c, wbc_sim* s, const int32_t* rigid_bodies, int nbodies, const uint8_t* active, const float* tau,
+                                    const float* acc_des, float damping, int flags, float* nudot, float* lambda, float* workspace, void* stream,
+                                    CdConst& C) {
   if (!s) return c.no_sim();
   if (!rigid_bodies || !nudot || !workspace) return c.fail(-1, "rigid_bodies / nudot / workspace is NULL");
   if (nbodies < 1 || nbodies > WBC_CONSTR_MAX_BODIES) return c.fail(-1, "nbodies must be 1..WBC_CONSTR_MAX_BODIES");
@@ -1177,7 +1178,6 @@ extern "C" int wbc_sim_constrained_dynamics(wbc_sim* s, const int32_t* rigid_bod
   if (!c.have) return c.no_state();
   for (int k = 0; k < nbodies; ++k)
     if (rigid_bodies[k] < 0 || rigid_bodies[k] >= WBC_NRB) return c.fail(-1, "rigid-body index outside 0..WBC_NRB-1");
-  CdConst C;
   if (ba_const_fill(c.hc->model, C, C) != 0) return c.no_tree();
   for (int k = 0; k < nbodies; ++k)
     for (int l = 0; l < k; ++l)
@@ -1204,6 +1204,14 @@ extern "C" int wbc_sim_constrained_dynamics(wbc_sim* s, const int32_t* rigid_bod
   hipLaunchKernelGGL(wbc_constraint_solve_kernel, grid, dim3(64), 0, (hipStream_t)stream, (const float*)blk, (const float*)Y, (const float*)gamma, active,
                      acc_des, damping, nbodies, live_cols, n, nudot, lambda);
   return c.launched();
+}
+
+extern "C" int wbc_sim_constrained_dynamics(wbc_sim* s, const int32_t* rigid_bodies, int nbodies, const uint8_t* active, const float* tau,
+                                            const float* acc_des, float damping, int flags, float* nudot, float* lambda, float* workspace,
+                                            void* stream) {
+  WbCall c("wbc_sim_constrained_dynamics", s, stream);
+  CdConst C;
+  return constrained_dynamics_run(c, s, rigid_bodies, nbodies, active, tau, acc_des, damping, flags, nudot, lambda, workspace, stream, C);
 }
 
 // ---- centre of mass, centroidal momentum and its matrix (include/wbc_sim.h: wbc_sim_centroidal) ----------------------------------------
@@ -1678,6 +1686,320 @@ extern "C" int wbc_sim_forward_dynamics_derivatives(wbc_sim* s, const float* tau
     return c.launched();
   }
   return 0;
+}
+
+// ---- analytic derivatives of stance-constrained forward dynamics (include/wbc_sim.h: wbc_sim_constrained_dynamics_derivatives) ----------
+// The solution (nudot, lambda) of wbc_sim_constrained_dynamics satisfies r1 = ID(q, nu, nudot) [+ armature nudot] - Jc^T lambda - tau = 0
+// and r2 = Jc nudot + (Jdot nu)_c - a_des + damping lambda = 0. With x a direction of q or of nu, X = -M^-1 dr1/dx, Y = M^-1 Jc^T:
+//     dlambda/dx = -(A + damping I)^-1 (Jc X + dr2/dx),   dnudot/dx = X + Y dlambda/dx;   for tau, X = M^-1 and Jc X = Y^T.
+// dr1/dx is wbc_dynamics_derivatives_kernel's output at the solution's nudot, less d(Jc^T lambda)/dq; the two kernels below supply that
+// term and dr2/dx, and the algebra per env. The tangent convention is wbc_sim_inverse_dynamics_derivatives'.
+#define CT_MAXPAIR (WBC_CONSTR_MAX_BODIES * (3 + WBC_MAX_DEPTH))   // (listed body, direction) pairs of one output: 45
+#define CT_R2ENV (2 * CD_MAXROWS * BD_NCOL)     // floats of dr2/dq, dr2/dnu per env in the workspace: [2][15][26]
+static_assert(CT_MAXPAIR <= 64 && WBC_NB + WBC_CONSTR_MAX_BODIES <= 64, "one round of lanes");
+struct CtConst : TreeWalk, TreeRigid, TreeCols {
+  int32_t nb, rb[WBC_CONSTR_MAX_BODIES];       // the listed rigid bodies
+  int32_t npair;                               // live (listed body, direction) pairs of one output
+  uint8_t pair_k[CT_MAXPAIR], pair_u[CT_MAXPAIR];   // u: 0..2 a root direction, 3 + i the joint path[body][i]
+};
+
+// One env per 64-lane workgroup.
+//  1) lane b < 19 = moving body b walks root -> b (frames only) and leaves its joint axis and origin (F) in LDS; lane 19 + k leaves listed
+//     body k's origin and lambda_k turned to F's axes.
+//  2) dr2/dq and dr2/dnu [3 nb, 26], the partials of the listed origins' classical acceleration Jc nudot + Jdot nu at fixed nudot: lane =
+//     (listed body, direction) pair redoes the body's path walk with omega, alpha and the classical acceleration of the body's own origin
+//     paired with their tangents (the vw, aw, ao lines of wbc_dynamics_derivatives_kernel's walk; the root rotation is seeded in the
+//     root body's frame, see below), carries them to rb_offset and turns the result to world axes. Every lever is a link or body offset. Every other entry of a row is exactly 0, as are the rows of an inactive body.
+//  3) + d(Jc^T lambda)/dq into the block of -dtau/dq [direction][row]: the tangent of a world-fixed force lambda_k applied at the origin
+//     x_k, in closed form from the joints' axes a and origins o (the root rotation counts as a joint above all with axis e_j, the root's
+//     angular rows as one with axis e_j that nothing turns): with l_c = x_k - o_c, a direction x strictly above row c turns c's axis and
+//     lever, d(a_c x l_c) = a_x x (a_c x l_c); otherwise it moves x_k alone, d(a_c x l_c) = a_c x (a_x x l_x). Triple products with lambda
+//     are formed in F's axes.
+// A single-wavefront workgroup: the __syncthreads() order the LDS traffic and cost no barrier instruction. The root position and linear
+// velocity are never read.
+extern "C" __global__ void __launch_bounds__(64) wbc_constraint_tangent_kernel(CtConst C, const float* __restrict__ root,
+                                                                              const float* __restrict__ dofs,
+                                                                              const uint8_t* __restrict__ active,
+                                                                              const float* __restrict__ nudot, const float* __restrict__ lambda,
+                                                                              int n, int want_q, int want_nu, float* __restrict__ rq,
+                                                                              float* __restrict__ r2) {
+  __shared__ float sJ[WBC_NB][6];                  // joint axis, joint origin, in F
+  __shared__ float sX[WBC_CONSTR_MAX_BODIES][6];   // listed body's origin, lambda, in F
+  __shared__ float sR[2][CD_MAXROWS][CD_LD];       // dr2/dq, dr2/dnu
+  const int lane = threadIdx.x;
+  const size_t e = blockIdx.x;
+  if ((int)blockIdx.x >= n) return;
+  const int nb = C.nb, m = 3 * nb;
+  const f3 zero = mk3(0.f, 0.f, 0.f);
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+  uint32_t act = 0;                                // bit k: listed body k is active
+#pragma unroll
+  for (int k = 0; k < WBC_CONSTR_MAX_BODIES; ++k)
+    if (k < nb && (!active || active[e * nb + k])) act |= 1u << k;
+
+  if (lane < WBC_NB + nb) {
+    const bool body = lane < WBC_NB;
+    const int k = body ? 0 : lane - WBC_NB, r = C.rb[k], b = body ? lane : C.rb_body[r];
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    f3 p = zero, Sw = zero;
+#pragma nounroll
+    for (int i = 0; i < WBC_MAX_DEPTH; ++i) {
+      const int a = C.path[b][i];
+      if (a < 0) break;
+      float Q[9];
+      const f3 u = tree_joint_rot(C.axis[a], dofs[e * (2 * WBC_NDOF) + 2 * C.dof[a]], Q);
+      Sw = tree_frame_step(E, p, Q, C.joint_xyz[a], u);
+    }
+    if (body) {
+      st3(sJ[b], Sw); st3(sJ[b] + 3, p);
+    } else {
+      st3(sX[k], p + mat_mul(E, mk3(C.rb_offset[r][0], C.rb_offset[r][1], C.rb_offset[r][2])));
+      st3(sX[k] + 3, ((act >> k) & 1u) ? matT_mul(R, ld3(lambda + e * m + 3 * k)) : zero);
+    }
+  }
+  for (int t = lane; t < 2 * CD_MAXROWS * CD_LD; t += 64) (&sR[0][0][0])[t] = 0.f;
+  __syncthreads();
+
+  const f3 w0 = matT_mul(R, ld3(root + e * 26 + 10));
+  const f3 al0 = matT_mul(R, ld3(nudot + e * BD_NCOL + 3)), a0 = matT_mul(R, ld3(nudot + e * BD_NCOL));
+#pragma nounroll
+  for (int which = 0; which < 2; ++which) {
+    if (!(which ? want_nu : want_q) || lane >= C.npair) continue;
+    const int k = C.pair_k[lane], u = C.pair_u[lane], r = C.rb[k], b = C.rb_body[r];
+    if (k >= nb || !((act >> k) & 1u)) continue;
+    const int t = u < 3 ? u + 3 * which : 3 + u + 6 * which;   // the derivative kernel's slots: rotation 0..2, omega 3..5, q 6 + i, qd 12 + i
+    const f3 phi = matT_mul(R, mk3(u == 0 ? 1.f : 0.f, u == 1 ? 1.f : 0.f, u == 2 ? 1.f : 0.f));
+    // Root rotation: the walk's axes stay where F stood, so the root vectors (world components held) keep their components and have no
+    // tangent; the root BODY's frame turns in them, dE = [phi]x. (wbc_dynamics_derivatives_kernel turns the root vectors by -phi x (.)
+    // instead and the world rows back by e_j x (.): the same derivative, but a_root x phi and e_j x a_root then cancel only to rounding,
+    // an error the size of |nudot[0:3]| that no term of these rows accounts for.)
+    const float rot = t < 3 ? 1.f : 0.f, omg = t >= 3 && t < 6 ? 1.f : 0.f;
+    d3 vw = mkd3(w0, phi * omg);
+    d3 aw = mkd3(al0, zero), ao = mkd3(a0, zero);
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    float dE[9] = {0.f, -phi.z * rot, phi.y * rot, phi.z * rot, 0.f, -phi.x * rot, -phi.y * rot, phi.x * rot, 0.f};
+    int col = 3 + u;                               // the output column: a root direction, or the joint's
+#pragma nounroll
+    for (int i = 0; i < WBC_MAX_DEPTH; ++i) {
+      const int a = C.path[b][i];
+      if (a < 0) break;
+      const int d = C.dof[a];
+      if (u == 3 + i) col = 6 + d;
+      const float dq = t == 6 + i ? 1.f : 0.f;
+      float s, c, Q[9], dQ[9];
+      const f3 uu = tree_joint_rot(C.axis[a], dofs[e * (2 * WBC_NDOF) + 2 * d], Q, s, c);
+      tree_rodrigues(uu, c * dq, -s * dq, s * dq, dQ);
+      const f3 xyz = mk3(C.joint_xyz[a][0], C.joint_xyz[a][1], C.joint_xyz[a][2]);
+      const d3 rr = mkd3(mat_mul(E, xyz), mat_mul(dE, xyz));
+      ao = ao + cross(aw, rr) + cross(vw, cross(vw, rr));
+      float En[9], dEQ[9], EdQ[9];
+      tree_frame_mul(E, Q, En);
+      tree_frame_mul(dE, Q, dEQ);
+      tree_frame_mul(E, dQ, EdQ);
+#pragma unroll
+      for (int j = 0; j < 9; ++j) { E[j] = En[j]; dE[j] = dEQ[j] + EdQ[j]; }
+      const d3 Sw = mkd3(mat_mul(E, uu), mat_mul(dE, uu));
+      du qd;
+      qd.v = dofs[e * (2 * WBC_NDOF) + 2 * d + 1];
+      qd.d = t == 12 + i ? 1.f : 0.f;
+      const float qdd = nudot[e * BD_NCOL + 6 + d];
+      const d3 jw = Sw * qd;
+      aw = aw + Sw * qdd + cross(vw, jw);
+      vw = vw + jw;
+    }
+    const f3 off = mk3(C.rb_offset[r][0], C.rb_offset[r][1], C.rb_offset[r][2]);
+    const d3 xo = mkd3(mat_mul(E, off), mat_mul(dE, off));
+    const d3 lin = ao + cross(aw, xo) + cross(vw, cross(vw, xo));
+    const f3 val = mat_mul(R, lin.d);
+    sR[which][3 * k][col] = val.x; sR[which][3 * k + 1][col] = val.y; sR[which][3 * k + 2][col] = val.z;
+  }
+  __syncthreads();
+  for (int t = lane; t < 2 * m * BD_NCOL; t += 64) {
+    const int g = t / (m * BD_NCOL), rem = t - g * (m * BD_NCOL), i = rem / BD_NCOL, x = rem - i * BD_NCOL;
+    if (g ? want_nu : want_q) r2[e * CT_R2ENV + g * (CD_MAXROWS * BD_NCOL) + rem] = sR[g][i][x];
+  }
+
+  if (!want_q) return;
+  for (int idx = lane; idx < DD_MENV; idx += 64) {
+    const int x = idx / BD_NCOL, c = idx - x * BD_NCOL;          // direction, row of tau: the block is [direction][row]
+    const int xb = x < 6 ? 0 : C.col_body[x - 6], cb = c < 6 ? 0 : C.col_body[c - 6];
+    if (x < 3 || c < 3 || xb < 0 || cb < 0) continue;
+    const f3 ax = x < 6 ? matT_mul(R, mk3(x == 3 ? 1.f : 0.f, x == 4 ? 1.f : 0.f, x == 5 ? 1.f : 0.f)) : ld3(sJ[xb]);
+    const f3 ac = c < 6 ? matT_mul(R, mk3(c == 3 ? 1.f : 0.f, c == 4 ? 1.f : 0.f, c == 5 ? 1.f : 0.f)) : ld3(sJ[cb]);
+    const f3 ox = x < 6 ? zero : ld3(sJ[xb] + 3), oc = c < 6 ? zero : ld3(sJ[cb] + 3);
+    // x strictly above c: the root rotation above every joint, a joint above the joints further out on its chain
+    const bool above = c >= 6 && (x < 6 || (xb != cb && ((C.anc[cb] >> xb) & 1u)));
+    float val = 0.f;
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < WBC_CONSTR_MAX_BODIES; ++k) {
+      if (k >= nb || !((act >> k) & 1u)) continue;
+      const uint32_t anc = C.anc[C.rb_body[C.rb[k]]];
+      if (!((anc >> xb) & 1u) || !((anc >> cb) & 1u)) continue;
+      const f3 xk = ld3(sX[k]), lam = ld3(sX[k] + 3);
+      const f3 v = above ? cross(ax, cross(ac, xk - oc)) : cross(ac, cross(ax, xk - ox));
+      val += dot(v, lam);
+      any = true;
+    }
+    if (any) rq[e * DD_MENV + idx] += val;
+  }
+}
+
+// Per env, one 64-lane workgroup: A + damping I rebuilt from the workspace's J and Y (delassus_fill, identity rows where a body is
+// inactive) and factorised (delassus_cholesky); then per requested group g (q, nu, tau), one after the other in the same LDS blocks:
+// X [direction][row] = the mass solve's output; Z[i][x] = Jc_i . X_x + dr2_i/dx (for tau: Y_i[x]); lane x solves its column
+// (delassus_column_solve) and negates it: dlambda/dx; dnudot/dx = X_x + sum_i Y_i Z[i][x]. The blocks sit in LDS, so either layout is
+// stored directly with consecutive lanes on consecutive addresses. Literal zeros: columns 0:3 of the q / nu groups, the fingers' rows and
+// columns, the rows of an inactive body. A single-wavefront workgroup: the __syncthreads() order the LDS traffic.
+struct CsOut { float *dnd[3], *dlam[3]; const float* X[3]; };
+extern "C" __global__ void __launch_bounds__(64) wbc_constraint_derivatives_solve_kernel(const float* __restrict__ rhs, const float* __restrict__ Y,
+                                                                                        const float* __restrict__ r2,
+                                                                                        const uint8_t* __restrict__ active, float damping,
+                                                                                        int nb, uint32_t live_cols, int n, int transposed,
+                                                                                        CsOut O) {
+  __shared__ float sJ[CD_MAXROWS][CD_LD], sY[CD_MAXROWS][CD_LD], sZ[CD_MAXROWS][CD_LD];
+  __shared__ float sX[BD_NCOL][CD_LD];
+  __shared__ float sA[CD_MAXROWS][CD_MAXROWS + 1];   // lower triangle: A, then L
+  __shared__ float sD[CD_MAXROWS + 1];
+  const int lane = threadIdx.x;
+  const size_t e = blockIdx.x;
+  if ((int)blockIdx.x >= n) return;
+  const int m = 3 * nb;
+  const float *rp = rhs + e * (size_t)((m + 1) * BD_NCOL), *yp = Y + e * (size_t)((m + 1) * BD_NCOL);
+  for (int t = lane; t < m * BD_NCOL; t += 64) {
+    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+    sJ[r][c] = rp[t]; sY[r][c] = yp[t];
+  }
+  uint32_t act = 0;                                // bit i: row i belongs to an active body
+#pragma unroll
+  for (int k = 0; k < WBC_CONSTR_MAX_BODIES; ++k)
+    if (k < nb && (!active || active[e * nb + k])) act |= 7u << (3 * k);
+  __syncthreads();
+  delassus_fill(sJ, sY, sA, m, act, damping, lane, 64);
+  delassus_cholesky(sA, sD, m, lane);
+  __syncthreads();
+
+#pragma nounroll
+  for (int g = 0; g < 3; ++g) {
+    float *dnd = O.dnd[g], *dlam = O.dlam[g];
+    if (!dnd && !dlam) continue;
+    const float* X = O.X[g];                       // NULL: the tau group with dlambda alone, where Z needs no X
+    if (X)
+      for (int t = lane; t < DD_MENV; t += 64) {
+        const int x = t / BD_NCOL, c = t - x * BD_NCOL;
+        sX[x][c] = X[e * DD_MENV + t];
+      }
+    __syncthreads();
+    for (int t = lane; t < m * BD_NCOL; t += 64) {
+      const int i = t / BD_NCOL, x = t - i * BD_NCOL;
+      float z;
+      if (g == 2) z = sY[i][x];
+      else {
+        z = r2[e * CT_R2ENV + g * (CD_MAXROWS * BD_NCOL) + t];
+#pragma unroll
+        for (int c = 0; c < BD_NCOL; ++c) z += sJ[i][c] * sX[x][c];
+      }
+      sZ[i][x] = ((act >> i) & 1u) ? z : 0.f;
+    }
+    __syncthreads();
+    if (lane < BD_NCOL) {
+      delassus_column_solve(sA, sD, &sZ[0][lane], CD_LD, m);
+#pragma nounroll
+      for (int i = 0; i < m; ++i) sZ[i][lane] = -sZ[i][lane];
+    }
+    __syncthreads();
+    const uint32_t cols = g == 2 ? live_cols : live_cols & ~7u;   // directions that are not literal zeros
+    if (dnd)
+      for (int idx = lane; idx < DD_MENV; idx += 64) {
+        const int hi = idx / BD_NCOL, lo = idx - hi * BD_NCOL;
+        const int c = transposed ? lo : hi, x = transposed ? hi : lo;   // row of nudot, direction
+        float v = sX[x][c];
+#pragma unroll
+        for (int i = 0; i < CD_MAXROWS; ++i)
+          if (i < m) v += sY[i][c] * sZ[i][x];
+        dnd[e * DD_MENV + idx] = (((live_cols >> c) & 1u) && ((cols >> x) & 1u)) ? v : 0.f;
+      }
+    if (dlam)
+      for (int idx = lane; idx < m * BD_NCOL; idx += 64) {
+        const int i = transposed ? idx % m : idx / BD_NCOL, x = transposed ? idx / m : idx - i * BD_NCOL;
+        dlam[e * (size_t)(m * BD_NCOL) + idx] = (((act >> i) & 1u) && ((cols >> x) & 1u)) ? sZ[i][x] : 0.f;
+      }
+    __syncthreads();
+  }
+}
+
+// Workspace layout (floats): wbc_sim_constrained_dynamics' own; lambda [N, 16] for the call without a lambda output; -dr1/dq and -dr1/dnu
+// [N, 26, 26] ([direction][row]); the three solve results of the same shape; dr2/dq, dr2/dnu [N, 2, 15, 26]; one 26 x 26 identity.
+extern "C" size_t wbc_sim_constrained_dynamics_derivatives_workspace_floats(int num_envs, int nbodies) {
+  const size_t base = wbc_sim_constrained_dynamics_workspace_floats(num_envs, nbodies);
+  return base ? base + (size_t)num_envs * (CD_GSTRIDE + 5 * DD_MENV + CT_R2ENV) + DD_MENV : 0;
+}
+
+// Launches on `stream`: the four of wbc_sim_constrained_dynamics, wbc_dynamics_derivatives_kernel at that nudot, the tangent kernel (if a
+// q or nu output is asked for), one mass solve of 26 right-hand sides per requested group, the solve kernel. Arguments: include/wbc_sim.h.
+extern "C" int wbc_sim_constrained_dynamics_derivatives(wbc_sim* s, const int32_t* rigid_bodies, int nbodies, const uint8_t* active,
+                                                        const float* tau, const float* acc_des, float damping, int flags, float* nudot,
+                                                        float* lambda, float* dnudot_dq, float* dnudot_dnu, float* dnudot_dtau,
+                                                        float* dlambda_dq, float* dlambda_dnu, float* dlambda_dtau, float* workspace,
+                                                        void* stream) {
+  WbCall c("wbc_sim_constrained_dynamics_derivatives", s, stream);
+  if (!s) return c.no_sim();
+  if (!rigid_bodies || !nudot || !workspace) return c.fail(-1, "rigid_bodies / nudot / workspace is NULL");
+  if (!dnudot_dq && !dnudot_dnu && !dnudot_dtau && !dlambda_dq && !dlambda_dnu && !dlambda_dtau)
+    return c.fail(-1, "all six derivative outputs are NULL");
+  if (flags & ~(WBC_SOLVE_ARMATURE | WBC_DERIV_TRANSPOSED)) return c.fail(-1, "unknown flag bits");
+  if (((uintptr_t)dnudot_dq | (uintptr_t)dnudot_dnu | (uintptr_t)dnudot_dtau | (uintptr_t)dlambda_dq | (uintptr_t)dlambda_dnu |
+       (uintptr_t)dlambda_dtau) & 3u)
+    return c.fail(-1, "the derivative outputs must be 4-byte aligned");
+  const size_t base = wbc_sim_constrained_dynamics_workspace_floats(c.n, nbodies);   // 0: refused below
+  const int n = c.n;
+  const size_t blk = (size_t)(n > 0 ? n : 0) * DD_MENV;
+  float* lam = lambda ? lambda : workspace + base;
+  const int solve_flags = flags & WBC_SOLVE_ARMATURE;
+  CtConst T;
+  {
+    CdConst C;
+    const int rc = constrained_dynamics_run(c, s, rigid_bodies, nbodies, active, tau, acc_des, damping, solve_flags, nudot, lam, workspace,
+                                            stream, C);
+    if (rc != 0 || n <= 0) return rc;
+    static_cast<TreeWalk&>(T) = C; static_cast<TreeRigid&>(T) = C; static_cast<TreeCols&>(T) = C;
+    T.nb = C.nb;
+    for (int k = 0; k < WBC_CONSTR_MAX_BODIES; ++k) T.rb[k] = C.rb[k];
+  }
+  T.npair = 0;
+  for (int k = 0; k < nbodies; ++k) {
+    const int b = T.rb_body[T.rb[k]];
+    int depth = 0;
+    while (depth < WBC_MAX_DEPTH && T.path[b][depth] >= 0) ++depth;
+    for (int u = 0; u < 3 + depth; ++u) { T.pair_k[T.npair] = (uint8_t)k; T.pair_u[T.npair] = (uint8_t)u; ++T.npair; }
+  }
+  for (int i = T.npair; i < CT_MAXPAIR; ++i) { T.pair_k[i] = 0; T.pair_u[i] = 0; }
+  uint32_t live_cols = 63u;
+  for (int d = 0; d < WBC_NDOF; ++d) if (T.col_body[d] >= 0) live_cols |= 1u << (6 + d);
+  const bool gq = dnudot_dq || dlambda_dq, gn = dnudot_dnu || dlambda_dnu;
+  const int nrow = 3 * nbodies + 1;
+  const float *jblk = workspace, *Y = workspace + (size_t)n * nrow * BD_NCOL;
+  float* w = workspace + base + (size_t)n * CD_GSTRIDE;
+  float *rq = gq ? w : nullptr, *rn = gn ? w + blk : nullptr;
+  float *xq = w + 2 * blk, *xn = w + 3 * blk, *xm = w + 4 * blk, *r2 = w + 5 * blk, *eye = dnudot_dtau ? r2 + (size_t)n * CT_R2ENV : nullptr;
+  int rc;
+  if ((gq || gn || eye) && (rc = derivatives_launch(c, nudot, rq, rn, eye, 1, 1, stream)) != 0) return rc;
+  if (gq || gn) {
+    hipLaunchKernelGGL(wbc_constraint_tangent_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, T, c.root, c.dofs, active, (const float*)nudot,
+                       (const float*)lam, n, gq ? 1 : 0, gn ? 1 : 0, rq, r2);
+    if ((rc = c.launched()) != 0) return rc;
+  }
+  if (gq && (rc = mass_solve_launch(c, rq, DD_MENV, BD_NCOL, nullptr, xq, solve_flags, stream)) != 0) return rc;
+  if (gn && (rc = mass_solve_launch(c, rn, DD_MENV, BD_NCOL, nullptr, xn, solve_flags, stream)) != 0) return rc;
+  if (eye && (rc = mass_solve_launch(c, eye, 0, BD_NCOL, nullptr, xm, solve_flags, stream)) != 0) return rc;
+  CsOut O;
+  O.dnd[0] = dnudot_dq; O.dnd[1] = dnudot_dnu; O.dnd[2] = dnudot_dtau;
+  O.dlam[0] = dlambda_dq; O.dlam[1] = dlambda_dnu; O.dlam[2] = dlambda_dtau;
+  O.X[0] = xq; O.X[1] = xn; O.X[2] = eye ? xm : nullptr;
+  hipLaunchKernelGGL(wbc_constraint_derivatives_solve_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, jblk, Y, (const float*)r2, active, damping,
+                     nbodies, live_cols, n, (flags & WBC_DERIV_TRANSPOSED) ? 1 : 0, O);
+  return c.launched();
 }
 
 // ---- whole-body inverse dynamics for task-space accelerations (include/wbc_sim.h: wbc_sim_task_inverse_dynamics) ---------------------

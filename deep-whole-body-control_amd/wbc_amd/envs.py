@@ -537,6 +537,16 @@ class WidowGo1(LeggedRobot):
             self._feet_list = [int(i) for i in self.feet_indices.tolist()]
         return self.sim.constrained_dynamics(self._feet_list, tau=tau, active=stance, armature=armature)
 
+    def stance_forward_dynamics_derivatives(self, tau: torch.Tensor = None, stance: torch.Tensor = None, armature: bool = False):
+        """stance_forward_dynamics linearised: (nudot [N, 26], foot_forces [N, 4, 3], dnudot_dq, dnudot_dnu, dnudot_dtau [N, 26, 26],
+        dforces_dq, dforces_dnu, dforces_dtau [N, 12, 26]) with [e, i, j] = d (.)_i / d x_j, in the tangent convention of
+        inverse_dynamics_derivatives; the rows of a swing foot are exactly 0 (include/wbc_sim.h:
+        wbc_sim_constrained_dynamics_derivatives)."""
+        if self.__dict__.get("_feet_list") is None:
+            self._feet_list = [int(i) for i in self.feet_indices.tolist()]
+        r = self.sim.constrained_dynamics_derivatives(self._feet_list, tau=tau, active=stance, armature=armature)
+        return (r["nudot"], r["lambda"]) + tuple(r[k] for k in self.sim.CDD_OUTPUTS)
+
     def whole_body_inverse_dynamics(self, base_acc: torch.Tensor = None, ee_acc: torch.Tensor = None, swing_acc: torch.Tensor = None,
                                     stance: torch.Tensor = None, qdd_ref: torch.Tensor = None, weights: dict = None,
                                     armature: bool = False):

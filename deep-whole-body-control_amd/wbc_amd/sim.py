@@ -464,6 +464,52 @@ class WbcSim:
                                                           self._fdd_ws.data_ptr(), self._stream()), "wbc_sim_forward_dynamics_derivatives")
         return (nudot,) + tuple(outs)
 
+    CDD_OUTPUTS = ("dnudot_dq", "dnudot_dnu", "dnudot_dtau", "dlambda_dq", "dlambda_dnu", "dlambda_dtau")
+
+    def constrained_dynamics_derivatives(self, rigid_bodies, tau: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,
+                                         acc_des: Optional[torch.Tensor] = None, damping: float = 0.0, armature: bool = False,
+                                         transposed: bool = False, want=CDD_OUTPUTS, out=None):
+        """wbc_sim_constrained_dynamics_derivatives on the current stream: constrained_dynamics' (nudot [N, 26], lam [N, K, 3]) for the
+        same arguments and the partial derivatives of both with respect to q, nu and tau, in the tangent convention of
+        inverse_dynamics_derivatives. Returns a dict with "nudot", "lambda" and the names in `want` (a subset of CDD_OUTPUTS; an
+        output that is not wanted costs neither its walks nor its solves): dnudot_* f32 [N, 26, 26] with [e, i, j] = d nudot_i / d x_j,
+        dlambda_* f32 [N, 3 K, 26] with [e, i, j] = d lambda_i / d x_j; with transposed [e, j, i], i.e. [N, 26, 26] and [N, 26, 3 K].
+        out: an optional dict of caller-owned tensors under the same names (the rest are allocated). The workspace is cached per
+        number of bodies."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        rbs = [int(r) for r in (rigid_bodies.tolist() if isinstance(rigid_bodies, torch.Tensor) else rigid_bodies)]
+        k = len(rbs)
+        assert 1 <= k <= 5, k
+        want = tuple(want)
+        assert want and all(w in self.CDD_OUTPUTS for w in want), want
+        out = dict(out) if out is not None else {}
+        assert all(key in ("nudot", "lambda") + want for key in out), tuple(out)
+        shapes = {"nudot": (n, ncol), "lambda": (n, k, 3)}
+        for w in want:
+            rows = ncol if w.startswith("dnudot") else 3 * k
+            shapes[w] = (n, ncol, rows) if transposed else (n, rows, ncol)
+        res = {key: out[key] if out.get(key) is not None else torch.empty(sh, dtype=torch.float32, device=self.device)
+               for key, sh in shapes.items()}
+        for t, shape in [(tau, (n, ncol)), (acc_des, (n, k, 3))] + [(res[key], sh) for key, sh in shapes.items()]:
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, tuple(t.shape)
+        if active is not None:
+            assert active.device == self.arena.device and active.dtype in (torch.bool, torch.uint8) and tuple(active.shape) == (n, k)
+            active = active.contiguous()
+            if active.dtype == torch.bool:
+                active = active.view(torch.uint8)
+        cache = self.__dict__.setdefault("_cdd_ws", {})
+        if k not in cache:
+            cache[k] = torch.empty(int(self.L.wbc_sim_constrained_dynamics_derivatives_workspace_floats(n, k)), dtype=torch.float32,
+                                   device=self.device)
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        check(self.L.wbc_sim_constrained_dynamics_derivatives(self.h, (C.c_int32 * k)(*rbs), k, ptr(active), ptr(tau), ptr(acc_des),
+                                                              float(damping), (1 if armature else 0) | (2 if transposed else 0),
+                                                              res["nudot"].data_ptr(), res["lambda"].data_ptr(),
+                                                              *[ptr(res.get(w)) for w in self.CDD_OUTPUTS], cache[k].data_ptr(),
+                                                              self._stream()), "wbc_sim_constrained_dynamics_derivatives")
+        return res
+
     def episode_stats(self, scale: float, track_state: torch.Tensor = None, track_cap: int = 0) -> torch.Tensor:
         """Means over the envs that reset in the last step of their finished episode's reward sums [NREW] and metric
         sums [NMETRIC], times `scale`, as one fresh device tensor (WG:743-754 without a host sync). With `track_state`

@@ -868,6 +868,53 @@ size_t wbc_sim_forward_dynamics_derivatives_workspace_floats(int num_envs);
 int wbc_sim_forward_dynamics_derivatives(wbc_sim* sim, const float* tau, float* nudot, float* dnudot_dq, float* dnudot_dnu, float* minv,
                                          int flags, float* workspace, void* stream);
 
+/* First-order layer of wbc_sim_constrained_dynamics: the analytic partial derivatives of its solution (nudot, lambda) with respect to
+ * the configuration, the velocity and the applied force, in the tangent convention of wbc_sim_inverse_dynamics_derivatives above (dq =
+ * root translation, WORLD rotation vector, joint increments; the world components of nu, nudot, tau (all 26 rows), acc_des and lambda
+ * held fixed). The solution satisfies, with m = 3 nbodies,
+ *     r1 = ID(q, nu, nudot) [+ armature nudot] - Jc^T lambda - tau = 0        (26 rows; ID = wbc_sim_inverse_dynamics)
+ *     r2 = Jc nudot + (Jdot nu)_c - acc_des + damping lambda    = 0        (m rows: the classical acceleration of the listed origins)
+ * and with A = Jc M^-1 Jc^T, Y = M^-1 Jc^T and x one of the 26 directions of q or of nu
+ *     X = -M^-1 dr1/dx,   dlambda/dx = -(A + damping I)^-1 (Jc X + dr2/dx),   dnudot/dx = X + Y dlambda/dx,
+ *     dr1/dq = dtau_ID/dq (at the solution's nudot) - d(Jc^T lambda)/dq,   dr1/dnu = dtau_ID/dnu,
+ *     dr2/dq, dr2/dnu = the partials of the listed origins' classical acceleration at fixed nudot,
+ *     dnudot/dtau = M^-1 - Y (A + damping I)^-1 Y^T,   dlambda/dtau = -(A + damping I)^-1 Y^T.
+ * The armature is constant, so it changes M only. Along any motion with tau(t): d nudot / dt = (dnudot/dq) nu + (dnudot/dnu) nudot +
+ * (dnudot/dtau) dtau/dt at fixed acc_des, and likewise for lambda.
+ * rigid_bodies, nbodies (1..WBC_CONSTR_MAX_BODIES), active, tau, acc_des, damping: exactly as in wbc_sim_constrained_dynamics.
+ * flags     any of WBC_SOLVE_ARMATURE and WBC_DERIV_TRANSPOSED.
+ * nudot     device f32 [N, 26] (required), lambda device f32 [N, nbodies, 3] or NULL: the bits wbc_sim_constrained_dynamics writes for
+ *           the same arguments.
+ * dnudot_dq, dnudot_dnu, dnudot_dtau    device f32 [N, 26, 26], [e, i, j] = d nudot_i / d x_j;
+ * dlambda_dq, dlambda_dnu, dlambda_dtau device f32 [N, 3 nbodies, 26], [e, i, j] = d lambda_i / d x_j. With WBC_DERIV_TRANSPOSED the
+ *           layouts are [e, j, i]: [N, 26, 26] and [N, 26, 3 nbodies]. Any of the six may be NULL (not written, and neither its walks
+ *           nor its solves are run), not all six.
+ * Exact structure, written as literal zeros: columns 0:3 of the four q / nu outputs (the root position and linear velocity are never
+ * read: every output is bit-identical under a translation of the robot), the fingers' rows and columns 24, 25 everywhere, and the
+ * three rows of an inactive body in every dlambda_*. For an env with no active body the dnudot_* are the free robot's partials
+ * (wbc_sim_forward_dynamics_derivatives' formulas).
+ * workspace caller-owned device floats, at least wbc_sim_constrained_dynamics_derivatives_workspace_floats(N, nbodies) of them (0 for a
+ *           bad argument). Nothing is allocated in the call, so it is safe under stream capture on a single stream. The sim's
+ *           bias-force scratch is used as in wbc_sim_constrained_dynamics, with the same caveat: one stream at a time per sim. The
+ *           sim's state is read and never written.
+ * Launches on `stream`, no host synchronisation: the four of wbc_sim_constrained_dynamics; wbc_dynamics_derivatives_kernel at that
+ * nudot (-dtau_ID/dq, -dtau_ID/dnu, an identity if dnudot_dtau is wanted); wbc_constraint_tangent_kernel (dr2/dq, dr2/dnu and
+ * + d(Jc^T lambda)/dq) if a q or nu output is wanted; one wbc_mass_solve_kernel launch of 26 right-hand sides per requested group;
+ * wbc_constraint_derivatives_solve_kernel, which factorises A + damping I again and stores either layout directly. Ten launches for
+ * everything.
+ * -1 with a message in wbc_last_error(), nothing written, for everything wbc_sim_constrained_dynamics refuses, all six derivative
+ * outputs NULL, unknown flag bits or a pointer that is not 4-byte aligned; -3 / -2 as there.
+ * OUT OF SCOPE: the derivatives of wbc_sim_task_inverse_dynamics and wbc_sim_task_inverse_dynamics_qp (with or without an active set);
+ * angular constraint rows; partials with respect to acc_des (they are Y (A + damping I)^-1 for nudot and (A + damping I)^-1 for lambda:
+ * a caller with a Baumgarte law chains them itself); partials with respect to body parameters; second order. */
+size_t wbc_sim_constrained_dynamics_derivatives_workspace_floats(int num_envs, int nbodies);
+int wbc_sim_constrained_dynamics_derivatives(wbc_sim* sim, const int32_t* rigid_bodies /* host */, int nbodies, const uint8_t* active,
+                                             const float* tau, const float* acc_des, float damping, int flags,
+                                             float* nudot, float* lambda,
+                                             float* dnudot_dq, float* dnudot_dnu, float* dnudot_dtau,
+                                             float* dlambda_dq, float* dlambda_dnu, float* dlambda_dtau,
+                                             float* workspace, void* stream);
+
 /* extras["episode"] of reset_idx (widowGo1.py:743-754): out[0:WBC_NREW] = mean over the envs that reset in the last
  * step of their finished episode's reward sums, out[WBC_NREW:+WBC_NMETRIC] the same for the metric sums, both
  * times `scale` (1 / max_episode_length_s). `out`: device, WBC_NREW + WBC_NMETRIC floats. On a step in which no env reset

@@ -5,7 +5,8 @@ its own) and comparing the two files as raw 32-bit integers.
   WBC_AMD_LIB=/path/libwbc_amd.so python tools/dump_whole_body.py OUT.npz      dump
   python tools/dump_whole_body.py --compare A.npz B.npz                         exit status 1 unless every array is equal, bit for bit
 
-Envs n = 1, 13, 64 (13: the idle half-workgroup of the two-envs-per-workgroup kernels is live); states and body parameters from the
+Envs n = 1, 13, 64 (13: the idle half-workgroup of the two-envs-per-workgroup kernels is live), and n = 273 for
+wbc_sim_constrained_dynamics_derivatives alone (arrays a dump of an older library lacks count as differences: compare like with like); states and body parameters from the
 generators of tests/test_mass_solve.py. Every array is float32: of task_inverse_dynamics_qp's integer outputs, status and iterations are
 stored by value (exact below 2^24, asserted) and the int64 active_set as its two 32-bit words, reinterpreted and not converted.
 """
@@ -62,7 +63,20 @@ def keep_qp(name, tau, nudot, lam, info):
           f"{len(aset)} envs, contact rows in {int((aset >> 36 != 0).sum())}")
 
 
-for n in (1, 13, 64):
+def keep_cdd(sim, name, feet, grip, tau, g):
+    """wbc_sim_constrained_dynamics_derivatives: feet masked; feet + gripper with damping; armature + transposed."""
+    n = sim.num_envs
+    act = (torch.rand(n, 4, device="cuda", generator=g) < 0.6)
+    order = ("nudot", "lambda") + sim.CDD_OUTPUTS
+    r = sim.constrained_dynamics_derivatives(feet, tau=tau, active=act)
+    keep(name + "cdd.4", *[r[k] for k in order])
+    r = sim.constrained_dynamics_derivatives(feet + [grip], tau=tau, damping=1e-3)
+    keep(name + "cdd.5", *[r[k] for k in order])
+    r = sim.constrained_dynamics_derivatives(feet, tau=None, armature=True, transposed=True)
+    keep(name + "cdd.4.a1.t1", *[r[k] for k in order])
+
+
+for n in (1, 13, 64, 273):
     cfg = WidowGo1RoughCfg(); cfg.env.num_envs = n; cfg.terrain.mesh_type = "plane"
     env = WidowGo1(cfg, sim_device="cuda:0", seed=5)
     sim, m, dev = env.sim, env.robot_model, "cuda"
@@ -82,6 +96,9 @@ for n in (1, 13, 64):
     tau = rnd(n, 26, scale=10.0)
     feet, grip = [int(i) for i in env.feet_indices.tolist()], int(env.gripper_idx)
     T = f"n{n}."
+    if n == 273:                                   # the new call alone at a size with a partial last workgroup of every two-env kernel
+        keep_cdd(sim, T, feet, grip, tau, g)
+        continue
 
     keep(T + "arm", *sim.arm_dynamics(env._arm_link_rb, m.rb_mass[-9:]))
     jac, mm = torch.empty(n, 27, 6, 26, device=dev), torch.empty(n, 26, 26, device=dev)
@@ -134,6 +151,7 @@ for n in (1, 13, 64):
     md = torch.empty(n, 26, 26, device=dev)
     fd = sim.forward_dynamics_derivatives(tau=None, minv=md)
     keep(T + "fdd.tau_null", *fd)
+    keep_cdd(sim, T, feet, grip, tau, g)           # last: the generator's earlier draws stay what they were
 
 np.savez(sys.argv[1], **out)
 print(f"{len(out)} arrays, {sum(a.size for a in out.values())} words -> {sys.argv[1]}")
