@@ -718,7 +718,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_mass_solve_kernel(MsConst C
                                                                       const float* __restrict__ body_params,
                                                                       const float* __restrict__ rhs, int64_t rhs_stride, int nrhs,
                                                                       const float* __restrict__ sub, int n, float* __restrict__ out,
-                                                                      int armature) {
+                                                                      int64_t out_stride, int armature) {
   __shared__ float sH[MS_EPW][MS_NS][MS_W];        // rows of M, then of L (unit lower, M = L^T D L)
   __shared__ float sID[MS_EPW][MS_NS];             // 1 / D
   __shared__ float sT[MS_EPW][MS_TN];
@@ -829,7 +829,7 @@ extern "C" __global__ void __launch_bounds__(64) wbc_mass_solve_kernel(MsConst C
   if (lane >= nrhs || !live) return;
   const float* bp = rhs ? rhs + e * rhs_stride + (size_t)lane * BD_NCOL : nullptr;
   const float* hp = sub ? sub + e * BD_NCOL : nullptr;
-  float* op = out + (e * nrhs + lane) * BD_NCOL;
+  float* op = out + e * out_stride + (size_t)lane * BD_NCOL;
   float* stash = sT[half] + lane;                  // [coordinate - 6][right-hand side]
   auto ld = [&](int s) { const int c = C.co_col[s]; return (bp ? bp[c] : 0.f) - (hp ? hp[c] : 0.f); };
   float xr[6];
@@ -912,13 +912,15 @@ static int ms_const_fill(const DevConst* hc, MsConst& C) {
   return 0;
 }
 
-static int mass_solve_launch(const WbCall& c, const float* rhs, int64_t rhs_env_stride, int nrhs, const float* sub, float* out, int flags, void* stream) {
+// out_env_stride (floats): 26 nrhs for the contiguous [N, nrhs, 26]; a caller that solves a wider block in chunks passes the block's own.
+static int mass_solve_launch(const WbCall& c, const float* rhs, int64_t rhs_env_stride, int nrhs, const float* sub, float* out,
+                             int64_t out_env_stride, int flags, void* stream) {
   if (!c.have) return c.no_state();
   if (c.n <= 0) return 0;
   MsConst C;
   if (ms_const_fill(c.hc, C) != 0) return c.no_tree();
   hipLaunchKernelGGL(wbc_mass_solve_kernel, dim3((c.n + MS_EPW - 1) / MS_EPW), dim3(64), 0, (hipStream_t)stream, C, c.root, c.dofs, c.bp, rhs,
-                     rhs_env_stride, nrhs, sub, c.n, out, (flags & WBC_SOLVE_ARMATURE) ? 1 : 0);
+                     rhs_env_stride, nrhs, sub, c.n, out, out_env_stride, (flags & WBC_SOLVE_ARMATURE) ? 1 : 0);
   return c.launched();
 }
 
@@ -931,21 +933,26 @@ extern "C" int wbc_sim_mass_solve(wbc_sim* s, const float* rhs, int64_t rhs_env_
   if (rhs_env_stride < (int64_t)BD_NCOL * nrhs) return c.fail(-1, "rhs_env_stride is below 26 * nrhs");
   if (flags & ~WBC_SOLVE_ARMATURE) return c.fail(-1, "unknown flag bits");
   if (((uintptr_t)rhs | (uintptr_t)out) & 3u) return c.fail(-1, "rhs / out must be 4-byte aligned");
-  return mass_solve_launch(c, rhs, rhs_env_stride, nrhs, nullptr, out, flags, stream);
+  return mass_solve_launch(c, rhs, rhs_env_stride, nrhs, nullptr, out, (int64_t)nrhs * BD_NCOL, flags, stream);
 }
 
 // nudot = M^-1 (tau - h): wbc_inverse_dynamics_kernel writes h into the sim's [N, 26] scratch, the solve subtracts it as it loads.
+// The two launches, arguments checked by the entry point c speaks for (wbc_sim_forward_dynamics, wbc_sim_forward_dynamics_sensitivity).
+static int forward_dynamics_run(const WbCall& c, wbc_sim* s, const float* tau, float* nudot, int flags, void* stream) {
+  float* h = nullptr;
+  if (wbc_sim_internal_fd_scratch(s, &h) != 0) return -1;
+  const int rc = wbc_sim_inverse_dynamics(s, nullptr, h, nullptr, stream);
+  if (rc != 0) return rc;
+  return mass_solve_launch(c, tau, BD_NCOL, 1, h, nudot, BD_NCOL, flags, stream);
+}
+
 extern "C" int wbc_sim_forward_dynamics(wbc_sim* s, const float* tau, float* nudot, int flags, void* stream) {
   WbCall c("wbc_sim_forward_dynamics", s, stream);
   if (!s) return c.no_sim();
   if (!nudot) return c.fail(-1, "nudot is NULL");
   if (flags & ~WBC_SOLVE_ARMATURE) return c.fail(-1, "unknown flag bits");
   if (((uintptr_t)tau | (uintptr_t)nudot) & 3u) return c.fail(-1, "tau / nudot must be 4-byte aligned");
-  float* h = nullptr;
-  if (wbc_sim_internal_fd_scratch(s, &h) != 0) return -1;
-  const int rc = wbc_sim_inverse_dynamics(s, nullptr, h, nullptr, stream);
-  if (rc != 0) return rc;
-  return mass_solve_launch(c, tau, BD_NCOL, 1, h, nudot, flags, stream);
+  return forward_dynamics_run(c, s, tau, nudot, flags, stream);
 }
 
 // ---- rigid-body accelerations and contact-constrained forward dynamics (include/wbc_sim.h) ---------------------------------------------
@@ -1199,7 +1206,7 @@ static int constrained_dynamics_run(const WbCall& c, wbc_sim* s, const int32_t* 
   const dim3 grid((n + BA_EPW - 1) / BA_EPW);
   hipLaunchKernelGGL(wbc_constraint_rhs_kernel, grid, dim3(64), 0, (hipStream_t)stream, C, c.root, c.dofs, active, tau, (const float*)h, n, blk, gamma);
   if ((rc = c.launched()) != 0) return rc;
-  rc = mass_solve_launch(c, blk, (int64_t)nrow * BD_NCOL, nrow, nullptr, Y, flags, stream);
+  rc = mass_solve_launch(c, blk, (int64_t)nrow * BD_NCOL, nrow, nullptr, Y, (int64_t)nrow * BD_NCOL, flags, stream);
   if (rc != 0) return rc;
   hipLaunchKernelGGL(wbc_constraint_solve_kernel, grid, dim3(64), 0, (hipStream_t)stream, (const float*)blk, (const float*)Y, (const float*)gamma, active,
                      acc_des, damping, nbodies, live_cols, n, nudot, lambda);
@@ -1678,12 +1685,256 @@ extern "C" int wbc_sim_forward_dynamics_derivatives(wbc_sim* s, const float* tau
   float* xq = tr ? dnudot_dq : workspace + 2 * blk;
   float* xn = tr ? dnudot_dnu : workspace + 3 * blk;
   float* xm = tr ? minv : workspace + 4 * blk;
-  if (dnudot_dq && (rc = mass_solve_launch(c, rq, DD_MENV, BD_NCOL, nullptr, xq, solve_flags, stream)) != 0) return rc;
-  if (dnudot_dnu && (rc = mass_solve_launch(c, rn, DD_MENV, BD_NCOL, nullptr, xn, solve_flags, stream)) != 0) return rc;
-  if (minv && (rc = mass_solve_launch(c, eye, 0, BD_NCOL, nullptr, xm, solve_flags, stream)) != 0) return rc;
+  if (dnudot_dq && (rc = mass_solve_launch(c, rq, DD_MENV, BD_NCOL, nullptr, xq, DD_MENV, solve_flags, stream)) != 0) return rc;
+  if (dnudot_dnu && (rc = mass_solve_launch(c, rn, DD_MENV, BD_NCOL, nullptr, xn, DD_MENV, solve_flags, stream)) != 0) return rc;
+  if (minv && (rc = mass_solve_launch(c, eye, 0, BD_NCOL, nullptr, xm, DD_MENV, solve_flags, stream)) != 0) return rc;
   if (!tr) {
     hipLaunchKernelGGL(wbc_derivatives_transpose_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, xq, dnudot_dq, xn, dnudot_dnu, xm, minv);
     return c.launched();
+  }
+  return 0;
+}
+
+// ---- body-parameter regressor of inverse dynamics (include/wbc_sim.h: wbc_sim_inverse_dynamics_regressor) --------------------------------
+// tau = Y(q, nu, nudot) pi: inverse dynamics is linear in every body's (m, m c, Ibar about the body's own origin, body axes). One env per
+// 64-lane workgroup, two phases, one LDS hand-over:
+//  1) lane b = moving body b: ba_walk root -> b (angular velocity, angular acceleration and the CLASSICAL acceleration of the body's own
+//     origin, every lever a link offset), then E, p, the joint axis in F and, in BODY axes, w, alpha and d = E^T (a_o - g) go to LDS with
+//     the body's current (m, c). In body axes about the body origin the wrench of body b is closed form in these three vectors:
+//         force = m d + alpha x h + w x (w x h),   moment = h x d + Ibar alpha + w x Ibar w,   h = m c.
+//  2) work item = (coordinate c, listed body b in the subtree c moves): with u^ = E_b^T u_c and w^ = u^ x E_b^T (p_b - o_c), the lever
+//     between two origins of one chain, entry (c, b) is u^ . moment + w^ . force, column by column:
+//         m: w^ . d;   h: w^ x alpha + (w^ x w) x w + d x u^;   Ibar: sym(u^, alpha) + sym(u^ x w, w),
+//     sym(a, b) = (ax bx, ay by, az bz, ax by + ay bx, ax bz + az bx, ay bz + az by). The root rows take u_c = R^T e_j about F's origin
+//     (rows 0:3: the force alone, w^ = E_b^T R^T e_j, whose Ibar columns are literal zeros). With `native` the ten values are chained to
+//     d/d(m, c, I_c) at the body's own (m, c): Ibar = I_c + m (|c|^2 1 - c c^T).
+// The output of one env is assembled in LDS a chunk at a time (RG_STAGE floats: whole rows, or whole bodies when transposed), zero-filled
+// first -- the structural zeros and the fingers' rows are never computed -- and stored 16 bytes per lane. The root position is never read.
+#define RG_NP 10                                // parameters per body
+#define RG_BT 28                                // floats per body in LDS: E 0..8, p 9..11, joint axis in F 12..14, then body axes: w 15..17, alpha 18..20, d 21..23; m 24, c 25..27
+#define RG_STAGE (12 * WBC_NB * RG_NP)          // 12 rows of all bodies, or 8 bodies' 260 floats and a rest
+#define RG_TBODIES (RG_STAGE / (BD_NCOL * RG_NP))   // bodies per chunk, transposed
+#define RG_MAXCHUNK 3
+#define RG_MAXITEM (WBC_NB * (6 + WBC_MAX_DEPTH))   // every body under the six root rows and under the joints of its own path
+static_assert((BD_NCOL + 11) / 12 <= RG_MAXCHUNK && (WBC_NB + RG_TBODIES - 1) / RG_TBODIES <= RG_MAXCHUNK && RG_STAGE % 4 == 0, "chunks");
+static_assert((RG_STAGE + WBC_NB * RG_BT) * sizeof(float) <= 20 * 1024, "8 workgroups per CU");
+struct RgConst : IdConst {
+  int32_t nitem, nchunk;
+  int32_t stride_c, stride_s, stride_k;         // floats between rows, listed bodies and parameters of one env's output
+  int32_t env_floats;                           // 26 * 10 * listed bodies
+  int32_t chunk_item[RG_MAXCHUNK + 1];          // the items of chunk k: chunk_item[k] .. chunk_item[k + 1]
+  int32_t chunk_off[RG_MAXCHUNK], chunk_len[RG_MAXCHUNK];   // its floats of the env's output: first, count (both multiples of 4)
+  uint8_t item_c[RG_MAXITEM], item_b[RG_MAXITEM], item_s[RG_MAXITEM];   // row, moving body, the body's place in the caller's list
+};
+
+extern "C" __global__ void __launch_bounds__(64) wbc_inverse_dynamics_regressor_kernel(RgConst C, const float* __restrict__ root,
+                                                                                      const float* __restrict__ dofs,
+                                                                                      const float* __restrict__ body_params,
+                                                                                      const float* __restrict__ nudot, float* __restrict__ Y,
+                                                                                      int native, int negate) {
+  __shared__ __align__(16) float sStage[RG_STAGE];
+  __shared__ float sB[WBC_NB][RG_BT];
+  const int lane = threadIdx.x;
+  const size_t e = blockIdx.x;
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+
+  if (lane < WBC_NB) {
+    const int b = lane;
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    f3 p, w, aw, ao;
+    ba_walk(C, b, e, R, root, dofs, nudot, E, p, w, aw, ao);
+    const f3 gF = matT_mul(R, mk3(C.gravity[0], C.gravity[1], C.gravity[2]));
+    float m = C.mass[b], com[3] = {C.com[b][0], C.com[b][1], C.com[b][2]};
+    const int slot = b == 0 ? TREE_BP_ROOT : (b == C.gripper_body ? TREE_BP_GRIPPER : -1);
+    if (slot >= 0) {
+      const float* bp = body_params + e * TREE_BP_STRIDE + slot;
+      m = bp[0];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
+    }
+    float* o = sB[b];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) o[j] = E[j];
+    st3(o + 9, p); st3(o + 12, mat_mul(E, tree_axis(C.axis[b])));   // -1 for the root: no joint axis
+    st3(o + 15, matT_mul(E, w)); st3(o + 18, matT_mul(E, aw)); st3(o + 21, matT_mul(E, ao - gF));
+    o[24] = m; o[25] = com[0]; o[26] = com[1]; o[27] = com[2];
+  }
+  __syncthreads();
+
+  float4* stage4 = reinterpret_cast<float4*>(sStage);
+  float4* out4 = reinterpret_cast<float4*>(Y + e * (size_t)C.env_floats);
+  for (int ch = 0; ch < C.nchunk; ++ch) {
+    const int off = C.chunk_off[ch], len4 = C.chunk_len[ch] >> 2;
+    for (int t = lane; t < len4; t += 64) stage4[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    for (int it = C.chunk_item[ch] + lane; it < C.chunk_item[ch + 1]; it += 64) {
+      const int c = C.item_c[it], b = C.item_b[it], s = C.item_s[it];
+      const float* B = sB[b];
+      f3 u, lever = ld3(B + 9);
+      if (c < 6) {
+        const int j = c < 3 ? c : c - 3;
+        u = matT_mul(R, mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f));
+      } else {
+        const float* J = sB[C.col_body[c - 6]];
+        u = ld3(J + 12);
+        lever = lever - ld3(J + 9);
+      }
+      const f3 uh = matT_mul(B, u), w = ld3(B + 15), al = ld3(B + 18), d = ld3(B + 21);
+      const bool lin = c < 3;
+      const f3 wh = lin ? uh : cross(uh, matT_mul(B, lever));
+      float y[RG_NP];
+      y[0] = dot(wh, d);
+      f3 yh = cross(wh, al) + cross(cross(wh, w), w);
+      if (lin) {
+#pragma unroll
+        for (int k = 4; k < RG_NP; ++k) y[k] = 0.f;
+      } else {
+        yh = yh + cross(d, uh);
+        const f3 t = cross(uh, w);
+        y[4] = uh.x * al.x + t.x * w.x; y[5] = uh.y * al.y + t.y * w.y; y[6] = uh.z * al.z + t.z * w.z;
+        y[7] = (uh.x * al.y + uh.y * al.x) + (t.x * w.y + t.y * w.x);
+        y[8] = (uh.x * al.z + uh.z * al.x) + (t.x * w.z + t.z * w.x);
+        y[9] = (uh.y * al.z + uh.z * al.y) + (t.y * w.z + t.z * w.y);
+      }
+      y[1] = yh.x; y[2] = yh.y; y[3] = yh.z;
+      if (native) {                                          // d/d(m, c, I_c) from d/d(m, h, Ibar): h = m c, Ibar = I_c + m (|c|^2 1 - c c^T)
+        const float m = B[24], cx = B[25], cy = B[26], cz = B[27];
+        const float n0 = y[0] + (y[1] * cx + y[2] * cy + y[3] * cz) +
+                         ((y[4] * (cy * cy + cz * cz) + y[5] * (cx * cx + cz * cz) + y[6] * (cx * cx + cy * cy)) -
+                          (y[7] * (cx * cy) + y[8] * (cx * cz) + y[9] * (cy * cz)));
+        const float n1 = m * (y[1] + ((2.f * cx) * (y[5] + y[6]) - (y[7] * cy + y[8] * cz)));
+        const float n2 = m * (y[2] + ((2.f * cy) * (y[4] + y[6]) - (y[7] * cx + y[9] * cz)));
+        const float n3 = m * (y[3] + ((2.f * cz) * (y[4] + y[5]) - (y[8] * cx + y[9] * cy)));
+        y[0] = n0; y[1] = n1; y[2] = n2; y[3] = n3;
+      }
+      float* o = sStage + (c * C.stride_c + s * C.stride_s - off);
+#pragma unroll
+      for (int k = 0; k < RG_NP; ++k) o[k * C.stride_k] = negate ? -y[k] : y[k];
+    }
+    __syncthreads();
+    for (int t = lane; t < len4; t += 64) out4[(off >> 2) + t] = stage4[t];
+    __syncthreads();
+  }
+}
+
+// The caller's list of bodies (NULL with 0: all, in order) into sel / nsel. False: not 1..WBC_NB distinct indices in 0..WBC_NB-1.
+static bool rg_bodies(const int32_t* bodies, int nbodies, int32_t* sel, int& nsel) {
+  if (!bodies) {
+    if (nbodies != 0) return false;
+    for (int b = 0; b < WBC_NB; ++b) sel[b] = b;
+    nsel = WBC_NB;
+    return true;
+  }
+  if (nbodies < 1 || nbodies > WBC_NB) return false;
+  uint32_t seen = 0;
+  for (int i = 0; i < nbodies; ++i) {
+    if (bodies[i] < 0 || bodies[i] >= WBC_NB || ((seen >> bodies[i]) & 1u)) return false;
+    seen |= 1u << bodies[i];
+    sel[i] = bodies[i];
+  }
+  nsel = nbodies;
+  return true;
+}
+
+// Fills C from the model and the list: the chunks of the layout and, chunk by chunk, the (row, body) items that are not structural zeros.
+// 0, or 1: a tree the kernel cannot walk.
+static int rg_const_fill(const DevConst* hc, const int32_t* sel, int nsel, int transposed, RgConst& C) {
+  if (id_const_fill(hc, C) != 0) return 1;
+  const int np = nsel * RG_NP;
+  C.env_floats = BD_NCOL * np;
+  int per;                                                   // rows (an even number: every chunk starts on 16 bytes) or bodies per chunk
+  if (transposed) {
+    C.stride_c = 1; C.stride_s = BD_NCOL * RG_NP; C.stride_k = BD_NCOL;
+    per = RG_TBODIES;
+    C.nchunk = (nsel + per - 1) / per;
+  } else {
+    C.stride_c = np; C.stride_s = RG_NP; C.stride_k = 1;
+    per = RG_STAGE / np >= BD_NCOL ? BD_NCOL : (RG_STAGE / np) & ~1;
+    C.nchunk = (BD_NCOL + per - 1) / per;
+  }
+  const int total = transposed ? nsel : BD_NCOL, unit = transposed ? BD_NCOL * RG_NP : np;
+  C.nitem = 0;
+  for (int ch = 0; ch < RG_MAXCHUNK; ++ch) {
+    C.chunk_item[ch] = C.nitem;
+    const int lo = ch * per, hi = ch < C.nchunk ? (lo + per < total ? lo + per : total) : lo;
+    C.chunk_off[ch] = ch < C.nchunk ? lo * unit : 0;
+    C.chunk_len[ch] = ch < C.nchunk ? (hi - lo) * unit : 0;
+    if (ch >= C.nchunk) continue;
+    for (int c = 0; c < BD_NCOL; ++c) {
+      const int cb = c < 6 ? 0 : C.col_body[c - 6];
+      if (cb < 0) continue;                                  // a locked finger: its rows stay zero
+      for (int s = 0; s < nsel; ++s) {
+        const int key = transposed ? s : c;
+        if (key < lo || key >= hi || !((C.anc[sel[s]] >> cb) & 1u)) continue;
+        if (C.nitem >= RG_MAXITEM) return 1;
+        C.item_c[C.nitem] = (uint8_t)c; C.item_b[C.nitem] = (uint8_t)sel[s]; C.item_s[C.nitem] = (uint8_t)s;
+        ++C.nitem;
+      }
+    }
+  }
+  C.chunk_item[RG_MAXCHUNK] = C.nitem;
+  for (int i = C.nitem; i < RG_MAXITEM; ++i) { C.item_c[i] = 0; C.item_b[i] = 0; C.item_s[i] = 0; }
+  return 0;
+}
+
+static int regressor_launch(const WbCall& c, const int32_t* sel, int nsel, const float* nudot, float* Y, int native, int transposed, int negate,
+                            void* stream) {
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
+  RgConst C;
+  if (rg_const_fill(c.hc, sel, nsel, transposed, C) != 0) return c.no_tree();
+  hipLaunchKernelGGL(wbc_inverse_dynamics_regressor_kernel, dim3(c.n), dim3(64), 0, (hipStream_t)stream, C, c.root, c.dofs, c.bp, nudot, Y, native,
+                     negate);
+  return c.launched();
+}
+
+// bodies (host, or NULL with 0 = all), nudot (device f32 [N,26] or NULL = zeros), Y (device f32 [N,26,nbodies,10], 16-byte aligned): include/wbc_sim.h.
+extern "C" int wbc_sim_inverse_dynamics_regressor(wbc_sim* s, const int32_t* bodies, int nbodies, const float* nudot, float* Y, int flags,
+                                                  void* stream) {
+  WbCall c("wbc_sim_inverse_dynamics_regressor", s, stream);
+  if (!s) return c.no_sim();
+  if (!Y) return c.fail(-1, "Y is NULL");
+  int32_t sel[WBC_NB];
+  int nsel = 0;
+  if (!rg_bodies(bodies, nbodies, sel, nsel)) return c.fail(-1, "bodies must be 1..WBC_NB distinct moving-body indices, or NULL with nbodies 0");
+  if (flags & ~(WBC_DERIV_TRANSPOSED | WBC_REGRESSOR_NATIVE)) return c.fail(-1, "unknown flag bits");
+  if (((uintptr_t)nudot & 3u) || ((uintptr_t)Y & 15u)) return c.fail(-1, "nudot must be 4-byte aligned, Y 16-byte aligned");
+  return regressor_launch(c, sel, nsel, nudot, Y, (flags & WBC_REGRESSOR_NATIVE) ? 1 : 0, (flags & WBC_DERIV_TRANSPOSED) ? 1 : 0, 0, stream);
+}
+
+// nudot = M^-1 (tau - h), then d nudot / d(parameters) = -M^-1 Y(q, nu, nudot): the regressor leaves -Y^T, one parameter's 26 values per
+// right-hand side, in the workspace, and the solves go over it WBC_SOLVE_MAX_RHS columns at a time (include/wbc_sim.h).
+extern "C" int wbc_sim_forward_dynamics_sensitivity(wbc_sim* s, const int32_t* bodies, int nbodies, const float* tau, float* nudot,
+                                                    float* dnudot_dpi, float* workspace, int flags, void* stream) {
+  WbCall c("wbc_sim_forward_dynamics_sensitivity", s, stream);
+  if (!s) return c.no_sim();
+  if (!nudot || !dnudot_dpi || !workspace) return c.fail(-1, "nudot / dnudot_dpi / workspace is NULL");
+  int32_t sel[WBC_NB];
+  int nsel = 0;
+  if (!rg_bodies(bodies, nbodies, sel, nsel)) return c.fail(-1, "bodies must be 1..WBC_NB distinct moving-body indices, or NULL with nbodies 0");
+  if (flags & ~(WBC_SOLVE_ARMATURE | WBC_REGRESSOR_NATIVE)) return c.fail(-1, "unknown flag bits");
+  if ((((uintptr_t)tau | (uintptr_t)nudot | (uintptr_t)dnudot_dpi) & 3u) || ((uintptr_t)workspace & 15u))
+    return c.fail(-1, "tau / nudot / dnudot_dpi must be 4-byte aligned, workspace 16-byte aligned");
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
+  const int ncol = nsel * RG_NP;
+  const int64_t env_stride = (int64_t)ncol * BD_NCOL;
+  // nudot is written by the first two launches and read by the regressor while the workspace is written: none of the three may share bytes
+  const uintptr_t bytes = (uintptr_t)c.n * env_stride * sizeof(float), x0 = (uintptr_t)dnudot_dpi, w0 = (uintptr_t)workspace;
+  const uintptr_t n0 = (uintptr_t)nudot, nbytes = (uintptr_t)c.n * BD_NCOL * sizeof(float);
+  if (x0 < w0 + bytes && w0 < x0 + bytes) return c.fail(-1, "dnudot_dpi overlaps workspace");
+  if ((n0 < w0 + bytes && w0 < n0 + nbytes) || (n0 < x0 + bytes && x0 < n0 + nbytes)) return c.fail(-1, "nudot overlaps dnudot_dpi / workspace");
+  const int solve_flags = flags & WBC_SOLVE_ARMATURE;
+  int rc = forward_dynamics_run(c, s, tau, nudot, solve_flags, stream);
+  if (rc != 0) return rc;
+  rc = regressor_launch(c, sel, nsel, nudot, workspace, (flags & WBC_REGRESSOR_NATIVE) ? 1 : 0, 1, 1, stream);
+  if (rc != 0) return rc;
+  for (int k0 = 0; k0 < ncol; k0 += WBC_SOLVE_MAX_RHS) {
+    const int k = ncol - k0 < WBC_SOLVE_MAX_RHS ? ncol - k0 : WBC_SOLVE_MAX_RHS;
+    rc = mass_solve_launch(c, workspace + (size_t)k0 * BD_NCOL, env_stride, k, nullptr, dnudot_dpi + (size_t)k0 * BD_NCOL, env_stride,
+                           solve_flags, stream);
+    if (rc != 0) return rc;
   }
   return 0;
 }
@@ -1990,9 +2241,9 @@ extern "C" int wbc_sim_constrained_dynamics_derivatives(wbc_sim* s, const int32_
                        (const float*)lam, n, gq ? 1 : 0, gn ? 1 : 0, rq, r2);
     if ((rc = c.launched()) != 0) return rc;
   }
-  if (gq && (rc = mass_solve_launch(c, rq, DD_MENV, BD_NCOL, nullptr, xq, solve_flags, stream)) != 0) return rc;
-  if (gn && (rc = mass_solve_launch(c, rn, DD_MENV, BD_NCOL, nullptr, xn, solve_flags, stream)) != 0) return rc;
-  if (eye && (rc = mass_solve_launch(c, eye, 0, BD_NCOL, nullptr, xm, solve_flags, stream)) != 0) return rc;
+  if (gq && (rc = mass_solve_launch(c, rq, DD_MENV, BD_NCOL, nullptr, xq, DD_MENV, solve_flags, stream)) != 0) return rc;
+  if (gn && (rc = mass_solve_launch(c, rn, DD_MENV, BD_NCOL, nullptr, xn, DD_MENV, solve_flags, stream)) != 0) return rc;
+  if (eye && (rc = mass_solve_launch(c, eye, 0, BD_NCOL, nullptr, xm, DD_MENV, solve_flags, stream)) != 0) return rc;
   CsOut O;
   O.dnd[0] = dnudot_dq; O.dnd[1] = dnudot_dnu; O.dnd[2] = dnudot_dtau;
   O.dlam[0] = dlambda_dq; O.dlam[1] = dlambda_dnu; O.dlam[2] = dlambda_dtau;
@@ -2648,7 +2899,7 @@ static int taskid_launch(const char* who, wbc_sim* s, const int32_t* stance_bodi
   hipLaunchKernelGGL(wbc_taskid_rhs_kernel, dim3((n + BA_EPW - 1) / BA_EPW), dim3(64), 0, (hipStream_t)stream, C, c.root, c.dofs, active, (const float*)h,
                      n, blk, gamma, jt, gt);
   if ((rc = c.launched()) != 0) return rc;
-  rc = mass_solve_launch(c, blk, (int64_t)nr * BD_NCOL, nr, nullptr, Y, flags, stream);
+  rc = mass_solve_launch(c, blk, (int64_t)nr * BD_NCOL, nr, nullptr, Y, (int64_t)nr * BD_NCOL, flags, stream);
   if (rc != 0) return rc;
   if (!qp) {
     hipLaunchKernelGGL(wbc_taskid_solve_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, T, (const float*)blk, (const float*)Y, (const float*)gamma,

@@ -106,6 +106,9 @@ class WbcTaskIdWeights(C.Structure):
 
 
 TASKQP_MAX_ITER = 128     # WBC_TASKQP_MAX_ITER
+SOLVE_ARMATURE, DERIV_TRANSPOSED, REGRESSOR_NATIVE = 1, 2, 4   # WBC_SOLVE_ARMATURE, WBC_DERIV_TRANSPOSED, WBC_REGRESSOR_NATIVE: one `flags` word
+WBC_REGRESSOR_NATIVE = REGRESSOR_NATIVE
+NPARAM = 10               # inertial parameters per moving body (include/wbc_sim.h: wbc_sim_inverse_dynamics_regressor)
 
 
 class WbcTaskQpLimits(C.Structure):
@@ -652,6 +655,25 @@ def body_params_from_randomisation(m: RobotModel, base_dmass, base_dcom, gripper
                              np.broadcast_to(gp["inertia"], (n, 6)))
     out = np.concatenate([M0[:, None], C0, I0, M1[:, None], C1, I1], axis=1)
     return out.astype(np.float32)
+
+
+def linear_body_params(m: RobotModel, body_params=None) -> np.ndarray:
+    """pi, float64 [N, nb, 10]: the parameters inverse dynamics is linear in (include/wbc_sim.h: wbc_sim_inverse_dynamics_regressor),
+    (m, m c, Ibar xx yy zz xy xz yz) with Ibar = I_c + m (|c|^2 1 - c c^T) the rotational inertia about the body's own origin. Every
+    body from the model; the root composite and the gripper body from body_params [N, 20] (or [20]: N = 1) where given."""
+    nb = m.nb
+    theta = np.concatenate([np.asarray(m.mass, dtype=np.float64).reshape(nb, 1), np.asarray(m.com, dtype=np.float64).reshape(nb, 3),
+                            np.asarray(m.inertia, dtype=np.float64).reshape(nb, 6)], axis=1)[None]
+    if body_params is not None:
+        bp = np.asarray(body_params, dtype=np.float64).reshape(-1, 20)
+        theta = np.repeat(theta, bp.shape[0], axis=0)
+        theta[:, 0] = bp[:, 0:10]
+        theta[:, m.gripper_piece["body"]] = bp[:, 10:20]
+    mass, c, I = theta[..., 0], theta[..., 1:4], theta[..., 4:10]
+    cc = (c * c).sum(-1)
+    shift = np.stack([cc - c[..., 0] ** 2, cc - c[..., 1] ** 2, cc - c[..., 2] ** 2,
+                      -c[..., 0] * c[..., 1], -c[..., 0] * c[..., 2], -c[..., 1] * c[..., 2]], axis=-1)
+    return np.concatenate([mass[..., None], mass[..., None] * c, I + mass[..., None] * shift], axis=-1)
 
 
 DEFAULT_ASSET = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "widowgo1_default.wbcasset")

@@ -632,6 +632,19 @@ class WidowGo1(LeggedRobot):
         d nudot = dnudot_dq dq + dnudot_dnu dnu + minv dtau a trajectory optimiser needs."""
         return self.sim.forward_dynamics_derivatives(tau, armature=armature)
 
+    # ---- body parameters (no counterpart in the reference): include/wbc_sim.h: wbc_sim_inverse_dynamics_regressor ----
+    def body_parameter_regressor(self, nudot: torch.Tensor = None) -> torch.Tensor:
+        """Y, a fresh f32 [N, 26, 19, 10]: inverse_dynamics(nudot) == sum_b Y[:, :, b] @ pi_b with pi_b = (m, m c, inertia about the
+        body origin) of every moving body (abi.linear_body_params(robot_model, body_params)); Y holds no body parameter. One launch:
+        the rows of logged (state, torque) pairs for identifying a payload by least squares."""
+        return self.sim.inverse_dynamics_regressor(nudot=nudot)
+
+    def randomised_parameter_sensitivity(self, nudot: torch.Tensor = None) -> torch.Tensor:
+        """A fresh f32 [N, 26, 20]: d inverse_dynamics(nudot) / d BODY_PARAMS, column for column (root composite (m, com, inertia about
+        the centre of mass) at 0:10, gripper body at 10:20), at every env's own randomised values. One launch."""
+        bodies = (0, int(self.robot_model.gripper_piece["body"]))
+        return self.sim.inverse_dynamics_regressor(bodies, nudot=nudot, native=True).view(self.num_envs, 6 + abi.NDOF, 20)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])

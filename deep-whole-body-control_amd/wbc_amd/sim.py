@@ -464,6 +464,71 @@ class WbcSim:
                                                           self._fdd_ws.data_ptr(), self._stream()), "wbc_sim_forward_dynamics_derivatives")
         return (nudot,) + tuple(outs)
 
+    # ---- body-parameter regressor of inverse dynamics (include/wbc_sim.h: wbc_sim_inverse_dynamics_regressor) ---------------------------
+    def _regressor_bodies(self, bodies):
+        """(host index array or None, its length for the C-ABI, the number of bodies in the output)."""
+        if bodies is None:
+            return None, 0, abi.NB
+        idx = [int(b) for b in (bodies.tolist() if isinstance(bodies, torch.Tensor) else bodies)]
+        return (C.c_int32 * max(len(idx), 1))(*idx), len(idx), len(idx)
+
+    def inverse_dynamics_regressor(self, bodies=None, nudot: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                                   native: bool = False, transposed: bool = False) -> torch.Tensor:
+        """One wbc_sim_inverse_dynamics_regressor launch on the current stream: Y f32 [N, 26, K, 10] with [e, i, b, k] =
+        d tau_i / d (parameter k of bodies[b]) of inverse_dynamics(nudot) at the current state; bodies: distinct moving-body indices
+        (None: all nineteen, in order). Columns: the linear parameters (m, m c, inertia about the body origin; abi.linear_body_params),
+        so that sum_b Y[:, :, b] @ pi_b is tau; native: (m, c, inertia about the centre of mass), the parametrisation of BODY_PARAMS.
+        transposed: [N, K * 10, 26], what mass_solve reads. nudot f32 [N, 26], None: zeros. out: filled if given, else allocated."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        idx, k, nb = self._regressor_bodies(bodies)
+        shape = (n, nb * abi.NPARAM, ncol) if transposed else (n, ncol, nb, abi.NPARAM)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        for t, sh in ((nudot, (n, ncol)), (out, shape)):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        flags = (abi.DERIV_TRANSPOSED if transposed else 0) | (abi.REGRESSOR_NATIVE if native else 0)
+        check(self.L.wbc_sim_inverse_dynamics_regressor(self.h, idx, k, nudot.data_ptr() if nudot is not None else None, out.data_ptr(),
+                                                        flags, self._stream()), "wbc_sim_inverse_dynamics_regressor")
+        return out
+
+    def forward_dynamics_sensitivity(self, bodies=None, tau: Optional[torch.Tensor] = None, armature: bool = False, native: bool = False,
+                                     nudot: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                                     workspace: Optional[torch.Tensor] = None):
+        """wbc_sim_forward_dynamics_sensitivity on the current stream. Returns (nudot [N, 26], dnudot_dpi [N, K * 10, 26]): nudot =
+        M^-1 (tau - h) (tau None: zeros; the bits of forward_dynamics) and [e, b * 10 + k, i] = d nudot_i / d (parameter k of
+        bodies[b]) = -M^-1 Y, parameter-major. bodies, native: as inverse_dynamics_regressor; armature: M + diag(0_6, joint_armature)
+        in every solve. Outputs that are not passed are allocated. workspace: a caller-owned f32 tensor of the shape of dnudot_dpi;
+        None: one buffer kept on the sim, as large as the largest request so far (81 MB for all bodies at 4096 envs;
+        release_sensitivity_workspace() frees it)."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        idx, k, nb = self._regressor_bodies(bodies)
+        shape = (n, nb * abi.NPARAM, ncol)
+        if nudot is None:
+            nudot = torch.empty((n, ncol), dtype=torch.float32, device=self.device)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        for t, sh in ((tau, (n, ncol)), (nudot, (n, ncol)), (out, shape)):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        assert tau is None or abs(tau.data_ptr() - nudot.data_ptr()) >= 4 * nudot.numel(), "nudot overlaps tau"
+        if workspace is None:
+            if "_fds_ws" not in self.__dict__ or self._fds_ws.numel() < out.numel():
+                self._fds_ws = torch.empty(out.numel(), dtype=torch.float32, device=self.device)
+            workspace = self._fds_ws
+        else:
+            assert workspace.device == self.arena.device and workspace.dtype == torch.float32 and workspace.is_contiguous()
+            assert tuple(workspace.shape) == shape, tuple(workspace.shape)
+        flags = (abi.SOLVE_ARMATURE if armature else 0) | (abi.REGRESSOR_NATIVE if native else 0)
+        check(self.L.wbc_sim_forward_dynamics_sensitivity(self.h, idx, k, tau.data_ptr() if tau is not None else None, nudot.data_ptr(),
+                                                          out.data_ptr(), workspace.data_ptr(), flags, self._stream()),
+              "wbc_sim_forward_dynamics_sensitivity")
+        return nudot, out
+
+    def release_sensitivity_workspace(self) -> None:
+        """Drop the buffer forward_dynamics_sensitivity keeps between calls (the next call without a workspace allocates again)."""
+        self.__dict__.pop("_fds_ws", None)
+
     CDD_OUTPUTS = ("dnudot_dq", "dnudot_dnu", "dnudot_dtau", "dlambda_dq", "dlambda_dnu", "dlambda_dtau")
 
     def constrained_dynamics_derivatives(self, rigid_bodies, tau: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,

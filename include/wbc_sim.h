@@ -868,6 +868,55 @@ size_t wbc_sim_forward_dynamics_derivatives_workspace_floats(int num_envs);
 int wbc_sim_forward_dynamics_derivatives(wbc_sim* sim, const float* tau, float* nudot, float* dnudot_dq, float* dnudot_dnu, float* minv,
                                          int flags, float* workspace, void* stream);
 
+/* How wbc_sim_inverse_dynamics depends on the bodies' inertial parameters. Inverse dynamics is LINEAR in every moving body's ten
+ * parameters: tau = sum_b Y_b(q, nu, nudot) pi_b. One launch (wbc_inverse_dynamics_regressor_kernel) writes Y from the state sources of
+ * wbc_sim_inverse_dynamics: the sim's current root / DoF state, all three gravity components, nudot. The sim's state is read, never
+ * written.
+ * bodies  HOST array of nbodies distinct moving-body indices in 0..WBC_NB-1 (1..WBC_NB of them), the order of the output's body axis;
+ *         NULL with nbodies == 0: all nineteen, in order.
+ * nudot   device f32 [N, 26] or NULL (= zeros: the regressor of the bias vector h), in the convention of wbc_sim_inverse_dynamics.
+ * Y       device f32 [N, 26, nbodies, 10], caller-owned, 16-byte aligned: [e, i, b, k] = d tau_i / d (parameter k of bodies[b]); rows as
+ *         the rows of tau (0:3 net external force, 3:6 net external moment about the root origin, world axes, 6: joint torques). With
+ *         WBC_DERIV_TRANSPOSED the layout is [N, nbodies * 10, 26]: one parameter's 26 values are contiguous, the right-hand-side
+ *         layout wbc_sim_mass_solve reads.
+ * flags   any of WBC_DERIV_TRANSPOSED and WBC_REGRESSOR_NATIVE.
+ * Columns, default: the linear parameters pi_b = (m, m c_x, m c_y, m c_z, Ibar_xx, Ibar_yy, Ibar_zz, Ibar_xy, Ibar_xz, Ibar_yz), c the
+ *         centre of mass in body axes and Ibar the rotational inertia about the body's own ORIGIN in body axes,
+ *         Ibar = I_c + m (|c|^2 1 - c c^T). Then sum_b Y[:, :, b] pi_b equals tau of wbc_sim_inverse_dynamics(nudot) up to rounding,
+ *         with pi of the root and the gripper body formed from WBC_T_BODY_PARAMS and pi of the other bodies from wbc_model. Y itself does
+ *         not depend on any body parameter.
+ * Columns, WBC_REGRESSOR_NATIVE: d tau / d theta_b with theta_b = (m, c_x, c_y, c_z, I_c xx, yy, zz, xy, xz, yz), the parametrisation
+ *         of WBC_T_BODY_PARAMS and of wbc_model, with the inertia about the centre of mass, by the chain rule in the kernel at the body's
+ *         CURRENT theta (per env for the root composite and the gripper body). With bodies = (0, wbc_model.gripper_body) the output
+ *         [N, 26, 20] lines up column for column with WBC_T_BODY_PARAMS.
+ * Exact structure, written as literal zeros: the entries of joint row i for a body that is not in the subtree joint i moves, the
+ * fingers' rows 24, 25 (their entries of nudot and of qd are ignored) and the inertia columns of the force rows 0:3.
+ * The root POSITION is never read: the result is bit-identical under a translation of the robot. RIGID-BODY dynamics only, exactly as
+ * wbc_sim_inverse_dynamics. Nothing is allocated, so the call is safe under stream capture.
+ *
+ * wbc_sim_forward_dynamics_sensitivity: nudot = M^-1 (tau - h), the bits of wbc_sim_forward_dynamics, and how it depends on the same
+ * parameters, d nudot / d (parameter) = -M^-1 Y(q, nu, nudot) (M nudot + h = tau at fixed tau, differentiated).
+ * bodies, nbodies   as above.  tau device f32 [N, 26] or NULL (= zeros), nudot device f32 [N, 26] (required).
+ * dnudot_dpi  device f32 [N, nbodies * 10, 26], parameter-major ([e, b * 10 + k, i]): the solve's own layout.
+ * workspace   caller-owned device f32 of the same size, 16-byte aligned. nudot, dnudot_dpi and workspace share no bytes (an overlap is
+ *             refused; tau is only read, by the launches that write nudot). Nothing is allocated in the call,
+ *             so it is safe under stream capture on a single stream. The sim's bias-force scratch of wbc_sim_forward_dynamics is used
+ *             as well, with the same caveat: one stream at a time per sim.
+ * flags       any of WBC_SOLVE_ARMATURE (M + diag(0_6, joint_armature) in every solve; the armature is no body parameter) and
+ *             WBC_REGRESSOR_NATIVE (columns as above).
+ * Launches on `stream`, no host synchronisation: the two of wbc_sim_forward_dynamics; the regressor kernel at that nudot, writing -Y
+ * transposed into the workspace; one wbc_mass_solve_kernel launch per WBC_SOLVE_MAX_RHS columns (1 for two bodies, 6 for all nineteen).
+ * The fingers' entries are exactly 0.
+ * Both: -1 with a message in wbc_last_error(), nothing written, for a NULL sim / Y (/ nudot / dnudot_dpi / workspace), a bad `bodies`
+ * (NULL with nbodies != 0, nbodies outside 1..WBC_NB, an index out of range or repeated), unknown flag bits, a misaligned pointer or
+ * overlapping nudot / dnudot_dpi / workspace; -3 for a model whose tree the kernel cannot walk; -2 if a launch fails. Stream / device handling as
+ * wbc_sim_centroidal. */
+#define WBC_REGRESSOR_NATIVE 4   /* distinct from WBC_SOLVE_ARMATURE (1) and WBC_DERIV_TRANSPOSED (2): the functions share `flags` */
+int wbc_sim_inverse_dynamics_regressor(wbc_sim* sim, const int32_t* bodies /* host */, int nbodies, const float* nudot, float* Y, int flags,
+                                       void* stream);
+int wbc_sim_forward_dynamics_sensitivity(wbc_sim* sim, const int32_t* bodies /* host */, int nbodies, const float* tau, float* nudot,
+                                         float* dnudot_dpi, float* workspace, int flags, void* stream);
+
 /* First-order layer of wbc_sim_constrained_dynamics: the analytic partial derivatives of its solution (nudot, lambda) with respect to
  * the configuration, the velocity and the applied force, in the tangent convention of wbc_sim_inverse_dynamics_derivatives above (dq =
  * root translation, WORLD rotation vector, joint increments; the world components of nu, nudot, tau (all 26 rows), acc_des and lambda

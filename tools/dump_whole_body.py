@@ -4,9 +4,12 @@ its own) and comparing the two files as raw 32-bit integers.
 
   WBC_AMD_LIB=/path/libwbc_amd.so python tools/dump_whole_body.py OUT.npz      dump
   python tools/dump_whole_body.py --compare A.npz B.npz                         exit status 1 unless every array is equal, bit for bit
+  python tools/dump_whole_body.py --compare A.npz B.npz --allow-new             the same, but arrays that B alone holds are listed, not
+                                                                                counted: an older build's dump against a newer one's
 
 Envs n = 1, 13, 64 (13: the idle half-workgroup of the two-envs-per-workgroup kernels is live), and n = 273 for
-wbc_sim_constrained_dynamics_derivatives alone (arrays a dump of an older library lacks count as differences: compare like with like); states and body parameters from the
+wbc_sim_constrained_dynamics_derivatives alone (arrays that only one of the two dumps holds count as differences, unless --allow-new
+lets the second, newer dump hold more); states and body parameters from the
 generators of tests/test_mass_solve.py. Every array is float32: of task_inverse_dynamics_qp's integer outputs, status and iterations are
 stored by value (exact below 2^24, asserted) and the int64 active_set as its two 32-bit words, reinterpreted and not converted.
 """
@@ -20,6 +23,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if sys.argv[1:2] == ["--compare"]:
     A, B = np.load(sys.argv[2]), np.load(sys.argv[3])
     bad = sorted(set(A.files) ^ set(B.files))
+    if sys.argv[4:5] == ["--allow-new"]:
+        print(f"arrays of {sys.argv[3]} alone: {sorted(set(B.files) - set(A.files))}")
+        bad = sorted(set(A.files) - set(B.files))
     for k in sorted(set(A.files) & set(B.files)):
         a, b = A[k], B[k]
         if a.shape != b.shape or not np.array_equal(a.view(np.uint32), b.view(np.uint32)):
@@ -148,6 +154,15 @@ for n in (1, 13, 64, 273):
         keep_qp(T + "tqp.4_6.box" + A, *sim.task_inverse_dynamics_qp(**full, mu=0.6, fn_min=2.0, tau_limit=half))
         keep_qp(T + "tqp.0_6" + A, *sim.task_inverse_dynamics_qp((), tasks, full["task_acc"], w, nudot_ref=full["nudot_ref"], armature=arm,
                                                                  tau_limit=half))
+    # the body-parameter regressor: full, a subset, native, transposed; the sensitivity call for two bodies and for all
+    gb = int(m.gripper_piece["body"])
+    keep(T + "reg.full", sim.inverse_dynamics_regressor(nudot=nudot), sim.inverse_dynamics_regressor())
+    keep(T + "reg.subset", sim.inverse_dynamics_regressor([gb, 3, 0, 17, 9], nudot=nudot))
+    keep(T + "reg.native", sim.inverse_dynamics_regressor(nudot=nudot, native=True), env.randomised_parameter_sensitivity(nudot))
+    keep(T + "reg.t1", sim.inverse_dynamics_regressor(nudot=nudot, transposed=True), sim.inverse_dynamics_regressor([0, gb], native=True, transposed=True))
+    for arm in (False, True):
+        keep(T + f"sens.2.a{int(arm)}", *sim.forward_dynamics_sensitivity([0, gb], tau, armature=arm, native=True))
+        keep(T + f"sens.19.a{int(arm)}", *sim.forward_dynamics_sensitivity(None, tau, armature=arm))
     md = torch.empty(n, 26, 26, device=dev)
     fd = sim.forward_dynamics_derivatives(tau=None, minv=md)
     keep(T + "fdd.tau_null", *fd)
