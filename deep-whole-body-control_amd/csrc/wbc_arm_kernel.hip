@@ -1221,6 +1221,233 @@ extern "C" int wbc_sim_constrained_dynamics(wbc_sim* s, const int32_t* rigid_bod
   return constrained_dynamics_run(c, s, rigid_bodies, nbodies, active, tau, acc_des, damping, flags, nudot, lambda, workspace, stream, C);
 }
 
+// ---- contact impulses and post-impact velocities (include/wbc_sim.h: wbc_sim_impulse_dynamics) ------------------------------------------
+// The impulse-level counterpart of the call above: with u_r = J_r nu the pre-impact velocity of listed body r's origin,
+//     M (nu+ - nu) = iota + sum_r J_r^T Lambda_r ,    J_r nu+ + damping Lambda_r = vdes_r - e_r (u_r - vdes_r) .
+// No h enters, so there are three launches: the right-hand-side block [J_c^T | iota], the mass solve, the impulse solve.
+
+// The right-hand-side block [N, 3 nb + 1, 26] as wbc_constraint_rhs_kernel writes it, with iota (zeros where NULL or on a finger column)
+// in the last row. Positions and joint axes only: lane b < 19 = moving body b walks root -> b with frame steps alone (no velocity or
+// acceleration is carried: the pre-impact contact velocity is the product J nu, formed in the solve kernel) and leaves its joint axis
+// and origin (F) in LDS; lane 19 + k walks to listed body k and leaves its origin. Then lane c = column c writes its entry of every
+// row: a row is one 104-byte store of consecutive lanes.
+extern "C" __global__ void __launch_bounds__(64) wbc_impulse_rhs_kernel(CdConst C, const float* __restrict__ root, const float* __restrict__ dofs,
+                                                                       const uint8_t* __restrict__ active,
+                                                                       const float* __restrict__ impulse_ext, int n, float* __restrict__ rhs) {
+  __shared__ float sJ[BA_EPW][WBC_NB][6];          // joint axis, joint origin, in F
+  __shared__ float sX[BA_EPW][WBC_CONSTR_MAX_BODIES][3];   // listed body's origin in F
+  const int half = BA_EPW == 2 ? threadIdx.x >> 5 : 0, lane = BA_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
+  const int env = blockIdx.x * BA_EPW + half;
+  const bool live = env < n;
+  const size_t e = live ? env : n - 1;             // the idle half of the last workgroup recomputes the last env and stores nothing
+  const int nb = C.nb, nrow = 3 * nb + 1;
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+  if (lane < WBC_NB + nb) {
+    const bool body = lane < WBC_NB;
+    const int k = body ? 0 : lane - WBC_NB, r = C.rb[k];
+    const int b = body ? lane : C.rb_body[r];
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    f3 p = mk3(0.f, 0.f, 0.f);
+#pragma nounroll
+    for (int s = 0; s < WBC_MAX_DEPTH; ++s) {
+      const int a = C.path[b][s];
+      if (a < 0) break;
+      float Q[9];
+      const f3 ax = tree_joint_rot(C.axis[a], dofs[e * (2 * WBC_NDOF) + 2 * C.dof[a]], Q);
+      tree_frame_step(E, p, Q, C.joint_xyz[a], ax);
+    }
+    if (body) {
+      st3(sJ[half][b], mat_mul(E, tree_axis(C.axis[b])));    // -1 for the root: no joint axis
+      st3(sJ[half][b] + 3, p);
+    } else {
+      st3(sX[half][k], p + mat_mul(E, mk3(C.rb_offset[r][0], C.rb_offset[r][1], C.rb_offset[r][2])));
+    }
+  }
+  __syncthreads();
+  if (lane < BD_NCOL && live) {
+    const int c = lane, b = c < 6 ? 0 : C.col_body[c - 6], j = c < 3 ? c : c - 3;
+    const f3 ej = mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f);
+    float* o = rhs + e * (size_t)(nrow * BD_NCOL) + c;
+    for (int k = 0; k < nb; ++k) {
+      const bool act = active ? active[e * nb + k] != 0 : true;
+      f3 lin = mk3(0.f, 0.f, 0.f);
+      if (act) lin = rhs_jac_lin(C, c, b, C.rb_body[C.rb[k]], ej, R, ld3(sX[half][k]), sJ[half]);
+      o[(3 * k) * BD_NCOL] = lin.x; o[(3 * k + 1) * BD_NCOL] = lin.y; o[(3 * k + 2) * BD_NCOL] = lin.z;
+    }
+    o[3 * nb * BD_NCOL] = (b >= 0 && impulse_ext) ? impulse_ext[e * BD_NCOL + c] : 0.f;
+  }
+}
+
+// Per env, with m = 3 nb rows, J the rows of the right-hand-side block, iota its last row and Y = (M^-1 [J^T | iota])^T: the Delassus
+// matrix, its Cholesky factor and the lane solve are wbc_constraint_solve_kernel's (wbc_delassus.h), with the right-hand side
+// c_i = (vdes_i - e (u_i - vdes_i)) - u_i - (J dnu_free)_i; an inactive body's e and vdes are never loaded. u_i = sum_c J_ic nu_c is
+// the 26-term product in column order, lane c's nu_c (0 on a finger) handed to the row lanes by a shuffle. Then lane c = column c:
+// dnu_c = Y_iota,c + sum_k Y_kc Lambda_k, nu+_c = nu_c + dnu_c (nu_c itself where dnu_c is 0, so that -0 stays), and the generalised
+// impulse g_c = iota_c + sum_k J_kc Lambda_k, whose product with nu + dnu / 2 summed over the lanes of the half is T(nu+) - T(nu)
+// = g^T nu + g^T M^-1 g / 2: the quadratic form, not the difference of two energies.
+// MAP: X = (A + damping)^-1 diag(1 + e) J in place of J, one column per lane (delassus_column_solve), then P = 1 - Y^T X staged in LDS
+// as the env's contiguous [26, 26] block, which leaves in 16-byte stores (676 floats = 169 of them). Without MAP the kernel holds no
+// LDS beyond the sibling's. A single-wavefront workgroup: the __syncthreads() order the LDS traffic and cost no barrier instruction.
+#define IM_MAP_FLOATS (BD_NCOL * BD_NCOL)
+static_assert(IM_MAP_FLOATS % 4 == 0, "the map leaves in 16-byte stores");
+struct ImArgs {
+  const float *rhs, *Y, *root, *dofs;
+  const uint8_t* active;
+  const float *restitution, *vel_des;
+  float damping;
+  int nb;
+  uint32_t live_cols;
+  int n;
+  float *nu_plus, *impulse, *denergy, *dnu_dnu;
+};
+
+template <bool MAP>
+__device__ __forceinline__ void impulse_solve_body(const ImArgs& a, float* sP) {
+  __shared__ float sJ[BA_EPW][CD_MAXROWS][CD_LD], sY[BA_EPW][CD_MAXROWS + 1][CD_LD];
+  __shared__ float sA[BA_EPW][CD_MAXROWS][CD_MAXROWS + 1];   // lower triangle: A, then L
+  __shared__ float sD[BA_EPW][CD_MAXROWS + 1], sV[BA_EPW][CD_MAXROWS + 1];   // 1 / L_jj; the value handed round
+  const int half = BA_EPW == 2 ? threadIdx.x >> 5 : 0, lane = BA_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
+  const int env = blockIdx.x * BA_EPW + half;
+  const bool live = env < a.n;
+  const size_t e = live ? env : a.n - 1;           // the idle half of the last workgroup recomputes the last env and stores nothing
+  const int nb = a.nb, m = 3 * nb;
+  float (*J)[CD_LD] = sJ[half], (*Yt)[CD_LD] = sY[half];
+  float (*A)[CD_MAXROWS + 1] = sA[half];
+  float *D = sD[half], *V = sV[half];
+  const float *rp = a.rhs + e * (size_t)((m + 1) * BD_NCOL), *yp = a.Y + e * (size_t)((m + 1) * BD_NCOL);
+  for (int t = lane; t < (m + 1) * BD_NCOL; t += BA_LPE) {
+    const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+    Yt[r][c] = yp[t];
+    if (r < m) J[r][c] = rp[t];
+  }
+  uint32_t act = 0;                                // bit i: row i belongs to an active body
+  for (int k = 0; k < nb; ++k)
+    if (!a.active || a.active[e * nb + k]) act |= 7u << (3 * k);
+  __syncthreads();
+
+  delassus_fill(J, Yt, A, m, act, a.damping, lane, BA_LPE);
+  const int i = lane;
+  const bool row = i < m, on = row && ((act >> i) & 1u);
+  const bool lc = lane < BD_NCOL && ((a.live_cols >> lane) & 1u);
+  float v = 0.f;                                   // lane c: nu_c of the state, 0 on a finger and past the columns
+  if (lc) v = lane < 6 ? a.root[e * 26 + 7 + lane] : a.dofs[e * (2 * WBC_NDOF) + 2 * (lane - 6) + 1];
+  float ui = 0.f;                                  // lane i: the pre-impact velocity along row i
+  for (int c = 0; c < BD_NCOL; ++c) {
+    const float vc = __shfl(v, c, BA_LPE);
+    if (row) ui += J[i][c] * vc;
+  }
+  float ci = 0.f, e1 = 0.f;                        // e1 = 1 + e of the row's body (MAP)
+  if (on) {
+    float s = 0.f;
+    for (int c = 0; c < BD_NCOL; ++c) s += J[i][c] * Yt[m][c];
+    const float vd = a.vel_des ? a.vel_des[e * m + i] : 0.f;
+    const float er = a.restitution ? a.restitution[e * nb + i / 3] : 0.f;
+    ci = ((vd - er * (ui - vd)) - ui) - s;
+    e1 = 1.f + er;
+  }
+  delassus_cholesky(A, D, m, i);
+  delassus_lane_solve(A, D, V, m, i, ci);
+  if (live && a.impulse && row) a.impulse[e * m + i] = on ? V[i] : 0.f;
+  float gn = 0.f;                                  // this column's share of the energy change
+  if (lane < BD_NCOL) {
+    const int c = lane;
+    float dv = Yt[m][c], g = rp[m * BD_NCOL + c];
+    for (int k = 0; k < m; ++k) {
+      const float lk = ((act >> k) & 1u) ? V[k] : 0.f;
+      dv += Yt[k][c] * lk;
+      g += J[k][c] * lk;
+    }
+    if (lc) gn = g * (v + 0.5f * dv);
+    if (live) a.nu_plus[e * BD_NCOL + c] = lc ? (dv != 0.f ? v + dv : v) : 0.f;
+  }
+  if (a.denergy) {
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) gn += __shfl_xor(gn, off);
+    if (live && lane == 0) a.denergy[e] = gn;
+  }
+  if constexpr (MAP) {
+    float* P = sP + half * IM_MAP_FLOATS;
+    __syncthreads();                               // every lane has read J
+    if (row)
+      for (int c = 0; c < BD_NCOL; ++c) J[i][c] *= e1;   // 0 for an inactive row, whose J is 0 already
+    __syncthreads();
+    if (lane < BD_NCOL) delassus_column_solve(A, D, &J[0][lane], CD_LD, m);
+    __syncthreads();
+    for (int t = lane; t < IM_MAP_FLOATS; t += BA_LPE) {
+      const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+      float s = 0.f;
+      for (int k = 0; k < m; ++k) s += Yt[k][r] * J[k][c];
+      const bool lrc = ((a.live_cols >> r) & 1u) && ((a.live_cols >> c) & 1u);
+      P[t] = lrc ? (r == c ? 1.f : 0.f) - s : 0.f;
+    }
+    __syncthreads();
+    if (live) {
+      float4* o = reinterpret_cast<float4*>(a.dnu_dnu + e * (size_t)IM_MAP_FLOATS);
+      const float4* P4 = reinterpret_cast<const float4*>(P);
+      for (int t = lane; t < IM_MAP_FLOATS / 4; t += BA_LPE) o[t] = P4[t];
+    }
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(64) wbc_impulse_solve_kernel(ImArgs a) { impulse_solve_body<false>(a, nullptr); }
+
+extern "C" __global__ void __launch_bounds__(64) wbc_impulse_solve_map_kernel(ImArgs a) {
+  __shared__ __attribute__((aligned(16))) float sP[BA_EPW * IM_MAP_FLOATS];
+  impulse_solve_body<true>(a, sP);
+}
+
+// Workspace layout (floats): the right-hand-side block [N, 3 nb + 1, 26], the mass solve's output of the same shape.
+extern "C" size_t wbc_sim_impulse_dynamics_workspace_floats(int num_envs, int nbodies) {
+  if (num_envs <= 0 || nbodies < 1 || nbodies > WBC_CONSTR_MAX_BODIES) return 0;
+  return (size_t)num_envs * 2 * (size_t)(3 * nbodies + 1) * BD_NCOL;
+}
+
+// Three launches on `stream`: the right-hand-side block, the existing mass solve with 3 nb + 1 right-hand sides, the impulse solve
+// (its map variant where dnu_dnu is asked for). Arguments and conventions: include/wbc_sim.h. The checks that need no sim come first.
+extern "C" int wbc_sim_impulse_dynamics(wbc_sim* s, const int32_t* rigid_bodies, int nbodies, const uint8_t* active, const float* restitution,
+                                        const float* vel_des, const float* impulse_ext, float damping, int flags, float* nu_plus,
+                                        float* impulse, float* denergy, float* dnu_dnu, float* workspace, void* stream) {
+  WbCall c("wbc_sim_impulse_dynamics", s, stream);
+  if (!rigid_bodies || !nu_plus || !workspace) return c.fail(-1, "rigid_bodies / nu_plus / workspace is NULL");
+  if (nbodies < 1 || nbodies > WBC_CONSTR_MAX_BODIES) return c.fail(-1, "nbodies must be 1..WBC_CONSTR_MAX_BODIES");
+  if (!(damping >= 0.f) || !(damping <= 3.4e38f)) return c.fail(-1, "damping must be finite and >= 0");
+  if (flags & ~WBC_SOLVE_ARMATURE) return c.fail(-1, "unknown flag bits");
+  if (((uintptr_t)restitution | (uintptr_t)vel_des | (uintptr_t)impulse_ext | (uintptr_t)nu_plus | (uintptr_t)impulse | (uintptr_t)denergy |
+       (uintptr_t)dnu_dnu | (uintptr_t)workspace) & 3u)
+    return c.fail(-1, "restitution / vel_des / impulse_ext / nu_plus / impulse / denergy / dnu_dnu / workspace must be 4-byte aligned");
+  if ((uintptr_t)dnu_dnu & 15u) return c.fail(-1, "dnu_dnu must be 16-byte aligned");
+  for (int k = 0; k < nbodies; ++k)
+    if (rigid_bodies[k] < 0 || rigid_bodies[k] >= WBC_NRB) return c.fail(-1, "rigid-body index outside 0..WBC_NRB-1");
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  CdConst C;
+  if (ba_const_fill(c.hc->model, C, C) != 0) return c.no_tree();
+  for (int k = 0; k < nbodies; ++k)
+    for (int l = 0; l < k; ++l)
+      if (C.rb_body[rigid_bodies[k]] == C.rb_body[rigid_bodies[l]])
+        return c.fail(-1, "two listed rigid bodies ride on the same moving body (dependent rows)");
+  const int n = c.n;
+  if (n <= 0) return 0;
+  tree_cols_fill(c.hc->model, C);
+  uint32_t live_cols = 63u;
+  for (int d = 0; d < WBC_NDOF; ++d) if (C.col_body[d] >= 0) live_cols |= 1u << (6 + d);
+  C.nb = nbodies;
+  for (int k = 0; k < WBC_CONSTR_MAX_BODIES; ++k) C.rb[k] = rigid_bodies[k < nbodies ? k : 0];
+  const int nrow = 3 * nbodies + 1;
+  float *blk = workspace, *Y = blk + (size_t)n * nrow * BD_NCOL;
+  const dim3 grid((n + BA_EPW - 1) / BA_EPW);
+  hipLaunchKernelGGL(wbc_impulse_rhs_kernel, grid, dim3(64), 0, (hipStream_t)stream, C, c.root, c.dofs, active, impulse_ext, n, blk);
+  int rc = c.launched();
+  if (rc != 0) return rc;
+  rc = mass_solve_launch(c, blk, (int64_t)nrow * BD_NCOL, nrow, nullptr, Y, (int64_t)nrow * BD_NCOL, flags, stream);
+  if (rc != 0) return rc;
+  const ImArgs a = {blk, Y, c.root, c.dofs, active, restitution, vel_des, damping, nbodies, live_cols, n, nu_plus, impulse, denergy, dnu_dnu};
+  if (dnu_dnu) hipLaunchKernelGGL(wbc_impulse_solve_map_kernel, grid, dim3(64), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(wbc_impulse_solve_kernel, grid, dim3(64), 0, (hipStream_t)stream, a);
+  return c.launched();
+}
+
 // ---- centre of mass, centroidal momentum and its matrix (include/wbc_sim.h: wbc_sim_centroidal) ----------------------------------------
 // With c the centre of mass, d_b = c_b - c and every vector in WORLD axes relative to the root origin (the walk starts from E = R):
 //     h_G = (m v_com ; sum I_b w_b + m_b d_b x v_cb),   hdot_G = (m a_com ; sum I_b al_b + w_b x I_b w_b + m_b d_b x a_cb),

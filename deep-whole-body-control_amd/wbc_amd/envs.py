@@ -537,6 +537,33 @@ class WidowGo1(LeggedRobot):
             self._feet_list = [int(i) for i in self.feet_indices.tolist()]
         return self.sim.constrained_dynamics(self._feet_list, tau=tau, active=stance, armature=armature)
 
+    def touchdown_impact(self, stance: torch.Tensor = None, restitution: float = 0.0, push: torch.Tensor = None, apply: bool = False):
+        """(nu_plus [N, 26], foot_impulses [N, 4, 3], denergy [N]): the velocity just after the feet in `stance` (bool [N, 4], the feet
+        in contact AFTER the event; None: all four) have met the ground with Newton restitution `restitution`, and / or the
+        generalised impulse push [N, 26] has acted (rows as tau of forward_dynamics). foot_impulses are in N s, applied TO the robot in
+        world axes, exactly 0 for a foot that is not in stance; denergy is the kinetic energy gained (<= 0 for a pure impact).
+        apply=True writes nu_plus into the root and DoF velocities (set_root_state / set_dof_state; positions and the locked fingers
+        untouched); by default the sim is left as it is (include/wbc_sim.h: wbc_sim_impulse_dynamics)."""
+        if self.__dict__.get("_feet_list") is None:
+            self._feet_list = [int(i) for i in self.feet_indices.tolist()]
+        r = self.sim.impulse_dynamics(self._feet_list, active=stance, restitution=restitution if restitution else None, impulse_ext=push,
+                                      want_energy=True)
+        if apply:
+            root, dof = self.sim.tensor("ROOT_STATES").clone(), self.sim.tensor("DOF_STATE").clone()
+            root[:, 0, 7:13] = r["nu_plus"][:, :6]
+            dof[:, :-2, 1] = r["nu_plus"][:, 6:-2]
+            self.sim.set_root_state(root.contiguous())
+            self.sim.set_dof_state(dof.contiguous())
+        return r["nu_plus"], r["impulse"], r["denergy"]
+
+    def impact_map(self, stance: torch.Tensor = None, restitution: float = 0.0) -> torch.Tensor:
+        """f32 [N, 26, 26]: d nu+ / d nu of touchdown_impact, the exact linear map of the velocity across the event (nu+ = P nu without
+        a push); finger rows and columns exactly 0."""
+        if self.__dict__.get("_feet_list") is None:
+            self._feet_list = [int(i) for i in self.feet_indices.tolist()]
+        return self.sim.impulse_dynamics(self._feet_list, active=stance, restitution=restitution if restitution else None,
+                                         want_map=True)["dnu_dnu"]
+
     def stance_forward_dynamics_derivatives(self, tau: torch.Tensor = None, stance: torch.Tensor = None, armature: bool = False):
         """stance_forward_dynamics linearised: (nudot [N, 26], foot_forces [N, 4, 3], dnudot_dq, dnudot_dnu, dnudot_dtau [N, 26, 26],
         dforces_dq, dforces_dnu, dforces_dtau [N, 12, 26]) with [e, i, j] = d (.)_i / d x_j, in the tangent convention of

@@ -302,6 +302,51 @@ class WbcSim:
                                                   self._stream()), "wbc_sim_constrained_dynamics")
         return nudot, lam
 
+    def impulse_dynamics(self, rigid_bodies, active: Optional[torch.Tensor] = None, restitution=None,
+                         vel_des: Optional[torch.Tensor] = None, impulse_ext: Optional[torch.Tensor] = None, damping: float = 0.0,
+                         armature: bool = False, want_map: bool = False, want_energy: bool = False,
+                         workspace: Optional[torch.Tensor] = None) -> dict:
+        """wbc_sim_impulse_dynamics on the current stream: the velocity jump when the origins of the listed rigid bodies (1..5
+        indices) meet surfaces that move at vel_des [N, K, 3] (None: zeros) with Newton restitution [N, K] (a Python float is
+        broadcast; None: 0, plastic) where active [N, K] (bool or uint8; None: all), and / or the generalised impulse impulse_ext
+        [N, 26] acts. Returns a dict: nu_plus [N, 26], impulse [N, K, 3] (N s, applied TO the robot, exactly 0 where inactive), and
+        denergy [N] (want_energy) / dnu_dnu [N, 26, 26] (want_map). workspace: f32, at least
+        wbc_sim_impulse_dynamics_workspace_floats(N, K) elements; None: cached per number of bodies, as in constrained_dynamics."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        rbs = [int(r) for r in (rigid_bodies.tolist() if isinstance(rigid_bodies, torch.Tensor) else rigid_bodies)]
+        k = len(rbs)
+        assert 1 <= k <= 5, k
+        if restitution is not None and not isinstance(restitution, torch.Tensor):
+            restitution = torch.full((n, k), float(restitution), dtype=torch.float32, device=self.device)
+        for t, shape in ((restitution, (n, k)), (vel_des, (n, k, 3)), (impulse_ext, (n, ncol))):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, tuple(t.shape)
+        if active is not None:
+            assert active.device == self.arena.device and active.dtype in (torch.bool, torch.uint8) and tuple(active.shape) == (n, k)
+            active = active.contiguous()
+            if active.dtype == torch.bool:
+                active = active.view(torch.uint8)
+        need = int(self.L.wbc_sim_impulse_dynamics_workspace_floats(n, k))
+        if workspace is None:
+            cache = self.__dict__.setdefault("_impulse_ws", {})
+            if k not in cache:
+                cache[k] = torch.empty(need, dtype=torch.float32, device=self.device)
+            workspace = cache[k]
+        assert workspace.device == self.arena.device and workspace.dtype == torch.float32 and workspace.is_contiguous()
+        assert workspace.numel() >= need, (workspace.numel(), need)
+        out = dict(nu_plus=torch.empty((n, ncol), dtype=torch.float32, device=self.device),
+                   impulse=torch.empty((n, k, 3), dtype=torch.float32, device=self.device))
+        if want_energy:
+            out["denergy"] = torch.empty((n,), dtype=torch.float32, device=self.device)
+        if want_map:
+            out["dnu_dnu"] = torch.empty((n, ncol, ncol), dtype=torch.float32, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        check(self.L.wbc_sim_impulse_dynamics(self.h, (C.c_int32 * k)(*rbs), k, ptr(active), ptr(restitution), ptr(vel_des), ptr(impulse_ext),
+                                              float(damping), 1 if armature else 0, out["nu_plus"].data_ptr(), out["impulse"].data_ptr(),
+                                              ptr(out.get("denergy")), ptr(out.get("dnu_dnu")), workspace.data_ptr(), self._stream()),
+              "wbc_sim_impulse_dynamics")
+        return out
+
     # ---- whole-body inverse dynamics for task-space accelerations (include/wbc_sim.h: wbc_sim_task_inverse_dynamics) ------------------
     def task_inverse_dynamics(self, stance_bodies=(), task_bodies=(), task_acc: Optional[torch.Tensor] = None,
                               task_weight: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,

@@ -706,6 +706,45 @@ int wbc_sim_constrained_dynamics(wbc_sim* sim, const int32_t* rigid_bodies /* ho
                                  const float* tau, const float* acc_des, float damping, int flags, float* nudot, float* lambda,
                                  float* workspace, void* stream);
 
+/* What a change of the contact set does to the velocity: the impulse-level counterpart of wbc_sim_constrained_dynamics. When a swing
+ * foot lands (or the robot is pushed while it stands), the generalised velocity jumps from the state's nu to nu+, per env
+ *     M (nu+ - nu) = iota + sum_r J_r^T Lambda_r ,      J_r nu+ + damping Lambda_r = vdes_r - e_r (u_r - vdes_r)   for every active r,
+ * with u_r = J_r nu the pre-impact world-frame velocity of listed body r's origin (three linear rows). Coordinates, nu, rigid-body
+ * indices, the fingers, WBC_T_BODY_PARAMS, WBC_SOLVE_ARMATURE and stream handling are those of wbc_sim_constrained_dynamics.
+ * rigid_bodies, nbodies, active: as there. An inactive body contributes no row, its entries of impulse are exactly 0 and its entries of
+ *              restitution and vel_des are never loaded into arithmetic (a NaN there does not spread).
+ * restitution  device f32 [N, nbodies] or NULL (= zeros, a plastic impact): Newton's coefficient e_r relative to the surface velocity,
+ *              used as given (values outside 0..1 are the caller's business).
+ * vel_des      device f32 [N, nbodies, 3] or NULL (= zeros): the surface's world-frame velocity at the contact.
+ * impulse_ext  device f32 [N, 26] or NULL (= zeros): a generalised impulse iota in the row conventions of tau in
+ *              wbc_sim_forward_dynamics (rows 0:3 a linear impulse on the robot, rows 3:6 an angular impulse about the root origin,
+ *              rows 6: joint impulses); a push on the trunk, or a J^T p the caller formed. Finger entries are ignored.
+ * damping      >= 0, added to the diagonal of the Delassus matrix. flags: 0 or WBC_SOLVE_ARMATURE.
+ * nu_plus      device f32 [N, 26], fingers exactly 0. With no active body and impulse_ext NULL it is the state's nu bit for bit on the
+ *              live coordinates.
+ * impulse      device f32 [N, nbodies, 3] or NULL: Lambda_r in N s, applied TO the robot at body r's origin, world axes.
+ * denergy      device f32 [N] or NULL: T(nu+) - T(nu), T = nu^T M nu / 2 with the matrix the solve used, formed as the quadratic form
+ *              g^T nu + g^T M^-1 g / 2 of g = iota + J^T Lambda (not as a difference of two energies). Exactly 0 with no active body
+ *              and impulse_ext NULL.
+ * dnu_dnu      device f32 [N, 26, 26] or NULL, 16-byte aligned: the exact linear map P[e, i, j] = d nu+_i / d nu_j
+ *              = 1 - M^-1 J^T (A + damping)^-1 diag(1 + e) J on the live coordinates, finger rows and columns exactly 0. With
+ *              impulse_ext and vel_des NULL, nu+ = P nu. The other outputs have the same bits with and without it.
+ * workspace    caller-owned device floats, at least wbc_sim_impulse_dynamics_workspace_floats(N, nbodies) of them (0 for a bad
+ *              argument). Nothing is allocated in the call and no bias-force scratch is used (no h enters), so the call is safe under
+ *              stream capture and calls on different streams need their own workspaces only.
+ * The root position is never read: every output is bit-identical under a translation of the robot.
+ * Three launches on `stream`, no host synchronisation: wbc_impulse_rhs_kernel ([J_c^T | iota]), the mass solve with
+ * 3 nbodies + 1 right-hand sides, wbc_impulse_solve_kernel (u = J nu, A, its Cholesky factorisation, Lambda, nu+; or
+ * wbc_impulse_solve_map_kernel where dnu_dnu is given).
+ * -1 with a message in wbc_last_error() that names this entry point, nothing written: NULL sim / rigid_bodies / nu_plus / workspace;
+ * nbodies outside 1..WBC_CONSTR_MAX_BODIES; an index outside 0..WBC_NRB-1; two entries that ride on the same moving body; damping
+ * negative or not finite; unknown flag bits; a pointer that is not 4-byte aligned; dnu_dnu not 16-byte aligned. The checks that need
+ * no sim are made first. Rank deficiency, -3 and -2 as wbc_sim_constrained_dynamics. */
+size_t wbc_sim_impulse_dynamics_workspace_floats(int num_envs, int nbodies);
+int wbc_sim_impulse_dynamics(wbc_sim* sim, const int32_t* rigid_bodies /* host */, int nbodies, const uint8_t* active,
+                             const float* restitution, const float* vel_des, const float* impulse_ext, float damping, int flags,
+                             float* nu_plus, float* impulse, float* denergy, float* dnu_dnu, float* workspace, void* stream);
+
 /* Whole-body inverse dynamics for task-space accelerations: the joint torques that produce wanted accelerations of a few rigid bodies
  * while the stance feet stay put. Coordinates, nu, nudot, tau rows and rigid-body indices are those of wbc_sim_body_dynamics /
  * wbc_sim_inverse_dynamics / wbc_sim_constrained_dynamics; state, WBC_T_BODY_PARAMS and all three gravity components as there. Per env:

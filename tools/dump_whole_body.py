@@ -82,6 +82,26 @@ def keep_cdd(sim, name, feet, grip, tau, g):
     keep(name + "cdd.4.a1.t1", *[r[k] for k in order])
 
 
+def keep_impulse(sim, name, feet, grip):
+    """wbc_sim_impulse_dynamics (a generator of its own: the other entry points' draws stay what they were): feet all active; feet
+    masked; feet + gripper with vel_des, restitution and impulse_ext; no active body."""
+    n = sim.num_envs
+    g = torch.Generator(device="cuda"); g.manual_seed(7000 + n)
+    rnd = lambda *shape, scale=1.0: ((torch.rand(*shape, device="cuda", generator=g) * 2 - 1) * scale).contiguous()  # noqa: E731
+    order = ("nu_plus", "impulse", "denergy", "dnu_dnu")
+    both = dict(want_map=True, want_energy=True)
+    keep(name + "imp.4", *[sim.impulse_dynamics(feet, **both)[k] for k in order])
+    act = (torch.rand(n, 4, device="cuda", generator=g) < 0.6)
+    keep(name + "imp.4.masked", *[sim.impulse_dynamics(feet, active=act, restitution=0.5, armature=True, **both)[k] for k in order])
+    r = sim.impulse_dynamics(feet + [grip], restitution=torch.rand(n, 5, device="cuda", generator=g).contiguous(), vel_des=rnd(n, 5, 3),
+                             impulse_ext=rnd(n, 26, scale=2.0), damping=1e-3, **both)
+    keep(name + "imp.5", *[r[k] for k in order])
+    r = sim.impulse_dynamics(feet, active=torch.zeros(n, 4, dtype=torch.bool, device="cuda"), impulse_ext=rnd(n, 26, scale=2.0), **both)
+    keep(name + "imp.4.none", *[r[k] for k in order])
+    r = sim.impulse_dynamics([grip], restitution=1.0)
+    keep(name + "imp.1.plain", r["nu_plus"], r["impulse"])
+
+
 for n in (1, 13, 64, 273):
     cfg = WidowGo1RoughCfg(); cfg.env.num_envs = n; cfg.terrain.mesh_type = "plane"
     env = WidowGo1(cfg, sim_device="cuda:0", seed=5)
@@ -166,7 +186,8 @@ for n in (1, 13, 64, 273):
     md = torch.empty(n, 26, 26, device=dev)
     fd = sim.forward_dynamics_derivatives(tau=None, minv=md)
     keep(T + "fdd.tau_null", *fd)
-    keep_cdd(sim, T, feet, grip, tau, g)           # last: the generator's earlier draws stay what they were
+    keep_cdd(sim, T, feet, grip, tau, g)           # last of the shared generator: its earlier draws stay what they were
+    keep_impulse(sim, T, feet, grip)
 
 np.savez(sys.argv[1], **out)
 print(f"{len(out)} arrays, {sum(a.size for a in out.values())} words -> {sys.argv[1]}")
