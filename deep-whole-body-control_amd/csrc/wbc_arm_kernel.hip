@@ -3166,3 +3166,399 @@ extern "C" int wbc_sim_task_inverse_dynamics_qp(wbc_sim* s, const int32_t* stanc
   return taskid_launch("wbc_sim_task_inverse_dynamics_qp", s, stance_bodies, nstance, active, stance_acc, task_bodies, ntasks, task_acc,
                        task_weight, nudot_ref, weights, flags, tau, nudot, lambda, workspace, stream, &qp);
 }
+
+// ---- whole-body inverse kinematics with joint limits (include/wbc_sim.h: wbc_sim_inverse_kinematics) -----------------------------------
+// Projected Levenberg-Marquardt over the 24 live coordinates, one launch, everything between the loads and the stores in LDS and registers.
+// IK_EPW envs per 64-lane workgroup, one per lane group; the state is (root position RELATIVE to the start's, root quaternion, q[20]):
+//  evaluate   lane b < 19 = moving body b walks root -> b in WORLD axes (tree_frame_step) and leaves its joint axis and origin in LDS;
+//             lane 19 + k walks to target k's body with the body's quaternion carried along, leaves the target's origin, its six residuals
+//             (target - x; phi = log(R_target R^T) from the error quaternion) and its share of the cost; lane j < 18 adds the posture
+//             share; a butterfly sum gives every lane of the group the same bits.
+//  accept     trip 0 takes the start; later trips take the candidate if the cost did not rise (lambda /= 8), else lambda *= 8.
+//  linearise  lane c = coordinate c fills column c of the listed bodies' Jacobian rows (pitch 25) and forms g_c; the lower triangle of
+//             H = J^T W J + posture S^T S, one entry per lane and round. Kept only when the point was accepted.
+//  solve      A = H + lambda diag H + floor, the identity's row and column for a joint that sits at a limit with the gradient pushing
+//             outward; delassus_cholesky / delassus_lane_solve (m = 24). Where a free joint's step would leave its limits, a second
+//             solve with that joint's step held at the distance to the limit; lane c retracts and clamps coordinate c into the candidate.
+// Every loop has a compile-time bound and every barrier is reached by all 64 lanes: what ends the loop is one value per lane group in
+// LDS, read back behind a barrier, and a group that is done keeps taking the trips (its stores predicated off) until both are.
+#ifndef IK_EPW
+#define IK_EPW 2                                // envs per workgroup: 2, or 1 (-DIK_EPW=1, the variant DESIGN.md compares with)
+#endif
+static_assert(IK_EPW == 1 || IK_EPW == 2, "one env per 64 lanes or one per 32-lane half");
+#define IK_LPE (64 / IK_EPW)                    // lanes per env
+#define IK_M (6 + WBC_NJ)                       // 24 live coordinates
+#define IK_ROWS (6 * WBC_IK_MAX_TARGETS)        // 36 residual rows at most
+#define IK_LD (IK_M + 1)                        // LDS pitch of J, H and A (odd)
+#define IK_NS (7 + WBC_NDOF)                    // a state: position 0..2, quaternion 3..6, q 7..26
+#define IK_TRI (IK_M * (IK_M + 1) / 2)
+#define IK_LAMBDA_MIN 1e-9f
+#define IK_LAMBDA_MAX 1e8f                      // the damping's ceiling: status 2 beyond it
+#define IK_FLOOR 1e-9f
+static_assert(WBC_NB + WBC_IK_MAX_TARGETS <= IK_LPE && IK_M <= 32 && IK_NS <= IK_LPE && WBC_NJ <= WBC_NB, "lanes");
+struct IkConst : TreeWalk, TreeRigid, TreeCols {
+  int32_t nt, rb[WBC_IK_MAX_TARGETS];          // the listed rigid bodies
+  int32_t jdof[WBC_NJ];                         // DoF of coordinate 6 + j
+  float lo[WBC_NDOF], hi[WBC_NDOF];
+  uint32_t limited;                             // bit d: DoF d has limits
+  float posture, lambda0, step_tol;
+  int32_t max_iter;
+};
+struct IkArgs {
+  const float *root, *dofs;                     // the start: rows root_stride / dof_env_stride floats apart, DoF d at d * dof_stride
+  int root_stride, dof_env_stride, dof_stride;
+  const float *target_pos, *target_quat, *w_pos, *w_ori, *q_ref;
+  int n;
+  float *root_out, *dof_out, *residual, *cost;
+  int32_t *status, *iterations;
+};
+
+__device__ __forceinline__ float ik_sum(float v) {   // the same bits in every lane of the group
+#pragma unroll
+  for (int off = IK_LPE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+extern "C" __global__ void __launch_bounds__(64) wbc_ik_kernel(IkConst C, IkArgs a) {
+  __shared__ float sJ[IK_EPW][IK_ROWS][IK_LD];
+  __shared__ float sH[IK_EPW][IK_M][IK_LD], sA[IK_EPW][IK_M][IK_LD];   // lower triangles: H; A, then L
+  __shared__ float sD[IK_EPW][IK_M + 1], sV[IK_EPW][IK_M + 1];
+  __shared__ float sFr[IK_EPW][WBC_NB][6];                             // joint axis, joint origin (world axes, relative position)
+  __shared__ float sX[IK_EPW][WBC_IK_MAX_TARGETS][3], sRes[IK_EPW][IK_ROWS], sWr[IK_EPW][IK_ROWS];
+  __shared__ float sT[IK_EPW][WBC_IK_MAX_TARGETS][8];                  // target: position relative to the start root's 0..2, unit quaternion 3..6
+  __shared__ float sCur[IK_EPW][IK_NS + 1], sCand[IK_EPW][IK_NS + 1];
+  __shared__ float sB[IK_EPW][IK_M + 1];                               // the second pass's held steps
+  __shared__ int sDone[2], sHit[2], sAcc[2];
+  const int half = IK_EPW == 2 ? threadIdx.x >> 5 : 0, lane = IK_EPW == 2 ? threadIdx.x & 31 : threadIdx.x;
+  const int env = blockIdx.x * IK_EPW + half;
+  const bool live = env < a.n;
+  const size_t e = live ? env : a.n - 1;           // the idle half of the last workgroup recomputes the last env and stores nothing
+  const int nt = C.nt < WBC_IK_MAX_TARGETS ? C.nt : WBC_IK_MAX_TARGETS, nrow = 6 * nt;
+  float (*J)[IK_LD] = sJ[half], (*H)[IK_LD] = sH[half], (*A)[IK_LD] = sA[half];
+  float *D = sD[half], *V = sV[half], *cur = sCur[half], *cand = sCand[half], *res = sRes[half], *wr = sWr[half];
+  const float *rs = a.root + e * (size_t)a.root_stride, *ds = a.dofs + e * (size_t)a.dof_env_stride;
+  const bool tl = lane >= WBC_NB && lane < WBC_NB + nt;   // a target's lane
+  const int tk = tl ? lane - WBC_NB : 0;
+  const int cdof = lane >= 6 && lane < IK_M ? C.jdof[lane - 6] : 0;   // lane c >= 6: the DoF of coordinate c
+  const bool clim = lane >= 6 && lane < IK_M && ((C.limited >> cdof) & 1u);
+  const float clo = C.lo[cdof], chi = C.hi[cdof];
+
+  // the start: positions relative to its root, unit quaternion, limited joints clamped
+  if (lane < IK_NS) {
+    float v = 0.f;
+    if (lane >= 3 && lane < 7) v = rs[lane] * (1.f / __fsqrt_rn(rs[3] * rs[3] + rs[4] * rs[4] + rs[5] * rs[5] + rs[6] * rs[6]));
+    if (lane >= 7) {
+      const int d = lane - 7;
+      v = ds[d * a.dof_stride];
+      if (C.col_body[d] >= 0 && ((C.limited >> d) & 1u)) v = fminf(fmaxf(v, C.lo[d]), C.hi[d]);
+    }
+    cand[lane] = v;
+  }
+  if (tl) {
+    const size_t ek = e * nt + tk;
+    const float wo = a.target_quat ? (a.w_ori ? a.w_ori[ek] : 1.f) : 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const float w = a.w_pos ? a.w_pos[ek * 3 + i] : 1.f;
+      wr[6 * tk + i] = w; wr[6 * tk + 3 + i] = wo;
+      sT[half][tk][i] = w != 0.f ? a.target_pos[ek * 3 + i] - rs[i] : 0.f;   // a skipped row's target is never loaded
+    }
+    float q4[4] = {0.f, 0.f, 0.f, 1.f};
+    if (wo != 0.f) {
+      const float* tq = a.target_quat + ek * 4;
+      const float inv = 1.f / __fsqrt_rn(tq[0] * tq[0] + tq[1] * tq[1] + tq[2] * tq[2] + tq[3] * tq[3]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) q4[i] = tq[i] * inv;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sT[half][tk][3 + i] = q4[i];
+  }
+  __syncthreads();
+  const float qref = lane >= 6 && lane < IK_M ? (a.q_ref ? a.q_ref[e * WBC_NDOF + cdof] : cand[7 + cdof]) : 0.f;
+
+  float lambda = C.lambda0, cost = 0.f, cost0 = 0.f, gc = 0.f;
+  float rcand[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, rcur[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // a target lane's residuals
+  uint32_t fix = 0;                                // bit c: coordinate c sits at a limit with the gradient pushing outward
+  int status = 1, iters = 0;
+  bool done = false, moved = false;
+
+#pragma nounroll
+  for (int trip = 0; trip <= WBC_IK_MAX_ITER; ++trip) {
+    // ---- evaluate the candidate (trip 0: the start)
+    float share = 0.f;
+    if (lane < WBC_NB + nt) {
+      const int r = C.rb[tk], b = tl ? C.rb_body[r] : lane;
+      float qa[4] = {cand[3], cand[4], cand[5], cand[6]}, E[9];
+      quat_to_mat(qa, E);
+      f3 p = mk3(cand[0], cand[1], cand[2]), ax = mk3(0.f, 0.f, 0.f);
+#pragma nounroll
+      for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
+        const int jb = C.path[b][k];
+        if (jb < 0) break;
+        float sh, ch, Q[9];
+        sincosf(0.5f * cand[7 + C.dof[jb]], &sh, &ch);
+        const f3 u = tree_axis(C.axis[jb]);
+        tree_rodrigues(u, 2.f * sh * ch, 1.f - 2.f * sh * sh, 2.f * sh * sh, Q);
+        ax = tree_frame_step(E, p, Q, C.joint_xyz[jb], u);
+        const float qj[4] = {u.x * sh, u.y * sh, u.z * sh, ch};
+        quat_mul(qa, qj, qa);
+      }
+      if (!tl) {
+        st3(sFr[half][b], ax); st3(sFr[half][b] + 3, p);
+      } else {
+        const f3 x = p + mat_mul(E, mk3(C.rb_offset[r][0], C.rb_offset[r][1], C.rb_offset[r][2]));
+        st3(sX[half][tk], x);
+        const float xs[3] = {x.x, x.y, x.z};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const float w = wr[6 * tk + i];
+          rcand[i] = w != 0.f ? sT[half][tk][i] - xs[i] : 0.f;
+          share += w != 0.f ? 0.5f * w * rcand[i] * rcand[i] : 0.f;
+        }
+        const float wo = wr[6 * tk + 3];
+        f3 phi = mk3(0.f, 0.f, 0.f);
+        if (wo != 0.f) {                           // phi = log(R_target R^T) from the error quaternion q_target conj(q)
+          const float qc[4] = {-qa[0], -qa[1], -qa[2], qa[3]};
+          float qe[4];
+          quat_mul(&sT[half][tk][3], qc, qe);
+          const float sg = qe[3] < 0.f ? -1.f : 1.f;
+          const f3 v = mk3(qe[0] * sg, qe[1] * sg, qe[2] * sg);
+          const float w = qe[3] * sg, nv = __fsqrt_rn(dot(v, v));
+          phi = v * (nv > 1e-6f ? 2.f * atan2f(nv, w) / nv : 2.f / w);
+          share += 0.5f * wo * dot(phi, phi);
+        }
+        rcand[3] = phi.x; rcand[4] = phi.y; rcand[5] = phi.z;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) res[6 * tk + i] = rcand[i];
+      }
+    }
+    if (lane >= 6 && lane < IK_M) {
+      const float dq = cand[7 + cdof] - qref;
+      share += 0.5f * C.posture * dq * dq;
+    }
+    const float cc = ik_sum(share);
+
+    // ---- accept or reject
+    bool acc;
+    if (trip == 0) {
+      cost0 = cost = cc;
+      if (!(fabsf(cc) <= 3.4e38f)) { status = 3; done = true; }
+      acc = !done;
+    } else {
+      acc = !done && cc <= cost;
+      if (!done) {
+        ++iters;
+        if (acc) { lambda = fmaxf(lambda * 0.125f, IK_LAMBDA_MIN); moved = true; cost = cc; }
+        else {
+          lambda *= 8.f;
+          if (lambda > IK_LAMBDA_MAX) { status = 2; done = true; }
+        }
+      }
+    }
+    if (acc) {
+      if (lane < IK_NS) cur[lane] = cand[lane];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) rcur[i] = rcand[i];
+    }
+    if (lane == 0) sAcc[half] = acc;
+    __syncthreads();
+
+    // ---- linearise at the evaluated point: kept only where it was accepted, and skipped by the whole workgroup where neither env's was
+    if (sAcc[0] != 0 || (IK_EPW == 2 && sAcc[1] != 0)) {
+      if (lane < IK_M) {
+        const int c = lane, jb = c >= 6 ? C.col_body[cdof] : 0, j = c < 3 ? c : c - 3;
+        const f3 ej = mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f);
+        const f3 pr = mk3(cand[0], cand[1], cand[2]);
+        float g = 0.f;
+        for (int k = 0; k < WBC_IK_MAX_TARGETS; ++k) {
+          if (k >= nt) break;
+          const f3 x = ld3(sX[half][k]);
+          f3 lin = mk3(0.f, 0.f, 0.f), ang = lin;
+          if (c < 3) lin = ej;
+          else if (c < 6) { lin = cross(ej, x - pr); ang = ej; }
+          else if ((C.anc[C.rb_body[C.rb[k]]] >> jb) & 1u) { ang = ld3(sFr[half][jb]); lin = cross(ang, x - ld3(sFr[half][jb] + 3)); }
+          const float col[6] = {lin.x, lin.y, lin.z, ang.x, ang.y, ang.z};
+#pragma unroll
+          for (int i = 0; i < 6; ++i) {
+            J[6 * k + i][c] = col[i];
+            g -= wr[6 * k + i] * col[i] * res[6 * k + i];
+          }
+        }
+        if (c >= 6) g += C.posture * (cand[7 + cdof] - qref);
+        if (acc) gc = g;
+      }
+      {
+        const float qv = cand[7 + cdof];
+        const bool f = clim && ((qv <= clo && gc > 0.f) || (qv >= chi && gc < 0.f));
+        const uint32_t m = (uint32_t)(__ballot(f) >> (32 * half));
+        if (acc) fix = m;
+      }
+      __syncthreads();
+#pragma nounroll
+      for (int t = lane; t < IK_TRI; t += IK_LPE) {
+        int i, j;
+        delassus_tri(t, i, j);
+        float h = 0.f;
+        for (int r = 0; r < IK_ROWS; ++r) {
+          if (r >= nrow) break;
+          h += wr[r] * J[r][i] * J[r][j];
+        }
+        if (i == j && i >= 6) h += C.posture;
+        if (acc) H[i][j] = h;
+      }
+    }
+    __syncthreads();
+
+    // ---- the damped step from the current point
+    auto damped_solve = [&](uint32_t held, float ci) {   // the identity's rows and columns on `held`; lane c: entry c of the right-hand side
+#pragma nounroll
+      for (int t = lane; t < IK_TRI; t += IK_LPE) {
+        int i, j;
+        delassus_tri(t, i, j);
+        const bool on = !((held >> i) & 1u) && !((held >> j) & 1u);
+        const float h = H[i][j];
+        A[i][j] = on ? (i == j ? h + lambda * h + IK_FLOOR : h) : (i == j ? 1.f : 0.f);   // delassus_fill's device for rows that are held
+      }
+      delassus_cholesky(A, D, IK_M, lane);
+      delassus_lane_solve(A, D, V, IK_M, lane, ci);
+    };
+    const bool mine = lane < IK_M && !((fix >> lane) & 1u);
+    damped_solve(fix, mine ? -gc : 0.f);
+    // second pass: a free joint whose step would leave its limits goes ONTO the limit, and the others solve again with those steps held
+    // (the clamped step of the first pass is not a descent step of the model). Taken by the whole workgroup if either env needs it.
+    bool hit = false;
+    float snap = 0.f;
+    if (mine && clim) {
+      const float v = cur[7 + cdof] + V[lane];
+      hit = v < clo || v > chi;
+      snap = v < clo ? clo : chi;
+    }
+    const uint32_t hits = (uint32_t)(__ballot(hit) >> (32 * half));
+    if (lane < IK_M) sB[half][lane] = hit ? snap - cur[7 + cdof] : 0.f;
+    if (lane == 0) sHit[half] = hits != 0u;
+    __syncthreads();
+    if (sHit[0] != 0 || (IK_EPW == 2 && sHit[1] != 0)) {
+      float ci = 0.f;
+      if (mine) {
+        ci = sB[half][lane];
+        if (!hit) {
+          float sum = 0.f;
+          for (int j = 0; j < IK_M; ++j)
+            if ((hits >> j) & 1u) sum += (lane >= j ? H[lane][j] : H[j][lane]) * sB[half][j];
+          ci = -gc - sum;
+        }
+      }
+      damped_solve(fix | hits, ci);
+    }
+    bool far = false;                              // this coordinate's projected step exceeds step_tol (or is not a number)
+    if (lane < IK_M) {
+      const float d = V[lane];
+      float s = fabsf(d);
+      if (lane < 3) cand[lane] = cur[lane] + d;
+      if (lane == 3) {                             // R <- exp([d theta]x) R
+        const f3 th = mk3(V[3], V[4], V[5]);
+        const float an = __fsqrt_rn(dot(th, th));
+        float sh, ch;
+        sincosf(0.5f * an, &sh, &ch);
+        const float kk = an > 1e-6f ? sh / an : 0.5f;
+        const float dq[4] = {th.x * kk, th.y * kk, th.z * kk, ch}, qo[4] = {cur[3], cur[4], cur[5], cur[6]};
+        float qn[4];
+        quat_mul(dq, qo, qn);
+        const float inv = 1.f / __fsqrt_rn(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cand[3 + i] = qn[i] * inv;
+      }
+      if (lane >= 6) {
+        const float q0 = cur[7 + cdof];
+        float qn = q0 + d;
+        if (clim) qn = fminf(fmaxf(qn, clo), chi);
+        if (hit) qn = snap;
+        cand[7 + cdof] = qn;
+        s = fabsf(qn - q0);
+      }
+      far = !(s <= C.step_tol) || !(d == d);
+    }
+    const bool anyfar = (uint32_t)(__ballot(far) >> (32 * half)) != 0u;
+    if (!done) {
+      if (!anyfar && lambda <= C.lambda0) { status = 0; done = true; }
+      else if (trip >= C.max_iter) done = true;    // status 1
+    }
+    // ---- one exit decision for the workgroup
+    if (lane == 0) sDone[half] = done || !live;
+    __syncthreads();
+    const bool all = sDone[0] != 0 && (IK_EPW == 1 || sDone[1] != 0);
+    __syncthreads();
+    if (all) break;
+  }
+
+  if (!live) return;
+  const bool start = status == 3 || !moved;        // no step was accepted: the start's own bits
+  if (lane < 7) a.root_out[e * 7 + lane] = start ? rs[lane] : (lane < 3 ? rs[lane] + cur[lane] : cur[lane]);
+  if (lane < WBC_NDOF) {
+    const bool joint = C.col_body[lane] >= 0;
+    a.dof_out[e * WBC_NDOF + lane] = joint && status != 3 ? cur[7 + lane] : ds[lane * a.dof_stride];
+  }
+  if (a.residual && tl) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) a.residual[(e * nt + tk) * 6 + i] = status == 3 ? rcand[i] : rcur[i];
+  }
+  if (lane == 0) {
+    if (a.cost) { a.cost[e * 2] = cost0; a.cost[e * 2 + 1] = cost; }
+    if (a.status) a.status[e] = status;
+    if (a.iterations) a.iterations[e] = iters;
+  }
+}
+
+// One launch on `stream`, no workspace. Arguments and conventions: include/wbc_sim.h. The checks that need no sim come first.
+extern "C" int wbc_sim_inverse_kinematics(wbc_sim* s, const int32_t* bodies, int ntargets, const float* target_pos, const float* target_quat,
+                                          const float* w_pos, const float* w_ori, const float* root_init, const float* dof_init,
+                                          const float* q_ref, const wbc_ik_opts* opts, float* root_out, float* dof_out, float* residual,
+                                          float* cost, int32_t* status, int32_t* iterations, void* stream) {
+  WbCall c("wbc_sim_inverse_kinematics", s, stream);
+  if (!bodies || !target_pos || !opts || !root_out || !dof_out) return c.fail(-1, "bodies / target_pos / opts / root_out / dof_out is NULL");
+  if (ntargets < 1 || ntargets > WBC_IK_MAX_TARGETS) return c.fail(-1, "ntargets must be 1..WBC_IK_MAX_TARGETS");
+  for (int k = 0; k < ntargets; ++k)
+    if (bodies[k] < 0 || bodies[k] >= WBC_NRB) return c.fail(-1, "rigid-body index outside 0..WBC_NRB-1");
+  if (w_ori && !target_quat) return c.fail(-1, "w_ori given without target_quat");
+  if (!(opts->posture >= 0.f) || !(opts->posture <= 3.4e38f)) return c.fail(-1, "posture must be finite and >= 0");
+  if (!(opts->damping > 0.f) || !(opts->damping <= 3.4e38f)) return c.fail(-1, "damping must be finite and > 0");
+  if (!(opts->step_tol > 0.f) || !(opts->step_tol <= 3.4e38f)) return c.fail(-1, "step_tol must be finite and > 0");
+  if (opts->max_iter < 0 || opts->max_iter > WBC_IK_MAX_ITER) return c.fail(-1, "max_iter must be 0..WBC_IK_MAX_ITER");
+  if (((uintptr_t)target_pos | (uintptr_t)target_quat | (uintptr_t)w_pos | (uintptr_t)w_ori | (uintptr_t)root_init | (uintptr_t)dof_init |
+       (uintptr_t)q_ref | (uintptr_t)root_out | (uintptr_t)dof_out | (uintptr_t)residual | (uintptr_t)cost | (uintptr_t)status |
+       (uintptr_t)iterations) & 3u)
+    return c.fail(-1, "every device pointer must be 4-byte aligned");
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  const wbc_model& m = c.hc->model;
+  IkConst C;
+  if (ba_const_fill(m, C, C) != 0) return c.no_tree();
+  tree_cols_fill(m, C);
+  int nj = 0;
+  C.limited = 0;
+  for (int d = 0; d < WBC_NDOF; ++d) {
+    C.lo[d] = m.q_lower[d]; C.hi[d] = m.q_upper[d];
+    if (C.col_body[d] < 0) continue;
+    if (!(m.q_lower[d] == 0.f && m.q_upper[d] == 0.f)) {
+      if (!(m.q_lower[d] <= m.q_upper[d])) return c.fail(-3, "a joint's lower limit exceeds its upper limit");
+      C.limited |= 1u << d;
+    }
+    if (nj < WBC_NJ) C.jdof[nj] = d;
+    ++nj;
+  }
+  if (nj != WBC_NJ) return c.no_tree();
+  const int n = c.n;
+  if (n <= 0) return 0;
+  C.nt = ntargets;
+  for (int k = 0; k < WBC_IK_MAX_TARGETS; ++k) C.rb[k] = bodies[k < ntargets ? k : 0];
+  C.posture = opts->posture; C.lambda0 = opts->damping; C.step_tol = opts->step_tol;
+  C.max_iter = opts->max_iter > 0 ? opts->max_iter : WBC_IK_MAX_ITER;
+  IkArgs a;
+  a.root = root_init ? root_init : c.root; a.root_stride = root_init ? 7 : 26;
+  a.dofs = dof_init ? dof_init : c.dofs; a.dof_env_stride = dof_init ? WBC_NDOF : 2 * WBC_NDOF; a.dof_stride = dof_init ? 1 : 2;
+  a.target_pos = target_pos; a.target_quat = target_quat; a.w_pos = w_pos; a.w_ori = w_ori; a.q_ref = q_ref;
+  a.n = n;
+  a.root_out = root_out; a.dof_out = dof_out; a.residual = residual; a.cost = cost; a.status = status; a.iterations = iterations;
+  hipLaunchKernelGGL(wbc_ik_kernel, dim3((n + IK_EPW - 1) / IK_EPW), dim3(64), 0, (hipStream_t)stream, C, a);
+  return c.launched();
+}

@@ -7,6 +7,13 @@
 #pragma once
 #include "wbc_device.h"
 
+// Entry t of a lower triangle stored row by row: t = i (i + 1) / 2 + j, j <= i.
+__device__ __forceinline__ void delassus_tri(int t, int& i, int& j) {
+  i = (int)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);
+  i = i * (i + 1) / 2 > t ? i - 1 : ((i + 1) * (i + 2) / 2 <= t ? i + 1 : i);
+  j = t - i * (i + 1) / 2;
+}
+
 // The lower triangle of A, one entry per lane and round: row i of J against row j of Y, the damping on the diagonal; where row i or j
 // belongs to an inactive body (bit of `act` clear) the identity's entry instead.
 template <int LD, int LA>
@@ -14,9 +21,8 @@ __device__ __forceinline__ void delassus_fill(const float (*J)[LD], const float 
                                               int lane, int stride) {
 #pragma nounroll
   for (int t = lane; t < m * (m + 1) / 2; t += stride) {
-    int i = (int)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);              // t = i (i + 1) / 2 + j, j <= i
-    i = i * (i + 1) / 2 > t ? i - 1 : ((i + 1) * (i + 2) / 2 <= t ? i + 1 : i);
-    const int j = t - i * (i + 1) / 2;
+    int i, j;
+    delassus_tri(t, i, j);
     float a = 0.f;
 #pragma unroll
     for (int c = 0; c < WBC_NCOL; ++c) a += J[i][c] * Y[j][c];

@@ -116,6 +116,14 @@ class WbcTaskQpLimits(C.Structure):
     _fields_ = [("mu", f32), ("fn_min", f32), ("max_iter", i32)]
 
 
+IK_MAX_TARGETS, IK_MAX_ITER = 6, 64     # WBC_IK_MAX_TARGETS, WBC_IK_MAX_ITER
+
+
+class WbcIkOpts(C.Structure):
+    """wbc_ik_opts (include/wbc_sim.h): the host scalars of wbc_sim_inverse_kinematics; max_iter 0 = WBC_IK_MAX_ITER."""
+    _fields_ = [("posture", f32), ("damping", f32), ("step_tol", f32), ("max_iter", i32)]
+
+
 # enum wbc_tensor_id, same order as the header
 TENSOR_IDS = [
     "ROOT_STATES", "DOF_STATE", "NET_CONTACT_FORCE", "RIGID_BODY_STATE", "FORCE_SENSOR", "TORQUES", "OBS_BUF",

@@ -624,6 +624,67 @@ class WidowGo1(LeggedRobot):
                                                                   tau_limit=tau_limit, normal=normal, max_iter=max_iter, **scalars)
         return tau[:, 6:].contiguous(), nudot, lam, info
 
+    # ---- whole-body inverse kinematics (no counterpart in the reference): one launch, include/wbc_sim.h: wbc_sim_inverse_kinematics ----
+    def reach_configuration(self, ee_pos: torch.Tensor, ee_quat: torch.Tensor = None, stance: torch.Tensor = None,
+                            base_height: torch.Tensor = None, apply: bool = False, refine: int = 2, refine_posture: float = 1e-5,
+                            refine_step_tol: float = 1e-5, **opts):
+        """(root_pose [N, 7], dof_pos [N, 20], info): the configuration near the current one, inside the joint limits, that keeps the
+        feet in `stance` (bool [N, 4]; None: all four) where they are now and puts the gripper at ee_pos [N, 3] (world) and, if given,
+        at the orientation ee_quat [N, 4] (xyzw); base_height [N] asks for that world height of the trunk's origin as well.
+        The first solve regularises the posture towards default_dof_pos (opts: posture, damping, step_tol, max_iter of
+        WbcSim.inverse_kinematics). Its posture term trades against the targets (it misses them by about posture * dq / lever:
+        centimetres at the default weight where the joints end 1 rad from default_dof_pos), so `refine` further solves follow, each
+        from the last answer with q_ref that answer itself and the small weight refine_posture (a proximal step: the posture term
+        vanishes at its start and only picks among the configurations that meet the targets the one nearest to the last answer).
+        Over the tests' family the targets are then met to 3e-5 m after one and 1e-7 m after two such solves, each of a few
+        iterations; refine=0 returns the first solve's trade-off. A goal out of reach keeps its residual through every solve.
+        apply=True writes the result into the root and DoF states with zero velocities (set_root_state / set_dof_state); by default
+        the sim is left as it is. info is the last solve's (rows: the four feet, the gripper, then the trunk), its "iterations" the
+        sum over the solves."""
+        if self.__dict__.get("_feet_list") is None:
+            self._feet_list = [int(i) for i in self.feet_indices.tolist()]
+        n, dev = self.num_envs, self.device
+        self.sim.refresh_rigid_body_state()
+        bodies = self._feet_list + [int(self.gripper_idx)] + ([0] if base_height is not None else [])
+        k = len(bodies)
+        pos = torch.zeros(n, k, 3, dtype=torch.float32, device=dev)
+        w = torch.zeros(n, k, 3, dtype=torch.float32, device=dev)
+        pos[:, :4] = self.rigid_body_state[:, self.feet_indices, :3]
+        w[:, :4] = 1.0 if stance is None else stance.bool().float().unsqueeze(-1)
+        pos[:, 4], w[:, 4] = ee_pos, 1.0
+        if base_height is not None:
+            pos[:, 5, 2], w[:, 5, 2] = base_height, 1.0
+        quat = w_ori = None
+        if ee_quat is not None:
+            quat = torch.zeros(n, k, 4, dtype=torch.float32, device=dev)
+            quat[..., 3] = 1.0
+            quat[:, 4] = ee_quat
+            w_ori = torch.zeros(n, k, dtype=torch.float32, device=dev)
+            w_ori[:, 4] = 1.0
+        q_ref = self.default_dof_pos.to(torch.float32).expand(n, -1).contiguous()
+        root, dof, info = self.sim.inverse_kinematics(bodies, pos, quat, w, w_ori, q_ref=q_ref, **opts)
+        total = info["iterations"]
+        for _ in range(int(refine)):
+            root, dof, info = self.sim.inverse_kinematics(bodies, pos, quat, w, w_ori, root_init=root, dof_init=dof, posture=refine_posture,
+                                                          damping=opts.get("damping", 1e-3), step_tol=refine_step_tol,
+                                                          max_iter=opts.get("max_iter", 0))
+            total = total + info["iterations"]
+        info = dict(info, iterations=total)
+        if apply:
+            rs, ds = self.sim.tensor("ROOT_STATES").clone(), self.sim.tensor("DOF_STATE").clone()
+            rs[:, 0, :7], rs[:, 0, 7:13] = root, 0.0
+            ds[..., 0], ds[..., 1] = dof, 0.0
+            self.sim.set_root_state(rs.contiguous())
+            self.sim.set_dof_state(ds.contiguous())
+        return root, dof, info
+
+    def ee_goal_reachable(self, ee_pos: torch.Tensor, tol: float = 1e-3, **opts) -> torch.Tensor:
+        """bool [N]: the gripper can reach ee_pos [N, 3] (world) with all four feet where they are and every joint inside its limits:
+        reach_configuration's last solve converged (status 0) and left the gripper within `tol` metres of the goal. The root and DoF
+        states are left untouched. opts: reach_configuration's."""
+        _, _, info = self.reach_configuration(ee_pos, **opts)
+        return (info["status"] == 0) & (info["residual"][:, 4, :3].norm(dim=-1) <= tol)
+
     # ---- centre of mass and centroidal momentum (no counterpart in the reference): one launch, include/wbc_sim.h: wbc_sim_centroidal ----
     def centre_of_mass(self):
         """(position [N, 3], velocity [N, 3]) of the robot's centre of mass in the world frame: the root position plus the kernel's

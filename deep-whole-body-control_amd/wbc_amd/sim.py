@@ -347,6 +347,39 @@ class WbcSim:
               "wbc_sim_impulse_dynamics")
         return out
 
+    # ---- whole-body inverse kinematics with joint limits (include/wbc_sim.h: wbc_sim_inverse_kinematics) ------------------------------
+    def inverse_kinematics(self, bodies, target_pos: torch.Tensor, target_quat: Optional[torch.Tensor] = None,
+                           w_pos: Optional[torch.Tensor] = None, w_ori: Optional[torch.Tensor] = None,
+                           root_init: Optional[torch.Tensor] = None, dof_init: Optional[torch.Tensor] = None,
+                           q_ref: Optional[torch.Tensor] = None, posture: float = 1e-2, damping: float = 1e-3, step_tol: float = 1e-4,
+                           max_iter: int = 0):
+        """wbc_sim_inverse_kinematics on the current stream, one launch: the configuration that puts the origins of the listed rigid
+        bodies (1..6 indices) at target_pos [N, K, 3] and, where target_quat [N, K, 4] (xyzw) is given, their frames at those
+        orientations, weighted by w_pos [N, K, 3] / w_ori [N, K] (None: ones; a row of weight 0 is skipped), regularised towards q_ref
+        [N, 20] (None: the start) with weight `posture` and kept inside the model's joint limits. The start is root_init [N, 7] /
+        dof_init [N, 20], None: the sim's current state, which is read and never written. damping: the initial Levenberg-Marquardt
+        factor; step_tol: metres / radians; max_iter: 0 = abi.IK_MAX_ITER. Returns (root_pose [N, 7], dof_pos [N, 20], info) with
+        info["status"] int32 [N] (0 converged, 1 iteration cap, 2 no descent: stationary or out of reach, 3 non-finite input),
+        info["iterations"] int32 [N], info["cost"] [N, 2] (start, output) and info["residual"] [N, K, 6] (target - x, phi)."""
+        n = self.num_envs
+        rbs = [int(r) for r in (bodies.tolist() if isinstance(bodies, torch.Tensor) else bodies)]
+        k = len(rbs)
+        assert 1 <= k <= abi.IK_MAX_TARGETS, k
+        for t, shape in ((target_pos, (n, k, 3)), (target_quat, (n, k, 4)), (w_pos, (n, k, 3)), (w_ori, (n, k)), (root_init, (n, 7)),
+                         (dof_init, (n, abi.NDOF)), (q_ref, (n, abi.NDOF))):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, tuple(t.shape)
+        new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=self.device)   # noqa: E731
+        root, dof = new((n, 7)), new((n, abi.NDOF))
+        info = dict(status=new((n,), torch.int32), iterations=new((n,), torch.int32), cost=new((n, 2)), residual=new((n, k, 6)))
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        opts = abi.WbcIkOpts(float(posture), float(damping), float(step_tol), int(max_iter))
+        check(self.L.wbc_sim_inverse_kinematics(self.h, (C.c_int32 * k)(*rbs), k, target_pos.data_ptr(), ptr(target_quat), ptr(w_pos), ptr(w_ori),
+                                                ptr(root_init), ptr(dof_init), ptr(q_ref), C.byref(opts), root.data_ptr(), dof.data_ptr(),
+                                                info["residual"].data_ptr(), info["cost"].data_ptr(), info["status"].data_ptr(),
+                                                info["iterations"].data_ptr(), self._stream()), "wbc_sim_inverse_kinematics")
+        return root, dof, info
+
     # ---- whole-body inverse dynamics for task-space accelerations (include/wbc_sim.h: wbc_sim_task_inverse_dynamics) ------------------
     def task_inverse_dynamics(self, stance_bodies=(), task_bodies=(), task_acc: Optional[torch.Tensor] = None,
                               task_weight: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,

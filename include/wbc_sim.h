@@ -745,6 +745,53 @@ int wbc_sim_impulse_dynamics(wbc_sim* sim, const int32_t* rigid_bodies /* host *
                              const float* restitution, const float* vel_des, const float* impulse_ext, float damping, int flags,
                              float* nu_plus, float* impulse, float* denergy, float* dnu_dnu, float* workspace, void* stream);
 
+/* Whole-body inverse kinematics with joint limits: which configuration puts the listed rigid bodies at the wanted poses. Per env, over
+ * the 24 live coordinates (root translation, root rotation, the 18 revolute joints; the fingers stay locked):
+ *     minimise  1/2 sum_k sum_{i<3} w_pos[k,i] (target_pos[k,i] - x_k(q)_i)^2 + 1/2 sum_k w_ori[k] |log(R_target,k R_k(q)^T)|^2
+ *             + 1/2 posture |q_j - q_ref|^2  (the 18 joints)         subject to  q_lower[j] <= q_j <= q_upper[j]
+ * x_k, R_k: world origin (rb_offset) and rotation of rigid body bodies[k], as wbc_sim_refresh_rigid_body_state reports them; limits
+ * from wbc_model, lower == upper == 0 meaning unlimited. Tangent: root translation in world axes, a WORLD rotation vector
+ * (R <- exp([dtheta]x) R) and joint increments, so the Gauss-Newton Jacobian of target k is rows 0:3 / 3:6 of wbc_sim_body_dynamics'
+ * J[bodies[k]]; for the scalar w_ori the orientation term's exact gradient is -w_ori J_ang^T phi.
+ * bodies       HOST array of 1..WBC_IK_MAX_TARGETS rigid-body indices; two entries on one moving body are allowed.
+ * target_pos   device f32 [N, nt, 3]. target_quat device f32 [N, nt, 4] (xyzw, normalised by the kernel) or NULL: no orientation rows.
+ * w_pos        device f32 [N, nt, 3], >= 0, or NULL (= ones). w_ori device f32 [N, nt] or NULL (= ones where target_quat is given);
+ *              NULL where target_quat is NULL. A row of weight 0 is skipped: its target is never loaded into arithmetic (a NaN there
+ *              does not spread) and its entry of residual is exactly 0.
+ * root_init    device f32 [N, 7] (position, xyzw quaternion) or NULL (= WBC_T_ROOT_STATES[:, 0, 0:7]); dof_init device f32 [N, 20] or
+ *              NULL (= WBC_T_DOF_STATE[..., 0]); start joints outside their limits are clamped before the first evaluation.
+ * q_ref        device f32 [N, 20] or NULL (= the clamped start joints).
+ * opts         HOST: posture >= 0; damping > 0, the initial Levenberg-Marquardt factor lambda0 on diag(H); step_tol > 0 (metres and
+ *              radians); max_iter 1..WBC_IK_MAX_ITER, 0 = WBC_IK_MAX_ITER.
+ * root_out     device f32 [N, 7]: a unit quaternion wherever a step was accepted; where none was (iterations 0, or status 3) the
+ *              start's own seven floats bit for bit, its quaternion as given and not re-normalised. dof_out device f32 [N, 20]: the
+ *              fingers are the start's bits, limited joints lie inside their limits exactly.
+ * residual     device f32 [N, nt, 6] or NULL: target - x and phi at the output. cost device f32 [N, 2] or NULL: the objective at the
+ *              start and at the output (cost[:,1] <= cost[:,0] bit-wise).
+ * status       device i32 [N] or NULL: 0 converged (the proposed projected step's infinity norm <= step_tol while lambda <= lambda0),
+ *              1 iteration cap, 2 no descent before the damping reached its ceiling (stationary to fp32 resolution, or a target out of
+ *              reach), 3 a non-finite input of that env (its outputs are the start; no other env is affected).
+ * iterations   device i32 [N] or NULL: candidates evaluated.
+ * Projected Levenberg-Marquardt: H = J^T W J + posture S^T S and g in LDS; a joint at a limit whose gradient pushes outward gets the
+ * identity's row and column; (H + lambda diag H + floor) d = -g; where a free joint's step would leave its limits, that joint goes
+ * onto the limit and the others solve once more with its step held; retract, clamp, evaluate; accepted if the cost did not rise
+ * (lambda /= 8), else lambda *= 8. The point returned is the last accepted one. Positions are carried relative to the start root
+ * position p0: under a translation S of start and targets that is exact in fp32 every output but root_out[:, 0:3] is bit-identical,
+ * and root_out[:, 0:3] = fl(p0 + d) with the same bits of the relative position d, so it moves by S to within one ulp of the moved
+ * value (fl(p0 + S + d) is not fl(p0 + d) + S in general).
+ * The sim's state is read and never written. One launch (wbc_ik_kernel), no workspace, nothing allocated: safe under stream capture and
+ * on any stream.
+ * -1 with a message in wbc_last_error() that names this entry point, nothing written: NULL sim / bodies / target_pos / opts / root_out /
+ * dof_out; ntargets out of range; a body index outside 0..WBC_NRB-1; w_ori without target_quat; an opts field out of range or not
+ * finite; a pointer that is not 4-byte aligned. The checks that need no sim are made first. -3 and -2 as wbc_sim_mass_solve. */
+#define WBC_IK_MAX_TARGETS 6
+#define WBC_IK_MAX_ITER 64
+typedef struct { float posture, damping, step_tol; int32_t max_iter; } wbc_ik_opts;
+int wbc_sim_inverse_kinematics(wbc_sim* sim, const int32_t* bodies /* host */, int ntargets, const float* target_pos,
+                               const float* target_quat, const float* w_pos, const float* w_ori, const float* root_init,
+                               const float* dof_init, const float* q_ref, const wbc_ik_opts* opts /* host */, float* root_out,
+                               float* dof_out, float* residual, float* cost, int32_t* status, int32_t* iterations, void* stream);
+
 /* Whole-body inverse dynamics for task-space accelerations: the joint torques that produce wanted accelerations of a few rigid bodies
  * while the stance feet stay put. Coordinates, nu, nudot, tau rows and rigid-body indices are those of wbc_sim_body_dynamics /
  * wbc_sim_inverse_dynamics / wbc_sim_constrained_dynamics; state, WBC_T_BODY_PARAMS and all three gravity components as there. Per env:

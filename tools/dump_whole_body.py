@@ -102,6 +102,32 @@ def keep_impulse(sim, name, feet, grip):
     keep(name + "imp.1.plain", r["nu_plus"], r["impulse"])
 
 
+def keep_ik(sim, name, feet, grip):
+    """wbc_sim_inverse_kinematics (a generator of its own): the feet and the gripper at the poses of the sim's own state from a start
+    perturbed by +-0.1 rad with q_ref the state's joints (reachable), and the same with the gripper's target 2 m from the trunk
+    (unreachable); status and iterations are stored by value."""
+    n = sim.num_envs
+    g = torch.Generator(device="cuda"); g.manual_seed(8000 + n)
+    sign = lambda *shape: (torch.randint(0, 2, shape, device="cuda", generator=g).float() * 2 - 1)   # noqa: E731
+    sim.refresh_rigid_body_state()
+    rb = sim.tensor("RIGID_BODY_STATE")
+    bodies = feet + [grip]
+    tpos, tquat = rb[:, bodies, 0:3].clone().contiguous(), rb[:, bodies, 3:7].clone().contiguous()
+    w_ori = torch.zeros(n, 5, device="cuda"); w_ori[:, 4] = 1.0
+    root = sim.tensor("ROOT_STATES")[:, 0, :7].clone().contiguous()
+    q = sim.tensor("DOF_STATE")[..., 0].clone().contiguous()
+    dof_init = q.clone(); dof_init[:, :18] += 0.1 * sign(n, 18)
+    root_init = root.clone(); root_init[:, :3] += 0.025 * sign(n, 3)
+    for tag, tp in (("reach", tpos), ("far", tpos.clone())):
+        if tag == "far":
+            d = tp[:, 4] - root[:, :3]
+            tp[:, 4] = root[:, :3] + 2.0 * d / d.norm(dim=-1, keepdim=True)
+        r, dof, info = sim.inverse_kinematics(bodies, tp.contiguous(), tquat, None, w_ori, root_init, dof_init.contiguous(), q)
+        torch.cuda.synchronize()
+        print(f"{name}ik.{tag}: status counts {torch.bincount(info['status'], minlength=4).tolist()}, most iterations {int(info['iterations'].max())}")
+        keep(name + "ik." + tag, r, dof, info["residual"], info["cost"], info["status"].float(), info["iterations"].float())
+
+
 for n in (1, 13, 64, 273):
     cfg = WidowGo1RoughCfg(); cfg.env.num_envs = n; cfg.terrain.mesh_type = "plane"
     env = WidowGo1(cfg, sim_device="cuda:0", seed=5)
@@ -188,6 +214,7 @@ for n in (1, 13, 64, 273):
     keep(T + "fdd.tau_null", *fd)
     keep_cdd(sim, T, feet, grip, tau, g)           # last of the shared generator: its earlier draws stay what they were
     keep_impulse(sim, T, feet, grip)
+    keep_ik(sim, T, feet, grip)
 
 np.savez(sys.argv[1], **out)
 print(f"{len(out)} arrays, {sum(a.size for a in out.values())} words -> {sys.argv[1]}")
