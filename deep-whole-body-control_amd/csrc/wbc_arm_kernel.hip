@@ -3562,3 +3562,319 @@ extern "C" int wbc_sim_inverse_kinematics(wbc_sim* s, const int32_t* bodies, int
   hipLaunchKernelGGL(wbc_ik_kernel, dim3((n + IK_EPW - 1) / IK_EPW), dim3(64), 0, (hipStream_t)stream, C, a);
   return c.launched();
 }
+
+// ---- Coriolis matrix, dM/dt, generalised momentum and the momentum observer (include/wbc_sim.h: wbc_sim_coriolis) ----------------------
+// C(q, nu) of M nudot + C nu + g = tau in the factorisation with C + C^T = dM/dt (Echeandia and Wensing):
+//     C = sum_k J_k^T (I_k Jdot_k + B_k J_k),    B_k = 1/2 [crf(v_k) I_k + crfbar(I_k v_k) - I_k crm(v_k)],
+// every spatial vector (angular; linear) about F's origin in F's axes AS AN INERTIAL FRAME that coincides with the base at this instant:
+// the root's own origin has the lever 0 and the velocity v_root. With I_k = [Ib, h x; -h x, m] (h = m c), v_k = (w; u) and the momentum
+// I_k v_k = (n; l), B_k has two non-zero blocks only,
+//     B_k = [B11, 0; -l x, 0],    2 B11 = P + P^T - h u^T - u h^T + 2 (u . h) 1 - n x,    P = w x Ib,
+// so that B_k^T v_k = 0 and the whole of C's first three columns (the root's linear coordinates) is structurally 0. Over the tree the sum
+// collapses to C[r, c] = S_r . (Ic_d Sdot_c + Bc_d S_c), d the deeper of the two coordinates' bodies, Ic / Bc the subtree's sums.
+// Two envs per 64-lane workgroup, one per 32-lane half:
+//  1) lane b = moving body b walks root -> b as wbc_inverse_dynamics_kernel does (tree_frame_step per joint) with the frame and the
+//     spatial velocity in registers; its joint's S and Sdot = v_parent x S, its momentum (n; l) and, for the matrices, I_k and B11 go to LDS;
+//  2) lane c = coordinate c sums the subtree it moves through the ancestor masks, in registers: p_c = S_c . h^C, (C^T nu)_c = Sdot_c . h^C
+//     leave from here (and the observer's update, if asked for); for the matrices f_c = Ic Sdot_c + Bc S_c, Ic S_c and Bc^T S_c go to LDS;
+//  3) the 26 x 26 entries, one or two six-term products each, into an LDS tile; C leaves as the tile, dM/dt as tile + tile^T, both in
+//     contiguous 16-byte stores.
+// The vector kernel is the same text without step 3 and without anything 26 x 26. What both kernels share (the walk, the momenta, the
+// sums, the two projections) is written with explicit fused multiply-adds where a product meets a sum and is compiled without
+// contraction otherwise, so that `vec` has the same bits from either kernel. The root position is never read.
+#define CO_EPW 2                                // envs per workgroup
+#define CO_LPE (64 / CO_EPW)                    // lanes per env
+#define CO_BT 28                                // floats per body, matrices: n 0..2, l 3..5, m 6, h 7..9, Ib xx yy zz xy xz yz 10..15, B11 16..24
+#define CO_BV 8                                 // floats per body, vectors: n 0..2, l 3..5
+#define CO_CT 28                                // floats per coordinate: S 0..5, Sdot 6..11, f 12..17, Ic S 18..23, angular part of Bc^T S 24..26
+static_assert(WBC_NB <= CO_LPE && BD_NCOL <= CO_LPE && BD_MENV % 4 == 0, "lanes");
+struct CoObs {                                  // the observer's update in the vector kernel's epilogue; state NULL: none
+  const float *tau, *grav;
+  float gain, dt;
+  int reset;
+  float* state;
+};
+
+__device__ __forceinline__ float co_dot3(float a, float b, float c, f3 v) { return __builtin_fmaf(c, v.z, __builtin_fmaf(b, v.y, a * v.x)); }
+__device__ __forceinline__ f3 co_cross(f3 a, f3 b) {
+  return mk3(__builtin_fmaf(a.y, b.z, -(a.z * b.y)), __builtin_fmaf(a.z, b.x, -(a.x * b.z)), __builtin_fmaf(a.x, b.y, -(a.y * b.x)));
+}
+__device__ __forceinline__ float co_dot6(const float* a, const float* b) {
+  float s = a[0] * b[0];
+#pragma unroll
+  for (int j = 1; j < 6; ++j) s = __builtin_fmaf(a[j], b[j], s);
+  return s;
+}
+// A value the compiler cannot look through: what only the matrix kernel computes starts from such copies, so that none of its
+// expressions is merged with one of the shared text.
+__device__ __forceinline__ float co_opaque(float x) { asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ f3 co_opaque(f3 v) { return mk3(co_opaque(v.x), co_opaque(v.y), co_opaque(v.z)); }
+// (Ib w + h x v; w x h + m v) of the spatial inertia I = (m, h, Ib xx yy zz xy xz yz) at I[0..9].
+__device__ __forceinline__ void co_inertia_mul(const float* I, const float* s, float* o) {
+  const f3 w = mk3(s[0], s[1], s[2]), v = mk3(s[3], s[4], s[5]), h = mk3(I[1], I[2], I[3]);
+  const f3 hv = co_cross(h, v), wh = co_cross(w, h);
+  o[0] = co_dot3(I[4], I[7], I[8], w) + hv.x; o[1] = co_dot3(I[7], I[5], I[9], w) + hv.y; o[2] = co_dot3(I[8], I[9], I[6], w) + hv.z;
+  o[3] = __builtin_fmaf(I[0], v.x, wh.x); o[4] = __builtin_fmaf(I[0], v.y, wh.y); o[5] = __builtin_fmaf(I[0], v.z, wh.z);
+}
+
+template <bool MAT>
+__device__ __forceinline__ void coriolis_body(const TreeConst& K, const float* __restrict__ root, const float* __restrict__ dofs,
+                                              const float* __restrict__ body_params, int n, float* __restrict__ cmat,
+                                              float* __restrict__ mdot, float* __restrict__ vec, const CoObs& ob) {
+#pragma clang fp contract(off)
+  constexpr int BT = MAT ? CO_BT : CO_BV, NT = MAT ? 25 : 6;
+  // per body: the table above, then the body's joint in F: S (axis; origin x axis) and Sdot. Dead after step 2: step 3's tile (C as
+  // stored) lies over them.
+  constexpr int BS = WBC_NB * (BT + 12);
+  static_assert(!MAT || BS >= BD_MENV, "the tile lies over the body tables");
+  __shared__ __align__(16) float sBS[CO_EPW][BS];
+  __shared__ __align__(16) float sC[MAT ? CO_EPW : 1][MAT ? BD_NCOL : 1][CO_CT];
+  __shared__ int32_t sCb[MAT ? CO_EPW : 1][BD_NCOL];
+  __shared__ uint32_t sAnc[MAT ? CO_EPW : 1][WBC_NB];
+  const int half = threadIdx.x >> 5, lane = threadIdx.x & 31;
+  float *sB = sBS[half], *sS = sBS[half] + WBC_NB * BT;
+  const int env = blockIdx.x * CO_EPW + half;
+  const bool live = env < n;
+  const size_t e = live ? env : n - 1;             // the idle half of the last workgroup recomputes the last env and stores nothing
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+  const f3 v0 = matT_mul(R, ld3(root + e * 26 + 7)), w0 = matT_mul(R, ld3(root + e * 26 + 10));   // the root's velocity in F
+
+  if (lane < WBC_NB) {
+    const int b = lane;
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    f3 p = mk3(0.f, 0.f, 0.f), Sw = p, Sv = p, Dw = p, Dv = p, vw = w0, vv = v0;
+#pragma nounroll
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
+      const int a = K.path[b][k];
+      if (a < 0) break;
+      const int d = K.dof[a];
+      float Q[9];
+      const f3 u = tree_joint_rot(K.axis[a], dofs[e * (2 * WBC_NDOF) + 2 * d], Q);
+      Sw = tree_frame_step(E, p, Q, K.joint_xyz[a], u);
+      Sv = co_cross(p, Sw);
+      Dw = co_cross(vw, Sw);                                   // Sdot = v_parent x S
+      Dv = co_cross(vw, Sv) + co_cross(vv, Sw);
+      const float qd = dofs[e * (2 * WBC_NDOF) + 2 * d + 1];
+      vw = mk3(__builtin_fmaf(Sw.x, qd, vw.x), __builtin_fmaf(Sw.y, qd, vw.y), __builtin_fmaf(Sw.z, qd, vw.z));
+      vv = mk3(__builtin_fmaf(Sv.x, qd, vv.x), __builtin_fmaf(Sv.y, qd, vv.y), __builtin_fmaf(Sv.z, qd, vv.z));
+    }
+    // spatial inertia about F's origin: the per-env root composite and gripper body (body_params), the model's otherwise
+    float m = K.mass[b], com[3] = {K.com[b][0], K.com[b][1], K.com[b][2]}, I6[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) I6[j] = K.inertia[b][j];
+    const int slot = b == 0 ? TREE_BP_ROOT : (b == K.gripper_body ? TREE_BP_GRIPPER : -1);
+    if (slot >= 0) {
+      const float* bp = body_params + e * TREE_BP_STRIDE + slot;
+      m = bp[0];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) I6[j] = bp[4 + j];
+    }
+    // every sum of products below names its fused multiply-adds: left to the compiler, which product of a sum it fuses depends on what
+    // else uses that product, and that differs between the two kernels
+    const f3 cm = mk3(com[0], com[1], com[2]);
+    const f3 C = mk3(p.x + co_dot3(E[0], E[1], E[2], cm), p.y + co_dot3(E[3], E[4], E[5], cm), p.z + co_dot3(E[6], E[7], E[8], cm));
+    const f3 h = mk3(m * C.x, m * C.y, m * C.z);
+    float EI[9], Ibar[6];                                      // E I_b E^T, as tree_rotate_inertia
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const float a = E[r * 3], b2 = E[r * 3 + 1], c2 = E[r * 3 + 2];
+      EI[r * 3] = co_dot3(a, b2, c2, mk3(I6[0], I6[3], I6[4]));
+      EI[r * 3 + 1] = co_dot3(a, b2, c2, mk3(I6[3], I6[1], I6[5]));
+      EI[r * 3 + 2] = co_dot3(a, b2, c2, mk3(I6[4], I6[5], I6[2]));
+    }
+    Ibar[0] = co_dot3(EI[0], EI[1], EI[2], mk3(E[0], E[1], E[2])); Ibar[1] = co_dot3(EI[3], EI[4], EI[5], mk3(E[3], E[4], E[5]));
+    Ibar[2] = co_dot3(EI[6], EI[7], EI[8], mk3(E[6], E[7], E[8])); Ibar[3] = co_dot3(EI[0], EI[1], EI[2], mk3(E[3], E[4], E[5]));
+    Ibar[4] = co_dot3(EI[0], EI[1], EI[2], mk3(E[6], E[7], E[8])); Ibar[5] = co_dot3(EI[3], EI[4], EI[5], mk3(E[6], E[7], E[8]));
+    const float CC = co_dot3(C.x, C.y, C.z, C);
+    const float Ib[6] = {__builtin_fmaf(m, CC - C.x * C.x, Ibar[0]), __builtin_fmaf(m, CC - C.y * C.y, Ibar[1]),
+                         __builtin_fmaf(m, CC - C.z * C.z, Ibar[2]), __builtin_fmaf(-h.x, C.y, Ibar[3]),
+                         __builtin_fmaf(-h.x, C.z, Ibar[4]), __builtin_fmaf(-h.y, C.z, Ibar[5])};
+    // the body's spatial momentum (n; l) = I_k v_k
+    const f3 hu = co_cross(h, vv), wh = co_cross(vw, h);
+    const f3 nn = mk3(co_dot3(Ib[0], Ib[3], Ib[4], vw) + hu.x, co_dot3(Ib[3], Ib[1], Ib[5], vw) + hu.y, co_dot3(Ib[4], Ib[5], Ib[2], vw) + hu.z);
+    const f3 ll = mk3(__builtin_fmaf(m, vv.x, wh.x), __builtin_fmaf(m, vv.y, wh.y), __builtin_fmaf(m, vv.z, wh.z));
+    float* o = sB + b * BT;
+    st3(o, nn); st3(o + 3, ll);
+    if (MAT) {
+      const f3 w2 = co_opaque(vw), u2 = co_opaque(vv), h2 = co_opaque(h), n2 = co_opaque(nn);
+      float I2[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) I2[j] = co_opaque(Ib[j]);
+      o[6] = m; st3(o + 7, h2);
+#pragma unroll
+      for (int j = 0; j < 6; ++j) o[10 + j] = I2[j];
+      // 2 B11 = P + P^T - h u^T - u h^T + 2 (u . h) 1 - n x, column j of P = w x (column j of Ib)
+      const f3 P0 = co_cross(w2, mk3(I2[0], I2[3], I2[4])), P1 = co_cross(w2, mk3(I2[3], I2[1], I2[5])), P2 = co_cross(w2, mk3(I2[4], I2[5], I2[2]));
+      const float P[9] = {P0.x, P1.x, P2.x, P0.y, P1.y, P2.y, P0.z, P1.z, P2.z};
+      const float hv[3] = {h2.x, h2.y, h2.z}, uv[3] = {u2.x, u2.y, u2.z}, uh2 = 2.f * co_dot3(u2.x, u2.y, u2.z, h2);
+      const float N[9] = {0.f, -n2.z, n2.y, n2.z, 0.f, -n2.x, -n2.y, n2.x, 0.f};
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          float s = (P[i * 3 + j] + P[j * 3 + i]) - (hv[i] * uv[j] + uv[i] * hv[j]);
+          if (i == j) s += uh2;
+          else s -= N[i * 3 + j];
+          o[16 + i * 3 + j] = 0.5f * s;
+        }
+      sAnc[half][b] = K.anc[b];
+    }
+    float* q = sS + b * 12;
+    st3(q, Sw); st3(q + 3, Sv); st3(q + 6, Dw); st3(q + 9, Dv);
+  }
+  __syncthreads();
+
+  if (lane < BD_NCOL) {
+    const int c = lane, b = c < 6 ? 0 : K.col_body[c - 6], bb = b < 0 ? 0 : b;
+    float S[6], D[6];                                          // the coordinate's motion vector in F and its rate
+    if (c < 6) {                                               // world-frame root coordinates: rows of R; Sdot = (0; v_root x e_j)
+      const int j = c < 3 ? c : c - 3;
+      const f3 row = matT_mul(R, mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f)), dr = co_cross(v0, row);
+      const bool lin = c < 3;
+      S[0] = lin ? 0.f : row.x; S[1] = lin ? 0.f : row.y; S[2] = lin ? 0.f : row.z;
+      S[3] = lin ? row.x : 0.f; S[4] = lin ? row.y : 0.f; S[5] = lin ? row.z : 0.f;
+      D[0] = D[1] = D[2] = 0.f;
+      D[3] = lin ? 0.f : dr.x; D[4] = lin ? 0.f : dr.y; D[5] = lin ? 0.f : dr.z;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) { S[j] = sS[bb * 12 + j]; D[j] = sS[bb * 12 + 6 + j]; }
+    }
+    float acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[j] = 0.f;
+    for (int d = 0; d < WBC_NB; ++d) {                         // the subtree's sums: everything is already about F's origin
+      const bool in = (K.anc[d] >> bb) & 1u;
+#pragma unroll
+      for (int j = 0; j < NT; ++j) acc[j] += in ? sB[d * BT + j] : 0.f;
+    }
+    const float pv = b >= 0 ? co_dot6(S, acc) : 0.f, ct = b >= 0 ? co_dot6(D, acc) : 0.f;
+    if (live) {
+      if (vec) { vec[e * (2 * BD_NCOL) + c] = pv; vec[e * (2 * BD_NCOL) + BD_NCOL + c] = ct; }
+      if (!MAT && ob.state) {                                  // the observer: fingers exactly 0
+        float* st = ob.state + e * (2 * BD_NCOL);
+        float integral = pv, residual = 0.f;
+        if (!ob.reset) {
+          const float t = ob.tau ? ob.tau[e * BD_NCOL + c] : 0.f;
+          integral = st[c] + ob.dt * (((t + ct) - ob.grav[e * BD_NCOL + c]) + st[BD_NCOL + c]);
+          residual = ob.gain * (pv - integral);
+        }
+        st[c] = b >= 0 ? integral : 0.f; st[BD_NCOL + c] = b >= 0 ? residual : 0.f;
+      }
+    }
+    if (MAT) {
+      float* o = sC[half][c];
+      float f[6], g[6];
+#pragma unroll
+      for (int j = 0; j < NT; ++j) acc[j] = co_opaque(acc[j]);
+#pragma unroll
+      for (int j = 0; j < 6; ++j) { S[j] = co_opaque(S[j]); D[j] = co_opaque(D[j]); }
+      co_inertia_mul(acc + 6, D, f);
+      co_inertia_mul(acc + 6, S, g);
+      const f3 sw = mk3(S[0], S[1], S[2]), sv = mk3(S[3], S[4], S[5]), lc = mk3(acc[3], acc[4], acc[5]);
+      const f3 lw = co_cross(lc, sw), lv = co_cross(lc, sv);   // Bc S = (B11 w; -l x w), Bc^T S = (B11^T w + l x v; 0)
+      f[0] += co_dot3(acc[16], acc[17], acc[18], sw); f[1] += co_dot3(acc[19], acc[20], acc[21], sw); f[2] += co_dot3(acc[22], acc[23], acc[24], sw);
+      f[3] -= lw.x; f[4] -= lw.y; f[5] -= lw.z;
+#pragma unroll
+      for (int j = 0; j < 6; ++j) { o[j] = S[j]; o[6 + j] = D[j]; o[12 + j] = f[j]; o[18 + j] = g[j]; }
+      o[24] = co_dot3(acc[16], acc[19], acc[22], sw) + lv.x;
+      o[25] = co_dot3(acc[17], acc[20], acc[23], sw) + lv.y;
+      o[26] = co_dot3(acc[18], acc[21], acc[24], sw) + lv.z;
+      sCb[half][c] = b;
+    }
+  }
+  if constexpr (MAT) {
+    __syncthreads();
+
+    // C[r, c]: r above c (or both on the root): S_r . f_c; r below c: (Ic_r S_r) . Sdot_c + (Bc_r^T S_r) . S_c; the root's linear columns,
+    // the fingers and the pairs of which neither moves the other: 0
+    for (int t = lane; t < BD_MENV; t += CO_LPE) {
+      const int r = t / BD_NCOL, c = t - r * BD_NCOL;
+      const int br = sCb[half][r], bc = sCb[half][c];
+      float x = 0.f;
+      if (br >= 0 && bc >= 0 && c >= 3) {
+        const float *cr = sC[half][r], *cc = sC[half][c];
+        if ((sAnc[half][bc] >> br) & 1u) x = co_dot6(cr, cc + 12);
+        else if ((sAnc[half][br] >> bc) & 1u) x = co_dot6(cr + 18, cc + 6) + co_dot3(cr[24], cr[25], cr[26], mk3(cc[0], cc[1], cc[2]));
+      }
+      sBS[half][t] = x;
+    }
+    __syncthreads();
+    if (!live) return;
+    const float* T = sBS[half];
+    if (cmat) {
+      float4* out = reinterpret_cast<float4*>(cmat + e * BD_MENV);
+      for (int t = lane; t < BD_MENV / 4; t += CO_LPE) out[t] = reinterpret_cast<const float4*>(T)[t];
+    }
+    if (mdot) {                                                  // dM/dt = C + C^T from the tile: symmetric and equal to cmat + cmat^T bit for bit
+      float4* out = reinterpret_cast<float4*>(mdot + e * BD_MENV);
+      for (int t = lane; t < BD_MENV / 4; t += CO_LPE) {
+        float v[4];
+        int i = (4 * t) / BD_NCOL, j = 4 * t - i * BD_NCOL;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          v[u] = T[i * BD_NCOL + j] + T[j * BD_NCOL + i];
+          if (++j == BD_NCOL) { j = 0; ++i; }
+        }
+        out[t] = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    }
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(64) wbc_coriolis_kernel(TreeConst K, const float* __restrict__ root, const float* __restrict__ dofs,
+                                                                    const float* __restrict__ body_params, int n, float* __restrict__ cmat,
+                                                                    float* __restrict__ mdot, float* __restrict__ vec) {
+  const CoObs none = {nullptr, nullptr, 0.f, 0.f, 0, nullptr};
+  coriolis_body<true>(K, root, dofs, body_params, n, cmat, mdot, vec, none);
+}
+
+extern "C" __global__ void __launch_bounds__(64) wbc_momentum_kernel(TreeConst K, const float* __restrict__ root, const float* __restrict__ dofs,
+                                                                    const float* __restrict__ body_params, int n, float* __restrict__ vec,
+                                                                    CoObs ob) {
+  coriolis_body<false>(K, root, dofs, body_params, n, nullptr, nullptr, vec, ob);
+}
+
+static int coriolis_launch(const WbCall& c, float* cmat, float* mdot, float* vec, const CoObs& ob, void* stream) {
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
+  TreeConst K;
+  if (tree_const_fill(c.hc->model, K) != 0) return c.no_tree();
+  const dim3 grid((c.n + CO_EPW - 1) / CO_EPW);
+  if (cmat || mdot) hipLaunchKernelGGL(wbc_coriolis_kernel, grid, dim3(64), 0, (hipStream_t)stream, K, c.root, c.dofs, c.bp, c.n, cmat, mdot, vec);
+  else hipLaunchKernelGGL(wbc_momentum_kernel, grid, dim3(64), 0, (hipStream_t)stream, K, c.root, c.dofs, c.bp, c.n, vec, ob);
+  return c.launched();
+}
+
+// cmat / mdot (device f32 [N,26,26], 16-byte aligned), vec (device f32 [N,2,26]: p, C^T nu), caller-owned, any may be NULL: include/wbc_sim.h.
+extern "C" int wbc_sim_coriolis(wbc_sim* s, float* cmat, float* mdot, float* vec, void* stream) {
+  WbCall c("wbc_sim_coriolis", s, stream);
+  if (!s) return c.no_sim();
+  if (!cmat && !mdot && !vec) return c.fail(-1, "cmat, mdot and vec are all NULL");
+  if (((uintptr_t)cmat | (uintptr_t)mdot) & 15u) return c.fail(-1, "cmat / mdot must be 16-byte aligned");
+  if ((uintptr_t)vec & 3u) return c.fail(-1, "vec must be 4-byte aligned");
+  const CoObs none = {nullptr, nullptr, 0.f, 0.f, 0, nullptr};
+  return coriolis_launch(c, cmat, mdot, vec, none, stream);
+}
+
+// Two launches: g(q) into the sim's [N, 26] scratch (wbc_inverse_dynamics_kernel), then the vector kernel with the update in its epilogue.
+extern "C" int wbc_sim_momentum_observer(wbc_sim* s, const float* tau, float gain, float dt, int flags, float* state, void* stream) {
+  WbCall c("wbc_sim_momentum_observer", s, stream);
+  if (!s) return c.no_sim();
+  if (!state) return c.fail(-1, "state is NULL");
+  if (flags & ~WBC_OBSERVER_RESET) return c.fail(-1, "unknown flag bits");
+  if (!(gain > 0.f) || !(gain <= 3.4e38f)) return c.fail(-1, "gain must be finite and > 0");
+  if (!(dt > 0.f) || !(dt <= 3.4e38f)) return c.fail(-1, "dt must be finite and > 0");
+  if (!(gain * dt < 1.f)) return c.fail(-1, "gain * dt must be below 1");
+  if (((uintptr_t)tau | (uintptr_t)state) & 3u) return c.fail(-1, "tau / state must be 4-byte aligned");
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
+  float* g = nullptr;
+  if (wbc_sim_internal_fd_scratch(s, &g) != 0) return -1;
+  const int rc = wbc_sim_inverse_dynamics(s, nullptr, nullptr, g, stream);
+  if (rc != 0) return rc;
+  const CoObs ob = {tau, g, gain, dt, (flags & WBC_OBSERVER_RESET) ? 1 : 0, state};
+  return coriolis_launch(c, nullptr, nullptr, nullptr, ob, stream);
+}

@@ -108,6 +108,7 @@ class WbcTaskIdWeights(C.Structure):
 TASKQP_MAX_ITER = 128     # WBC_TASKQP_MAX_ITER
 SOLVE_ARMATURE, DERIV_TRANSPOSED, REGRESSOR_NATIVE = 1, 2, 4   # WBC_SOLVE_ARMATURE, WBC_DERIV_TRANSPOSED, WBC_REGRESSOR_NATIVE: one `flags` word
 WBC_REGRESSOR_NATIVE = REGRESSOR_NATIVE
+OBSERVER_RESET = 1         # WBC_OBSERVER_RESET (wbc_sim_momentum_observer's own flags word)
 NPARAM = 10               # inertial parameters per moving body (include/wbc_sim.h: wbc_sim_inverse_dynamics_regressor)
 
 

@@ -707,6 +707,29 @@ class WidowGo1(LeggedRobot):
         inr = self.sim.centroidal()[3]
         return inr[:, 0], inr[:, [1, 4, 5, 4, 2, 6, 5, 6, 3]].view(-1, 3, 3)
 
+    # ---- Coriolis matrix and momentum observer (no counterpart in the reference): include/wbc_sim.h: wbc_sim_coriolis ----
+    def coriolis_matrix(self) -> torch.Tensor:
+        """A fresh f32 [N, 26, 26] C(q, nu) of M nudot + C nu + g = tau in the coordinates of mm_whole, in the factorisation with
+        C + C^T = dM/dt: C nu == bias_forces - gravity_forces. One launch."""
+        return self.sim.coriolis(cmat=torch.empty((self.num_envs, 26, 26), dtype=torch.float32, device=self.device))[0]
+
+    def mass_matrix_rate(self) -> torch.Tensor:
+        """A fresh f32 [N, 26, 26] dM/dt of mm_whole along the current velocity, bit-symmetric. One launch."""
+        return self.sim.coriolis(mdot=torch.empty((self.num_envs, 26, 26), dtype=torch.float32, device=self.device))[0]
+
+    def generalized_momentum(self) -> torch.Tensor:
+        """A fresh f32 [N, 26] p = mm_whole nu, without forming the matrix. One launch of the vector kernel."""
+        return self.sim.coriolis(vec=torch.empty((self.num_envs, 2, 26), dtype=torch.float32, device=self.device))[0][:, 0]
+
+    def external_torque_estimate(self, gain: float, reset: bool = False) -> torch.Tensor:
+        """The momentum observer's residual f32 [N, 26] after one update at the current state with the env's own joint torques
+        (`torques`, rows 6:; no known wrench on the root) and control step `dt`: a first-order low-pass, of bandwidth `gain` (1/s,
+        gain dt < 1), of the generalised forces the model does not explain -- contacts, pushes, a payload. Call it once per step();
+        the first call, and any call with reset, starts the observer at the current momentum with residual 0."""
+        tau = torch.zeros((self.num_envs, 26), dtype=torch.float32, device=self.device)
+        tau[:, 6:] = self.torques
+        return self.sim.momentum_observer(tau, gain, self.dt, reset=reset)[:, 1]
+
     # ---- first-order layer (no counterpart in the reference): include/wbc_sim.h: wbc_sim_inverse_dynamics_derivatives ----
     def inverse_dynamics_derivatives(self, nudot: torch.Tensor = None):
         """(dtau_dq, dtau_dnu), fresh f32 [N, 26, 26] indexed [N, i, j] = d tau_i / d x_j of inverse_dynamics(nudot) at the current

@@ -68,6 +68,8 @@ def lib():
         L.wbc_sim_forward_dynamics.argtypes = [c_void, c_void, c_void, c_int, c_void]
         L.wbc_sim_body_accelerations.argtypes = [c_void, c_void, c_void, c_void]
         L.wbc_sim_centroidal.argtypes = [c_void] * 7
+        L.wbc_sim_coriolis.argtypes = [c_void] * 5
+        L.wbc_sim_momentum_observer.argtypes = [c_void, c_void, C.c_float, C.c_float, c_int, c_void, c_void]
         L.wbc_sim_inverse_dynamics_derivatives.argtypes = [c_void, c_void, c_void, c_void, c_int, c_void]
         L.wbc_sim_forward_dynamics_derivatives_workspace_floats.argtypes = [c_int]
         L.wbc_sim_forward_dynamics_derivatives_workspace_floats.restype = C.c_size_t

@@ -501,6 +501,42 @@ class WbcSim:
                                         self._stream()), "wbc_sim_centroidal")
         return tuple(outs)
 
+    # ---- Coriolis matrix, dM/dt, generalised momentum and the momentum observer (include/wbc_sim.h: wbc_sim_coriolis) -------------------
+    def coriolis(self, cmat: Optional[torch.Tensor] = None, mdot: Optional[torch.Tensor] = None, vec: Optional[torch.Tensor] = None):
+        """One wbc_sim_coriolis launch on the current stream into the tensors that are passed; returns the tensors it filled, in the
+        order (cmat [N, 26, 26] = C(q, nu), mdot [N, 26, 26] = dM/dt = C + C^T, vec [N, 2, 26] = (M nu, C^T nu)). With none passed all
+        three are allocated and filled. vec alone takes the vector kernel, which forms nothing 26 x 26."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        shapes = ((n, ncol, ncol), (n, ncol, ncol), (n, 2, ncol))
+        outs = [cmat, mdot, vec]
+        if all(t is None for t in outs):
+            outs = [torch.empty(sh, dtype=torch.float32, device=self.device) for sh in shapes]
+        for t, sh in zip(outs, shapes):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        check(self.L.wbc_sim_coriolis(self.h, *[t.data_ptr() if t is not None else None for t in outs], self._stream()), "wbc_sim_coriolis")
+        return tuple(t for t in outs if t is not None)
+
+    def momentum_observer(self, tau: Optional[torch.Tensor], gain: float, dt: float, state: Optional[torch.Tensor] = None,
+                          reset: bool = False) -> torch.Tensor:
+        """One wbc_sim_momentum_observer update on the current stream at the sim's current state; returns state f32 [N, 2, 26] (the
+        integral, then the residual: the estimate of the generalised forces that tau [N, 26] does not hold; tau None: zeros). state None:
+        the observer's own tensor, allocated on first use (and then reset, whatever `reset` says) and kept. gain > 0, dt > 0,
+        gain dt < 1. Uses the sim's bias-force scratch: one stream at a time per sim."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        if state is None:
+            state = self.__dict__.get("_observer_state")
+            if state is None:
+                state = self._observer_state = torch.zeros((n, 2, ncol), dtype=torch.float32, device=self.device)
+                reset = True
+        for t, sh in ((tau, (n, ncol)), (state, (n, 2, ncol))):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        check(self.L.wbc_sim_momentum_observer(self.h, tau.data_ptr() if tau is not None else None, float(gain), float(dt),
+                                               abi.OBSERVER_RESET if reset else 0, state.data_ptr(), self._stream()),
+              "wbc_sim_momentum_observer")
+        return state
+
     # ---- analytic derivatives of inverse and forward dynamics (include/wbc_sim.h: wbc_sim_inverse_dynamics_derivatives) ----------------
     def inverse_dynamics_derivatives(self, nudot: Optional[torch.Tensor] = None, dq: Optional[torch.Tensor] = None,
                                      dnu: Optional[torch.Tensor] = None, transposed: bool = False):

@@ -905,6 +905,44 @@ int wbc_sim_task_inverse_dynamics_qp(wbc_sim* sim, const int32_t* stance_bodies 
  * wbc_sim_inverse_dynamics. */
 int wbc_sim_centroidal(wbc_sim* sim, const float* nudot, float* com, float* mom, float* cmm, float* inertia, void* stream);
 
+/* The Coriolis matrix C(q, nu) of M nudot + C nu + g = tau, dM/dt, the generalised momentum p = M nu and C^T nu, in the coordinates of
+ * wbc_sim_body_dynamics / wbc_sim_inverse_dynamics (nu = (v_root, omega_root, qd), world axes, 26 columns; nudot the derivative of nu's
+ * world components) with the inertias of the per-env WBC_T_BODY_PARAMS, from the sim's current root / DoF state. The sim's state is
+ * read, never written. C is the factorisation of Echeandia and Wensing (Pinocchio's): with S_c the spatial motion vector of coordinate
+ * c, v_k the spatial velocity and I_k the spatial inertia of moving body k,
+ *     C = sum_k J_k^T (I_k Jdot_k + B_k J_k),    B_k = 1/2 [crf(v_k) I_k + crfbar(I_k v_k) - I_k crm(v_k)],
+ * which satisfies C nu = h - g (wbc_sim_inverse_dynamics) and C + C^T = dM/dt EXACTLY; the generalised momentum then obeys
+ *     d/dt p = tau + C^T nu - g + tau_ext.
+ * cmat  device f32 [N, 26, 26] = C. The whole of columns 0:3 (the root's linear coordinates, the block [0:3, 0:3] included), the locked
+ *       fingers' rows and columns 24, 25 and every pair of joints of which neither moves the other are exactly 0.
+ * mdot  device f32 [N, 26, 26] = dM/dt along nu: bit-symmetric, and bit-equal to cmat + cmat^T of the same launch.
+ * vec   device f32 [N, 2, 26]: p = M nu, then C^T nu; the fingers' entries exactly 0.
+ * Any output may be NULL and is then not written; not all three. cmat and mdot need 16-byte alignment, vec 4-byte alignment. One launch:
+ * wbc_coriolis_kernel where a matrix is asked for, wbc_momentum_kernel (which forms nothing 26 x 26) for vec alone; vec has the same bits
+ * from either. The fingers' qd is ignored. The root POSITION is never read: every output is bit-identical under a translation of the
+ * robot. Nothing is allocated and nothing synchronises: safe under stream capture. Error codes (-1 NULL sim, all outputs NULL or a
+ * misaligned pointer, nothing written; -3; -2) and stream handling as wbc_sim_inverse_dynamics. */
+int wbc_sim_coriolis(wbc_sim* sim, float* cmat, float* mdot, float* vec, void* stream);
+
+/* One update of the generalised-momentum observer, the estimator of external joint torques (contact detection without force sensors):
+ * along a motion d/dt p = tau + C^T nu - g + tau_ext, so with the caller-owned
+ * state  device f32 [N, 2, 26]: the integral, then the residual r (the estimate of tau_ext, a first-order low-pass of it with the
+ *        bandwidth `gain`),
+ * evaluated at the sim's current state, the call performs
+ *     with WBC_OBSERVER_RESET:  integral = p,                                        r = 0
+ *     otherwise:                integral += dt (tau + C^T nu - g + r_old),           r = gain (p - integral).
+ * tau    device f32 [N, 26] or NULL (= zeros), rows as wbc_sim_inverse_dynamics: 0:6 the KNOWN external wrench on the root (force, moment
+ *        about the root origin, world axes), 6: the joint torques. What is not in tau shows up in r.
+ * gain > 0 (1/s), dt > 0 (s), gain dt < 1: the explicit update must not overshoot. flags: 0 or WBC_OBSERVER_RESET.
+ * The fingers' entries of state are exactly 0 after every call. g comes with all three gravity components.
+ * Two launches on `stream`, no host synchronisation, nothing allocated: wbc_inverse_dynamics_kernel writes g(q) into the sim's [N, 26]
+ * bias-force scratch (the one wbc_sim_forward_dynamics uses: one stream at a time per sim among the calls that use it), then
+ * wbc_momentum_kernel forms p and C^T nu and updates state in its epilogue. The sim's state is read, never written.
+ * -1 with a message in wbc_last_error() that names this entry point, nothing written: NULL sim or state; unknown flag bits; gain or dt not
+ * finite or <= 0; gain dt >= 1; a tau or state that is not 4-byte aligned. -3 / -2 as wbc_sim_mass_solve. */
+#define WBC_OBSERVER_RESET 1
+int wbc_sim_momentum_observer(wbc_sim* sim, const float* tau, float gain, float dt, int flags, float* state, void* stream);
+
 /* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and
  * of nudot(q, nu, tau) in the coordinates of wbc_sim_body_dynamics, from the sim's current root / DoF state, WBC_T_BODY_PARAMS and all
  * three gravity components. The sim's state is read, never written.

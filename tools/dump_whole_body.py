@@ -128,6 +128,19 @@ def keep_ik(sim, name, feet, grip):
         keep(name + "ik." + tag, r, dof, info["residual"], info["cost"], info["status"].float(), info["iterations"].float())
 
 
+def keep_coriolis(sim, name, tau):
+    """wbc_sim_coriolis (all three outputs; vec alone: the vector kernel) and wbc_sim_momentum_observer: a reset, then two updates with
+    tau and one with a NULL tau at the same state."""
+    n = sim.num_envs
+    keep(name + "coriolis", *sim.coriolis())
+    keep(name + "coriolis.vec_only", *sim.coriolis(vec=torch.empty(n, 2, 26, device="cuda")))
+    state = torch.zeros(n, 2, 26, device="cuda")
+    keep(name + "observer.reset", sim.momentum_observer(tau, 30.0, 0.02, state=state, reset=True).clone())
+    sim.momentum_observer(tau, 30.0, 0.02, state=state)
+    keep(name + "observer.2", sim.momentum_observer(tau, 30.0, 0.02, state=state).clone())
+    keep(name + "observer.null", sim.momentum_observer(None, 30.0, 0.02, state=state).clone())
+
+
 for n in (1, 13, 64, 273):
     cfg = WidowGo1RoughCfg(); cfg.env.num_envs = n; cfg.terrain.mesh_type = "plane"
     env = WidowGo1(cfg, sim_device="cuda:0", seed=5)
@@ -215,6 +228,7 @@ for n in (1, 13, 64, 273):
     keep_cdd(sim, T, feet, grip, tau, g)           # last of the shared generator: its earlier draws stay what they were
     keep_impulse(sim, T, feet, grip)
     keep_ik(sim, T, feet, grip)
+    keep_coriolis(sim, T, tau)
 
 np.savez(sys.argv[1], **out)
 print(f"{len(out)} arrays, {sum(a.size for a in out.values())} words -> {sys.argv[1]}")
