@@ -2166,6 +2166,367 @@ extern "C" int wbc_sim_forward_dynamics_sensitivity(wbc_sim* s, const int32_t* b
   return 0;
 }
 
+// ---- recursive identification of inertial parameters (include/wbc_sim.h: wbc_sim_identification_accumulate / _solve) ---------------------
+// The consumer of the regressor: per env the normal equations A = sum Phi^T W Phi, b = sum Phi^T W z of the listed bodies' P = 10 nbodies
+// linear parameters, with exponential forgetting, one launch per control step. Phi is the regressor's columns of the listed bodies and
+// z = tau_gen - sum over the OTHER bodies of Y_b pi_b, both from the regressor's closed-form entries; Y never reaches HBM. One env per
+// 64-lane workgroup, four phases:
+//  1) lane b = moving body b: the regressor's phase 1 (ba_walk; E, p, the joint axis, w, alpha, d to LDS) and the body's current linear
+//     parameters pi_b = (m, m c, I_c + m (|c|^2 1 - c c^T)) to LDS; the other lanes clear Phi and fetch the env's A, 16 bytes per lane;
+//  2) work item = (row c, body b in the subtree c moves), ALL bodies: the ten closed-form values y. A listed body's go to Phi[c][s * 10 + k];
+//     another body's are folded with its pi_b into one float per item (nothing is formed as tau - Phi pi: nothing cancels);
+//  3) lane c = row c: z_c = tau_gen_c - (its items' floats, in item order), the row's weight (0 for the fingers' rows), z to `target`;
+//  4) lane t = entries t, t + 64, ... of A's lower triangle: forget * A_ij + sum_c (w_c Phi_ci) Phi_cj over the 26 rows in order, written
+//     to (i, j) and (j, i) of the LDS copy, which goes back 16 bytes per lane; lane i = entry i of b; lane 0 the two floats of stat.
+// Every sum has a fixed order and no atomics: the bits repeat from run to run. An env without a row of positive weight stores nothing but
+// its target (with WBC_IDENT_RESET: zeros). The root position is never read.
+#define IA_MAXP (WBC_IDENT_MAX_BODIES * RG_NP)  // 30 parameters at most: the m <= 32 Cholesky core of wbc_delassus.h
+#define IA_LP (IA_MAXP + 1)                     // LDS pitch of Phi's rows
+#define IA_OTHER 0xff                           // item_s of a body that is not listed
+static_assert(RG_MAXITEM < 256 && IA_MAXP <= 32 && (RG_NP * RG_NP) % 4 == 0, "items index in a byte, P fits the core, A is whole float4s");
+struct IaConst : IdConst {
+  int32_t nitem, np;                            // np = 10 * listed bodies
+  uint32_t live;                                // bit c: row c is not a locked finger's
+  uint8_t row_item[BD_NCOL + 1];                // the items of row c: row_item[c] .. row_item[c + 1]
+  uint8_t item_c[RG_MAXITEM], item_b[RG_MAXITEM], item_s[RG_MAXITEM];   // row, moving body, its place in the caller's list or IA_OTHER
+};
+
+// The ten values of regressor entry (row c, body b) in the linear parameters: wbc_inverse_dynamics_regressor_kernel's phase 2, its
+// statements as they stand there. Written out a second time, not shared: that kernel's bits depend on how its own statements contract
+// into FMAs (wbc_tree.h), and it is left untouched.
+__device__ __forceinline__ void ia_entry(const IaConst& C, const float* R, const float (*sB)[RG_BT], int c, int b, float* y) {
+  const float* B = sB[b];
+  f3 u, lever = ld3(B + 9);
+  if (c < 6) {
+    const int j = c < 3 ? c : c - 3;
+    u = matT_mul(R, mk3(j == 0 ? 1.f : 0.f, j == 1 ? 1.f : 0.f, j == 2 ? 1.f : 0.f));
+  } else {
+    const float* J = sB[C.col_body[c - 6]];
+    u = ld3(J + 12);
+    lever = lever - ld3(J + 9);
+  }
+  const f3 uh = matT_mul(B, u), w = ld3(B + 15), al = ld3(B + 18), d = ld3(B + 21);
+  const bool lin = c < 3;
+  const f3 wh = lin ? uh : cross(uh, matT_mul(B, lever));
+  y[0] = dot(wh, d);
+  f3 yh = cross(wh, al) + cross(cross(wh, w), w);
+  if (lin) {
+#pragma unroll
+    for (int k = 4; k < RG_NP; ++k) y[k] = 0.f;
+  } else {
+    yh = yh + cross(d, uh);
+    const f3 t = cross(uh, w);
+    y[4] = uh.x * al.x + t.x * w.x; y[5] = uh.y * al.y + t.y * w.y; y[6] = uh.z * al.z + t.z * w.z;
+    y[7] = (uh.x * al.y + uh.y * al.x) + (t.x * w.y + t.y * w.x);
+    y[8] = (uh.x * al.z + uh.z * al.x) + (t.x * w.z + t.z * w.x);
+    y[9] = (uh.y * al.z + uh.z * al.y) + (t.y * w.z + t.z * w.y);
+  }
+  y[1] = yh.x; y[2] = yh.y; y[3] = yh.z;
+}
+
+extern "C" __global__ void __launch_bounds__(64) wbc_identification_accumulate_kernel(
+    IaConst C, const float* __restrict__ root, const float* __restrict__ dofs, const float* __restrict__ body_params,
+    const float* __restrict__ nudot, const float* __restrict__ tau_gen, const float* __restrict__ row_weight, float forget, int reset,
+    float* __restrict__ info_mat, float* __restrict__ info_vec, float* __restrict__ stat, float* __restrict__ target) {
+  __shared__ __align__(16) float sA[IA_MAXP * IA_MAXP];   // the env's A, [P][P] as in HBM
+  __shared__ float sPhi[BD_NCOL][IA_LP];
+  __shared__ float sB[WBC_NB][RG_BT];
+  __shared__ float sPi[WBC_NB][RG_NP];
+  __shared__ float sT[RG_MAXITEM];                        // an unlisted body's y . pi_b, per item
+  __shared__ float sZ[BD_NCOL], sW[BD_NCOL];
+  const int lane = threadIdx.x, P = C.np;
+  const size_t e = blockIdx.x;
+  float R[9];
+  quat_to_mat(root + e * 26 + 3, R);
+
+  if (lane < WBC_NB) {
+    const int b = lane;
+    float E[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    f3 p, w, aw, ao;
+    ba_walk(C, b, e, R, root, dofs, nudot, E, p, w, aw, ao);
+    const f3 gF = matT_mul(R, mk3(C.gravity[0], C.gravity[1], C.gravity[2]));
+    float m = C.mass[b], com[3] = {C.com[b][0], C.com[b][1], C.com[b][2]}, I6[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) I6[j] = C.inertia[b][j];
+    const int slot = b == 0 ? TREE_BP_ROOT : (b == C.gripper_body ? TREE_BP_GRIPPER : -1);
+    if (slot >= 0) {
+      const float* bp = body_params + e * TREE_BP_STRIDE + slot;
+      m = bp[0];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) com[j] = bp[1 + j];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) I6[j] = bp[4 + j];
+    }
+    float* o = sB[b];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) o[j] = E[j];
+    st3(o + 9, p); st3(o + 12, mat_mul(E, tree_axis(C.axis[b])));   // -1 for the root: no joint axis
+    st3(o + 15, matT_mul(E, w)); st3(o + 18, matT_mul(E, aw)); st3(o + 21, matT_mul(E, ao - gF));
+    o[24] = m; o[25] = com[0]; o[26] = com[1]; o[27] = com[2];
+    const float cx = com[0], cy = com[1], cz = com[2];
+    float* q = sPi[b];
+    q[0] = m; q[1] = m * cx; q[2] = m * cy; q[3] = m * cz;
+    q[4] = I6[0] + m * (cy * cy + cz * cz); q[5] = I6[1] + m * (cx * cx + cz * cz); q[6] = I6[2] + m * (cx * cx + cy * cy);
+    q[7] = I6[3] - m * (cx * cy); q[8] = I6[4] - m * (cx * cz); q[9] = I6[5] - m * (cy * cz);
+  }
+  for (int t = lane; t < BD_NCOL * IA_LP; t += 64) (&sPhi[0][0])[t] = 0.f;
+  if (!reset) {
+    const float4* in4 = reinterpret_cast<const float4*>(info_mat + e * (size_t)(P * P));
+    for (int t = lane; t < (P * P) >> 2; t += 64) reinterpret_cast<float4*>(sA)[t] = in4[t];
+  }
+  __syncthreads();
+
+  for (int it = lane; it < C.nitem; it += 64) {
+    const int c = C.item_c[it], b = C.item_b[it], s = C.item_s[it];
+    float y[RG_NP];
+    ia_entry(C, R, sB, c, b, y);
+    if (s != IA_OTHER) {
+#pragma unroll
+      for (int k = 0; k < RG_NP; ++k) sPhi[c][s * RG_NP + k] = y[k];
+    } else {
+      const float* q = sPi[b];
+      sT[it] = (y[0] * q[0] + (y[1] * q[1] + y[2] * q[2] + y[3] * q[3])) +
+               ((y[4] * q[4] + y[5] * q[5] + y[6] * q[6]) + (y[7] * q[7] + y[8] * q[8] + y[9] * q[9]));
+    }
+  }
+  __syncthreads();
+
+  if (lane < BD_NCOL) {
+    const int c = lane;
+    float others = 0.f;
+    for (int it = C.row_item[c]; it < C.row_item[c + 1]; ++it)
+      if (C.item_s[it] == IA_OTHER) others += sT[it];
+    const float z = tau_gen[e * BD_NCOL + c] - others;
+    if (target) target[e * BD_NCOL + c] = z;
+    sZ[c] = z;
+    sW[c] = ((C.live >> c) & 1u) ? (row_weight ? row_weight[e * BD_NCOL + c] : 1.f) : 0.f;
+  }
+  __syncthreads();
+
+  float wzz = 0.f;                                          // every lane the same sums in the same order: no hand-over
+  int rows = 0;
+#pragma unroll
+  for (int c = 0; c < BD_NCOL; ++c) {
+    const float w = sW[c], z = sZ[c];
+    wzz += (w * z) * z;
+    rows += w > 0.f ? 1 : 0;
+  }
+  if (rows == 0 && !reset) return;                          // nothing observed: A, b and stat keep their bits, without decay
+
+  for (int t = lane; t < P * (P + 1) / 2; t += 64) {
+    int i, j;
+    delassus_tri(t, i, j);
+    float a = 0.f;
+#pragma unroll
+    for (int c = 0; c < BD_NCOL; ++c) a += (sW[c] * sPhi[c][i]) * sPhi[c][j];
+    const float v = reset ? a : forget * sA[i * P + j] + a;
+    sA[i * P + j] = v; sA[j * P + i] = v;                   // only the lower triangle is ever read: the result is bit-symmetric
+  }
+  if (lane < P) {
+    float a = 0.f;
+#pragma unroll
+    for (int c = 0; c < BD_NCOL; ++c) a += (sW[c] * sPhi[c][lane]) * sZ[c];
+    float* o = info_vec + e * (size_t)P + lane;
+    *o = reset ? a : forget * *o + a;
+  }
+  if (lane == 0) {
+    float* o = stat + e * 2;
+    o[0] = reset ? wzz : forget * o[0] + wzz;
+    o[1] = reset ? (float)rows : forget * o[1] + (float)rows;
+  }
+  __syncthreads();
+  float4* out4 = reinterpret_cast<float4*>(info_mat + e * (size_t)(P * P));
+  for (int t = lane; t < (P * P) >> 2; t += 64) out4[t] = reinterpret_cast<const float4*>(sA)[t];
+}
+
+// Fills C from the model and the list: every (row, body) entry that is not a structural zero, row by row, bodies in order.
+static int ia_const_fill(const DevConst* hc, const int32_t* sel, int nsel, IaConst& C) {
+  if (id_const_fill(hc, C) != 0) return 1;
+  int slot[WBC_NB];
+  for (int b = 0; b < WBC_NB; ++b) slot[b] = IA_OTHER;
+  for (int s = 0; s < nsel; ++s) slot[sel[s]] = s;
+  C.np = nsel * RG_NP; C.nitem = 0; C.live = 0;
+  for (int c = 0; c < BD_NCOL; ++c) {
+    C.row_item[c] = (uint8_t)C.nitem;
+    const int cb = c < 6 ? 0 : C.col_body[c - 6];
+    if (cb < 0) continue;                                    // a locked finger: the row never counts
+    C.live |= 1u << c;
+    for (int b = 0; b < WBC_NB; ++b) {
+      if (!((C.anc[b] >> cb) & 1u)) continue;
+      if (C.nitem >= RG_MAXITEM) return 1;
+      C.item_c[C.nitem] = (uint8_t)c; C.item_b[C.nitem] = (uint8_t)b; C.item_s[C.nitem] = (uint8_t)slot[b];
+      ++C.nitem;
+    }
+  }
+  C.row_item[BD_NCOL] = (uint8_t)C.nitem;
+  for (int i = C.nitem; i < RG_MAXITEM; ++i) { C.item_c[i] = 0; C.item_b[i] = 0; C.item_s[i] = IA_OTHER; }
+  return 0;
+}
+
+// True if the byte ranges [a, a + na) and [b, b + nb) of two buffers that are both there share a byte.
+static bool ia_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+// True if an output (the first `nout` of the list) shares a byte with any other buffer of the list.
+static bool ia_any_overlap(const void* const* ptr, const size_t* bytes, int count, int nout) {
+  for (int i = 0; i < nout; ++i)
+    for (int j = 0; j < count; ++j)
+      if (j != i && (j > i || j >= nout) && ia_overlap(ptr[i], bytes[i], ptr[j], bytes[j])) return true;
+  return false;
+}
+
+// bodies (host, 1..3 distinct), nudot / row_weight / target (device f32 [N,26] or NULL), tau_gen (device f32 [N,26]), info_mat [N,P,P],
+// info_vec [N,P], stat [N,2] (device f32, read and written), all 16-byte aligned: include/wbc_sim.h.
+extern "C" int wbc_sim_identification_accumulate(wbc_sim* s, const int32_t* bodies, int nbodies, const float* nudot, const float* tau_gen,
+                                                 const float* row_weight, float forget, float* info_mat, float* info_vec, float* stat,
+                                                 float* target, int flags, void* stream) {
+  WbCall c("wbc_sim_identification_accumulate", s, stream);
+  if (!s) return c.no_sim();
+  if (!tau_gen || !info_mat || !info_vec || !stat) return c.fail(-1, "tau_gen / info_mat / info_vec / stat is NULL");
+  int32_t sel[WBC_NB];
+  int nsel = 0;
+  if (!bodies || nbodies > WBC_IDENT_MAX_BODIES || !rg_bodies(bodies, nbodies, sel, nsel))
+    return c.fail(-1, "bodies must be 1..WBC_IDENT_MAX_BODIES distinct moving-body indices");
+  if (!(forget > 0.f && forget <= 1.f)) return c.fail(-1, "forget must be in (0, 1]");
+  if (flags & ~WBC_IDENT_RESET) return c.fail(-1, "unknown flag bits");
+  if (((uintptr_t)nudot | (uintptr_t)tau_gen | (uintptr_t)row_weight | (uintptr_t)info_mat | (uintptr_t)info_vec | (uintptr_t)stat |
+       (uintptr_t)target) & 15u)
+    return c.fail(-1, "every buffer must be 16-byte aligned");
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
+  const size_t np = (size_t)nsel * RG_NP, row = (size_t)c.n * BD_NCOL * sizeof(float);
+  const void* ptr[7] = {info_mat, info_vec, stat, target, nudot, tau_gen, row_weight};
+  const size_t bytes[7] = {(size_t)c.n * np * np * sizeof(float), (size_t)c.n * np * sizeof(float), (size_t)c.n * 2 * sizeof(float), row, row, row, row};
+  if (ia_any_overlap(ptr, bytes, 7, 4)) return c.fail(-1, "info_mat / info_vec / stat / target overlap another buffer");
+  IaConst C;
+  if (ia_const_fill(c.hc, sel, nsel, C) != 0) return c.no_tree();
+  hipLaunchKernelGGL(wbc_identification_accumulate_kernel, dim3(c.n), dim3(64), 0, (hipStream_t)stream, C, c.root, c.dofs, c.bp, nudot, tau_gen,
+                     row_weight, forget, (flags & WBC_IDENT_RESET) ? 1 : 0, info_mat, info_vec, stat, target);
+  return c.launched();
+}
+
+// (A + Lambda) pi = b + Lambda pi_0 per env, one env per 64-lane workgroup, lane i = parameter i. The matrix is equilibrated to a unit
+// diagonal, D = diag(A + Lambda)^-1/2, factorised by delassus_cholesky and solved by delassus_lane_solve (wbc_delassus.h, as they stand);
+// the strict upper triangle of the LDS block keeps A as it came, for the residual sum. An env with a diagonal entry that is not positive
+// and finite, or with a squared pivot of the equilibrated factor <= pivot_tol, falls back to the prior.
+#define IS_LA 33                                // LDS pitch of the 32 x 32 blocks
+extern "C" __global__ void __launch_bounds__(64) wbc_identification_solve_kernel(
+    int P, const float* __restrict__ info_mat, const float* __restrict__ info_vec, const float* __restrict__ stat,
+    const float* __restrict__ prior, const float* __restrict__ prior_weight, float pivot_tol, float* __restrict__ pi_hat,
+    float* __restrict__ theta_hat, float* __restrict__ cov_diag, float* __restrict__ sse, int32_t* __restrict__ status) {
+  __shared__ float sL[32][IS_LA];                          // lower triangle: the equilibrated matrix, then its factor; above the diagonal: A
+  __shared__ float sX[32][IS_LA];                          // the identity, then the columns of the equilibrated inverse (cov_diag only)
+  __shared__ float sD[32], sV[32], sDiag[32], sPi[32], sQ[32], sLin[32];
+  const int lane = threadIdx.x;
+  const size_t e = blockIdx.x;
+  const bool row = lane < P;
+  for (int t = lane; t < P * P; t += 64) sL[t / P][t % P] = info_mat[e * (size_t)(P * P) + t];
+  __syncthreads();
+  float lam = 0.f, p0 = 0.f, bi = 0.f, dm = 1.f;
+  if (row) {
+    lam = prior_weight ? prior_weight[e * P + lane] : 0.f;
+    p0 = prior ? prior[e * P + lane] : 0.f;
+    bi = info_vec[e * P + lane];
+    sDiag[lane] = sL[lane][lane];
+    dm = sL[lane][lane] + lam;
+  }
+  const bool okd = dm > 0.f && dm < INFINITY;
+  const float sc = okd ? 1.f / __fsqrt_rn(dm) : 0.f;
+  if (lane < 32) sV[lane] = sc;
+  __syncthreads();
+  if (row) {
+    for (int j = 0; j < lane; ++j) sL[lane][j] = (sc * sL[lane][j]) * sV[j];
+    sL[lane][lane] = (sc * dm) * sc;
+  }
+  delassus_cholesky<IS_LA>(sL, sD, P, lane);
+  __syncthreads();
+  const float idv = row ? sD[lane] : 0.f;
+  const bool bad = __any((row && !okd) || !(idv * idv * pivot_tol < 1.f)) != 0;
+  delassus_lane_solve<IS_LA>(sL, sD, sV, P, lane, row ? sc * (bi + lam * p0) : 0.f);
+  const float pi = row ? (bad ? p0 : sc * sV[lane]) : 0.f;
+  if (row) {
+    sPi[lane] = pi;
+    pi_hat[e * P + lane] = pi;
+  }
+  if (cov_diag) {                                          // diag((A + Lambda)^-1) = D diag((D (A + Lambda) D)^-1) D
+    for (int t = lane; t < P * P; t += 64) sX[t / P][t % P] = t / P == t % P ? 1.f : 0.f;
+    __syncthreads();
+    if (row) {
+      delassus_column_solve<IS_LA>(sL, sD, &sX[0][lane], IS_LA, P);
+      cov_diag[e * P + lane] = bad ? INFINITY : (sc * sX[lane][lane]) * sc;
+    }
+  }
+  __syncthreads();
+  if (sse) {                                               // stat_0 - 2 pi^T b + pi^T A pi with A as it came
+    if (row) {
+      float r = 0.f;
+      for (int j = 0; j < P; ++j) r += (j == lane ? sDiag[j] : (lane < j ? sL[lane][j] : sL[j][lane])) * sPi[j];
+      sQ[lane] = pi * r;
+      sLin[lane] = pi * bi;
+    }
+    __syncthreads();
+    if (lane == 0) {
+      float q = 0.f, l = 0.f;
+      for (int j = 0; j < P; ++j) { q += sQ[j]; l += sLin[j]; }
+      sse[e] = fmaxf((stat[e * 2] - 2.f * l) + q, 0.f);
+    }
+  }
+  if (lane < P / RG_NP && (theta_hat || status)) {         // lane s = listed body s: (m, c, I_c) and the flags
+    const float* q = sPi + lane * RG_NP;
+    const float m = q[0], cx = q[1] / m, cy = q[2] / m, cz = q[3] / m;
+    float th[RG_NP] = {m, cx, cy, cz, q[4] - m * (cy * cy + cz * cz), q[5] - m * (cx * cx + cz * cz), q[6] - m * (cx * cx + cy * cy),
+                       q[7] + m * (cx * cy), q[8] + m * (cx * cz), q[9] + m * (cy * cz)};
+    int st = 1;
+    if (bad && !prior) {
+#pragma unroll
+      for (int k = 0; k < RG_NP; ++k) th[k] = 0.f;
+    }
+    if (!bad) {
+      const float xx = th[4], yy = th[5], zz = th[6], xy = th[7], xz = th[8], yz = th[9];
+      const float det = xx * (yy * zz - yz * yz) - xy * (xy * zz - yz * xz) + xz * (xy * yz - yy * xz);
+      const bool pd = xx > 0.f && xx * yy - xy * xy > 0.f && det > 0.f;
+      // lambda_1 + lambda_2 >= lambda_3  <=>  T = (trace / 2) 1 - I_c is positive semi-definite: all seven principal minors >= 0
+      const float h = 0.5f * (xx + yy + zz), a = h - xx, b = h - yy, c = h - zz;
+      const float dT = a * (b * c - yz * yz) - xy * (xy * c + yz * xz) - xz * (xy * yz + b * xz);   // T's off-diagonal entries are -xy, -xz, -yz
+      const bool tri = a >= 0.f && b >= 0.f && c >= 0.f && a * b - xy * xy >= 0.f && a * c - xz * xz >= 0.f && b * c - yz * yz >= 0.f && dT >= 0.f;
+      st = (m > 0.f ? 0 : 2) | (pd ? 0 : 4) | (tri ? 0 : 8);
+    }
+    if (theta_hat) {
+#pragma unroll
+      for (int k = 0; k < RG_NP; ++k) theta_hat[(e * (P / RG_NP) + lane) * RG_NP + k] = th[k];
+    }
+    if (status) status[e * (P / RG_NP) + lane] = st;
+  }
+}
+
+// info_mat [N,P,P], info_vec [N,P], stat [N,2] (device f32, read), prior / prior_weight (device f32 [N,nbodies,10] or NULL), pi_hat and
+// the optional theta_hat / cov_diag [N,nbodies,10], sse [N], status int32 [N,nbodies]: include/wbc_sim.h.
+extern "C" int wbc_sim_identification_solve(wbc_sim* s, int nbodies, const float* info_mat, const float* info_vec, const float* stat,
+                                            const float* prior, const float* prior_weight, float pivot_tol, float* pi_hat, float* theta_hat,
+                                            float* cov_diag, float* sse, int32_t* status, void* stream) {
+  WbCall c("wbc_sim_identification_solve", s, stream);
+  if (!s) return c.no_sim();
+  if (!info_mat || !info_vec || !pi_hat) return c.fail(-1, "info_mat / info_vec / pi_hat is NULL");
+  if (sse && !stat) return c.fail(-1, "stat is NULL with sse given");
+  if (prior_weight && !prior) return c.fail(-1, "prior is NULL with prior_weight given");
+  if (nbodies < 1 || nbodies > WBC_IDENT_MAX_BODIES) return c.fail(-1, "nbodies must be 1..WBC_IDENT_MAX_BODIES");
+  if (!(pivot_tol > 0.f && pivot_tol < INFINITY)) return c.fail(-1, "pivot_tol must be positive and finite");
+  if (((uintptr_t)info_mat | (uintptr_t)info_vec | (uintptr_t)stat | (uintptr_t)prior | (uintptr_t)prior_weight | (uintptr_t)pi_hat |
+       (uintptr_t)theta_hat | (uintptr_t)cov_diag | (uintptr_t)sse | (uintptr_t)status) & 15u)
+    return c.fail(-1, "every buffer must be 16-byte aligned");
+  if (!c.have) return c.no_state();
+  if (c.n <= 0) return 0;
+  const size_t np = (size_t)nbodies * RG_NP, vec = (size_t)c.n * np * sizeof(float);
+  const void* ptr[10] = {pi_hat, theta_hat, cov_diag, sse, status, info_mat, info_vec, stat, prior, prior_weight};
+  const size_t bytes[10] = {vec, vec, vec, (size_t)c.n * sizeof(float), (size_t)c.n * nbodies * sizeof(int32_t), vec * np, vec,
+                            (size_t)c.n * 2 * sizeof(float), vec, vec};
+  if (ia_any_overlap(ptr, bytes, 10, 5)) return c.fail(-1, "an output overlaps another buffer");
+  hipLaunchKernelGGL(wbc_identification_solve_kernel, dim3(c.n), dim3(64), 0, (hipStream_t)stream, (int)np, info_mat, info_vec, stat, prior,
+                     prior_weight, pivot_tol, pi_hat, theta_hat, cov_diag, sse, status);
+  return c.launched();
+}
+
 // ---- analytic derivatives of stance-constrained forward dynamics (include/wbc_sim.h: wbc_sim_constrained_dynamics_derivatives) ----------
 // The solution (nudot, lambda) of wbc_sim_constrained_dynamics satisfies r1 = ID(q, nu, nudot) [+ armature nudot] - Jc^T lambda - tau = 0
 // and r2 = Jc nudot + (Jdot nu)_c - a_des + damping lambda = 0. With x a direction of q or of nu, X = -M^-1 dr1/dx, Y = M^-1 Jc^T:

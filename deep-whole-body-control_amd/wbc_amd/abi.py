@@ -109,6 +109,8 @@ TASKQP_MAX_ITER = 128     # WBC_TASKQP_MAX_ITER
 SOLVE_ARMATURE, DERIV_TRANSPOSED, REGRESSOR_NATIVE = 1, 2, 4   # WBC_SOLVE_ARMATURE, WBC_DERIV_TRANSPOSED, WBC_REGRESSOR_NATIVE: one `flags` word
 WBC_REGRESSOR_NATIVE = REGRESSOR_NATIVE
 OBSERVER_RESET = 1         # WBC_OBSERVER_RESET (wbc_sim_momentum_observer's own flags word)
+IDENT_RESET = 8            # WBC_IDENT_RESET (wbc_sim_identification_accumulate; distinct from the three above)
+IDENT_MAX_BODIES = 3       # WBC_IDENT_MAX_BODIES: 10 parameters each, P <= 30
 NPARAM = 10               # inertial parameters per moving body (include/wbc_sim.h: wbc_sim_inverse_dynamics_regressor)
 
 

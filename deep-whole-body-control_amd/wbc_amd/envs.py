@@ -756,6 +756,25 @@ class WidowGo1(LeggedRobot):
         bodies = (0, int(self.robot_model.gripper_piece["body"]))
         return self.sim.inverse_dynamics_regressor(bodies, nudot=nudot, native=True).view(self.num_envs, 6 + abi.NDOF, 20)
 
+    # ---- recursive identification (no counterpart in the reference): include/wbc_sim.h: wbc_sim_identification_accumulate ----
+    def generalised_force(self, tau: torch.Tensor, foot_forces: torch.Tensor = None, feet=None) -> torch.Tensor:
+        """A fresh f32 [N, 26] tau + sum_f J_f^T f_f: the net generalised force of applied forces tau [N, 26] (rows as inverse_dynamics)
+        and the world-frame forces foot_forces [N, K, 3] acting on the origins of the rigid bodies `feet` (None: feet_indices), through
+        the translational rows of jacobian_whole, which is refreshed. With (nudot, foot_forces) of stance_forward_dynamics(tau) this is
+        inverse_dynamics(nudot); with logged torques and force-sensor readings, the tau_gen a parameter_identifier takes."""
+        out = tau.to(torch.float32).clone()
+        if foot_forces is not None:
+            feet = self.feet_indices if feet is None else torch.as_tensor(feet, dtype=torch.long, device=self.device)
+            self.sim.refresh_jacobian_tensors()
+            J = self.jacobian_whole[:, feet, 0:3, :]                                      # [N, K, 3, 26]
+            out += torch.einsum("nkic,nki->nc", J, foot_forces.to(torch.float32))
+        return out
+
+    def parameter_identifier(self, bodies=None, forget: float = 1.0) -> "ParameterIdentifier":
+        """A recursive least-squares estimator of the linear inertial parameters of `bodies` (1..3 moving-body indices; None: the root
+        composite and the gripper body, the two that BODY_PARAMS randomises): see ParameterIdentifier."""
+        return ParameterIdentifier(self, bodies, forget)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])
@@ -953,3 +972,58 @@ class WidowGo1(LeggedRobot):
     # gym-tensor-API style helpers some callers of the reference use
     def get_foot_contacts(self):                                                    # WG:1090-1098
         return self.force_sensor_tensor.norm(dim=-1) > 1.5
+
+
+class ParameterIdentifier:
+    """Recursive least squares for the linear inertial parameters (m, m c, inertia about the body origin) of up to three moving bodies
+    of every env, the classical baseline to the learned adaptation module: it owns the per-env normal equations A [N, P, P], b [N, P]
+    and stat [N, 2] and feeds them one wbc_sim_identification_accumulate launch per update; estimate() is one
+    wbc_sim_identification_solve launch. The other bodies' parameters are taken as the sim holds them."""
+
+    def __init__(self, env, bodies=None, forget: float = 1.0):
+        m = env.robot_model
+        self.env, self.forget = env, float(forget)
+        self.bodies = [int(b) for b in ((0, m.gripper_piece["body"]) if bodies is None else bodies)]
+        n, p = env.num_envs, abi.NPARAM * len(self.bodies)
+        self.info_mat = torch.zeros((n, p, p), dtype=torch.float32, device=env.device)
+        self.info_vec = torch.zeros((n, p), dtype=torch.float32, device=env.device)
+        self.stat = torch.zeros((n, 2), dtype=torch.float32, device=env.device)
+        nominal = abi.body_params_from_randomisation(m, np.zeros(1), np.zeros((1, 3)), np.zeros(1))
+        pi0 = abi.linear_body_params(m, nominal)[0, self.bodies]                          # the nominal model, no randomisation
+        self.prior = torch.tensor(pi0, dtype=torch.float32, device=env.device).expand(n, -1, -1).contiguous()
+        self.last_target = None
+
+    def update(self, tau_gen: torch.Tensor, nudot: torch.Tensor = None, row_weight: torch.Tensor = None) -> None:
+        """One observation per env at the sim's current state: tau_gen [N, 26] (env.generalised_force), the acceleration nudot [N, 26]
+        (None: zeros) and the rows' weights [N, 26] (None: 1; an env whose weights are all 0 is left as it is, without decay)."""
+        self.last_target = self.env.sim.identification_accumulate(self.bodies, tau_gen, nudot=nudot, row_weight=row_weight,
+                                                                  forget=self.forget, info_mat=self.info_mat, info_vec=self.info_vec,
+                                                                  stat=self.stat, target=self.last_target)[3]
+
+    def reset(self, env_ids=None) -> None:
+        """Forget everything (env_ids None), or everything the listed envs have seen."""
+        for t in (self.info_mat, self.info_vec, self.stat):
+            if env_ids is None:
+                t.zero_()
+            else:
+                t[env_ids] = 0.0
+
+    def solve(self, prior_weight=None, pivot_tol: float = 1e-5, want=WbcSim.IDENT_OUTPUTS) -> dict:
+        """WbcSim.identification_solve on the owned buffers with the nominal model as the prior; prior_weight: None (no prior term),
+        a float, or f32 [N, len(bodies), 10]."""
+        if prior_weight is not None and not isinstance(prior_weight, torch.Tensor):
+            prior_weight = torch.full_like(self.prior, float(prior_weight))
+        return self.env.sim.identification_solve(self.info_mat, self.info_vec, self.stat, prior=self.prior, prior_weight=prior_weight,
+                                                 pivot_tol=pivot_tol, want=want)
+
+    def estimate(self, prior_weight=None):
+        """(body_params_hat f32 [N, 10 len(bodies)], status int32 [N, len(bodies)]): every listed body's (m, c, I_c) -- column for column
+        BODY_PARAMS when the bodies are the root and the gripper body -- and the flags of wbc_sim_identification_solve. An env that
+        cannot be solved yet (status bit 0) returns the nominal model's parameters."""
+        r = self.solve(prior_weight, want=("theta_hat", "status"))
+        return r["theta_hat"].view(self.env.num_envs, -1), r["status"]
+
+    def payload(self, prior_weight=None) -> torch.Tensor:
+        """f32 [N]: the estimated mass of the gripper body less its nominal mass (the gripper body must be listed)."""
+        s = self.bodies.index(int(self.env.robot_model.gripper_piece["body"]))
+        return self.estimate(prior_weight)[0][:, abi.NPARAM * s] - self.prior[:, s, 0]

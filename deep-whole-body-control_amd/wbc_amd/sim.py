@@ -643,6 +643,79 @@ class WbcSim:
         """Drop the buffer forward_dynamics_sensitivity keeps between calls (the next call without a workspace allocates again)."""
         self.__dict__.pop("_fds_ws", None)
 
+    # ---- recursive identification of inertial parameters (include/wbc_sim.h: wbc_sim_identification_accumulate) ---------------------------
+    def identification_accumulate(self, bodies, tau_gen: torch.Tensor, nudot: Optional[torch.Tensor] = None,
+                                  row_weight: Optional[torch.Tensor] = None, forget: float = 1.0, info_mat: Optional[torch.Tensor] = None,
+                                  info_vec: Optional[torch.Tensor] = None, stat: Optional[torch.Tensor] = None, target=None,
+                                  reset: bool = False):
+        """One wbc_sim_identification_accumulate launch on the current stream: A <- forget A + Phi^T W Phi, b <- forget b + Phi^T W z,
+        stat <- forget stat + (sum w z^2, rows with w > 0) for the linear parameters of `bodies` (1..3 distinct moving-body indices) at
+        the current state. tau_gen f32 [N, 26]: the net generalised force; nudot, row_weight f32 [N, 26] or None (zeros; 1 on the live
+        rows). info_mat f32 [N, P, P], info_vec [N, P], stat [N, 2], P = 10 len(bodies): updated in place; the three are passed together,
+        or all left out: then they are allocated and the call resets. reset: the incoming three are taken as zero. target f32 [N, 26]:
+        z (None: allocated; False: not written). Returns (info_mat, info_vec, stat, target)."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        idx, k, nb = self._regressor_bodies(bodies)
+        assert idx is not None and 1 <= k <= abi.IDENT_MAX_BODIES, bodies
+        p = nb * abi.NPARAM
+        state = (info_mat, info_vec, stat)
+        assert all(t is None for t in state) or all(t is not None for t in state), "info_mat, info_vec and stat go together"
+        if info_mat is None:
+            info_mat = torch.empty((n, p, p), dtype=torch.float32, device=self.device)
+            info_vec = torch.empty((n, p), dtype=torch.float32, device=self.device)
+            stat = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+            reset = True
+        if target is None:
+            target = torch.empty((n, ncol), dtype=torch.float32, device=self.device)
+        elif target is False:
+            target = None
+        for t, sh in ((tau_gen, (n, ncol)), (nudot, (n, ncol)), (row_weight, (n, ncol)), (info_mat, (n, p, p)), (info_vec, (n, p)),
+                      (stat, (n, 2)), (target, (n, ncol))):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        check(self.L.wbc_sim_identification_accumulate(self.h, idx, k, ptr(nudot), tau_gen.data_ptr(), ptr(row_weight), float(forget),
+                                                       info_mat.data_ptr(), info_vec.data_ptr(), stat.data_ptr(), ptr(target),
+                                                       abi.IDENT_RESET if reset else 0, self._stream()), "wbc_sim_identification_accumulate")
+        return info_mat, info_vec, stat, target
+
+    IDENT_OUTPUTS = ("pi_hat", "theta_hat", "cov_diag", "sse", "status")
+
+    def identification_solve(self, info_mat: torch.Tensor, info_vec: torch.Tensor, stat: Optional[torch.Tensor] = None,
+                             prior: Optional[torch.Tensor] = None, prior_weight: Optional[torch.Tensor] = None, pivot_tol: float = 1e-5,
+                             want=IDENT_OUTPUTS, out=None):
+        """One wbc_sim_identification_solve launch on the current stream: (A + diag(prior_weight)) pi_hat = b + prior_weight * prior per
+        env, equilibrated, by fp32 Cholesky. info_mat [N, P, P], info_vec [N, P], stat [N, 2] as identification_accumulate leaves them;
+        prior, prior_weight f32 [N, P / 10, 10] or None. Returns a dict with the names in `want` (a subset of IDENT_OUTPUTS, pi_hat
+        always): pi_hat, theta_hat (m, c, I_c), cov_diag f32 [N, P / 10, 10], sse f32 [N] (needs stat), status int32 [N, P / 10] (bit 0:
+        not solvable, the prior is returned; 1: m <= 0; 2: I_c not positive definite; 3: triangle inequality). out: an optional dict
+        of caller-owned tensors under the same names."""
+        n = self.num_envs
+        assert info_mat.dim() == 3 and info_mat.shape[1] % abi.NPARAM == 0, tuple(info_mat.shape)
+        p = int(info_mat.shape[1])
+        nb = p // abi.NPARAM
+        assert 1 <= nb <= abi.IDENT_MAX_BODIES, nb
+        want = tuple(dict.fromkeys(("pi_hat",) + tuple(want)))
+        assert all(w in self.IDENT_OUTPUTS for w in want), want
+        assert "sse" not in want or stat is not None, "sse needs stat"
+        out = dict(out) if out is not None else {}
+        assert all(key in want for key in out), tuple(out)
+        shapes = {"pi_hat": (n, nb, abi.NPARAM), "theta_hat": (n, nb, abi.NPARAM), "cov_diag": (n, nb, abi.NPARAM), "sse": (n,), "status": (n, nb)}
+        res = {w: out[w] if out.get(w) is not None else
+               torch.empty(shapes[w], dtype=torch.int32 if w == "status" else torch.float32, device=self.device) for w in want}
+        for t, sh in [(info_mat, (n, p, p)), (info_vec, (n, p)), (stat, (n, 2)), (prior, shapes["pi_hat"]), (prior_weight, shapes["pi_hat"])] + \
+                     [(res[w], shapes[w]) for w in want if w != "status"]:
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        if "status" in res:
+            t = res["status"]
+            assert t.device == self.arena.device and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shapes["status"]
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        check(self.L.wbc_sim_identification_solve(self.h, nb, info_mat.data_ptr(), info_vec.data_ptr(), ptr(stat), ptr(prior), ptr(prior_weight),
+                                                  float(pivot_tol), *[ptr(res.get(w)) for w in self.IDENT_OUTPUTS], self._stream()),
+              "wbc_sim_identification_solve")
+        return res
+
     CDD_OUTPUTS = ("dnudot_dq", "dnudot_dnu", "dnudot_dtau", "dlambda_dq", "dlambda_dnu", "dlambda_dtau")
 
     def constrained_dynamics_derivatives(self, rigid_bodies, tau: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,

@@ -1041,6 +1041,60 @@ int wbc_sim_inverse_dynamics_regressor(wbc_sim* sim, const int32_t* bodies /* ho
 int wbc_sim_forward_dynamics_sensitivity(wbc_sim* sim, const int32_t* bodies /* host */, int nbodies, const float* tau, float* nudot,
                                          float* dnudot_dpi, float* workspace, int flags, void* stream);
 
+/* Recursive least-squares identification of the listed bodies' linear parameters (the columns of wbc_sim_inverse_dynamics_regressor),
+ * the classical baseline to the learned adaptation module: per env the P x P normal equations, P = 10 nbodies <= 30,
+ *     A <- forget A + Phi^T W Phi,   b <- forget b + Phi^T W z,   stat <- forget stat + (sum_c w_c z_c^2, number of rows with w_c > 0),
+ * updated by ONE launch per control step (wbc_identification_accumulate_kernel) at the sim's current state (the state sources of the
+ * regressor; read, never written). Phi [26, P] is the regressor's linear-parameter columns of the listed bodies, column s * 10 + k for
+ * bodies[s]; z = tau_gen - sum over the bodies NOT listed of Y_b pi_b, with pi_b their current linear parameters (the root's and the
+ * gripper body's from that env's WBC_T_BODY_PARAMS, the others' from wbc_model). Both come from the same closed-form entries inside the
+ * kernel: Y is never formed in HBM, and z is not formed as tau - Phi pi, so nothing cancels.
+ * bodies      HOST array of 1..WBC_IDENT_MAX_BODIES distinct moving-body indices (NULL is refused).
+ * nudot       device f32 [N, 26] or NULL (= zeros).
+ * tau_gen     device f32 [N, 26], required: the net generalised force in the rows of wbc_sim_inverse_dynamics, S^T tau + sum J^T f.
+ * row_weight  device f32 [N, 26], entries >= 0, or NULL (= 1 on the 24 live rows). The fingers' rows 24, 25 never count.
+ * forget      HOST float in (0, 1].
+ * info_mat    device f32 [N, P, P] (A), info_vec device f32 [N, P] (b), stat device f32 [N, 2]: read and written.
+ * target      device f32 [N, 26] or NULL: z (the fingers' rows: tau_gen).
+ * flags       WBC_IDENT_RESET: the incoming A, b and stat are taken as zero and never read (NaN-poisoned buffers are fine).
+ * A is written in full and is bit-symmetric. An env without a row of positive weight keeps its A, b and stat bit for bit, without
+ * decay (with WBC_IDENT_RESET they become zeros); its target is still written. Every sum has a fixed order and there are no atomics: the
+ * result is bitwise reproducible. The root POSITION is never read. All buffers are caller-owned, 16-byte aligned and share no bytes with
+ * an output. Nothing is allocated, so the call is safe under stream capture. HBM traffic per env: the state, the three [26] rows and one
+ * read and one write of A, b and stat.
+ *
+ * wbc_sim_identification_solve (wbc_identification_solve_kernel, one launch): (A + Lambda) pi_hat = b + Lambda pi_0 per env, Lambda =
+ * diag(prior_weight) >= 0. The matrix is equilibrated to a unit diagonal, D = diag(A + Lambda)^-1/2, then factorised and solved by the
+ * fp32 Cholesky core the contact kernels share.
+ * nbodies       1..WBC_IDENT_MAX_BODIES, as in the accumulate calls that built A, b and stat (device f32, read only).
+ * prior, prior_weight  device f32 [N, nbodies, 10] (pi_0 in the linear parameters; Lambda's diagonal) or NULL (weight NULL: 0; a NULL
+ *               prior with a weight is refused).
+ * pivot_tol     HOST float > 0.
+ * pi_hat        device f32 [N, nbodies, 10], required.
+ * theta_hat     device f32 [N, nbodies, 10] or NULL: (m, c = h / m, I_c = Ibar - m (|c|^2 1 - c c^T)), the parametrisation of
+ *               WBC_T_BODY_PARAMS.
+ * cov_diag      device f32 [N, nbodies, 10] or NULL: diag((A + Lambda)^-1).
+ * sse           device f32 [N] or NULL (needs stat): stat_0 - 2 pi_hat^T b + pi_hat^T A pi_hat, clamped at 0. Three fp32 numbers of the
+ *               size of stat_0 cancel here: it resolves no better than a few 2^-24 stat_0, whatever the true residual.
+ * status        device int32 [N, nbodies] or NULL. Bit 0, the same for all bodies of an env: a diagonal entry of A + Lambda that is not
+ *               positive and finite, or a squared pivot of the equilibrated factor <= pivot_tol; pi_hat is then the prior (zeros without
+ *               one), theta_hat its map (zeros without one), cov_diag +inf, sse the formula at that pi_hat, and status exactly 1.
+ *               Otherwise bit 1: m_hat <= 0; bit 2: I_c_hat not positive definite; bit 3: the triangle inequality of its principal
+ *               moments violated. Only the flags are built: the estimate is not projected.
+ * Both: -1 with a message in wbc_last_error(), nothing written, for a NULL sim or required buffer, a bad `bodies` / nbodies, forget
+ * outside (0, 1], pivot_tol not positive, unknown flag bits, a buffer that is not 16-byte aligned or an output that overlaps another
+ * buffer; -3 for a model whose tree the kernel cannot walk; -2 if a launch fails. Stream / device handling as wbc_sim_centroidal.
+ * OUT OF SCOPE: the step kernel's own substep (implicit PD, armature, contact impulses) as the source of tau_gen; a physically
+ * consistent projection; more than three bodies or a base-parameter reduction. */
+#define WBC_IDENT_MAX_BODIES 3   /* P = 10 * nbodies <= 30: fits the m <= 32 Cholesky core */
+#define WBC_IDENT_RESET 8        /* distinct from WBC_SOLVE_ARMATURE (1), WBC_DERIV_TRANSPOSED (2), WBC_REGRESSOR_NATIVE (4) */
+int wbc_sim_identification_accumulate(wbc_sim* sim, const int32_t* bodies /* host */, int nbodies, const float* nudot,
+                                      const float* tau_gen, const float* row_weight, float forget, float* info_mat, float* info_vec,
+                                      float* stat, float* target, int flags, void* stream);
+int wbc_sim_identification_solve(wbc_sim* sim, int nbodies, const float* info_mat, const float* info_vec, const float* stat,
+                                 const float* prior, const float* prior_weight, float pivot_tol, float* pi_hat, float* theta_hat,
+                                 float* cov_diag, float* sse, int32_t* status, void* stream);
+
 /* First-order layer of wbc_sim_constrained_dynamics: the analytic partial derivatives of its solution (nudot, lambda) with respect to
  * the configuration, the velocity and the applied force, in the tangent convention of wbc_sim_inverse_dynamics_derivatives above (dq =
  * root translation, WORLD rotation vector, joint increments; the world components of nu, nudot, tau (all 26 rows), acc_des and lambda
