@@ -266,7 +266,8 @@ def test_action_clip_timeout_and_episode_boundaries(robot):
     np.testing.assert_array_equal(_t(g, "RESET_BUF"), o.get("RESET_BUF"))
     np.testing.assert_array_equal(_t(g, "EPISODE_LENGTH"), o.get("EPISODE_LENGTH"))
     assert np.abs(_t(g, "ACTION_HISTORY")[_t(g, "RESET_BUF") == 0]).max() <= 100.0
-    for name in ("COMMANDS", "GOAL_STATE", "ACTION_HISTORY", "ROOT_STATES", "DOF_STATE"):
+    np.testing.assert_array_equal(_t(g, "ACTION_HISTORY"), o.get("ACTION_HISTORY"))      # a copy of the clipped action, zeros after a reset
+    for name in ("COMMANDS", "GOAL_STATE", "ROOT_STATES", "DOF_STATE"):
         np.testing.assert_allclose(_t(g, name), o.get(name), atol=5e-4, rtol=5e-4, err_msg=name)
     np.testing.assert_allclose(_t(g, "EPISODE_SUMS_DONE"), o.get("EPISODE_SUMS_DONE"), atol=2e-2, rtol=2e-3)
     g.close()
