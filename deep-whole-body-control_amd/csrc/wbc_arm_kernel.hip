@@ -12,6 +12,7 @@
 #include "wbc_delassus.h"
 #include "wbc_stream_guard.h"
 #include "wbc_tree.h"
+#include "wbc_proximity.h"
 
 #define ARM_N 6
 #define ARM_NLINK 9          // rigid bodies whose weight the reference compensates: the last 9 of the actor
@@ -4238,4 +4239,97 @@ extern "C" int wbc_sim_momentum_observer(wbc_sim* s, const float* tau, float gai
   if (rc != 0) return rc;
   const CoObs ob = {tau, g, gain, dt, (flags & WBC_OBSERVER_RESET) ? 1 : 0, state};
   return coriolis_launch(c, nullptr, nullptr, nullptr, ob, stream);
+}
+
+// ---- self-collision proximity: signed gaps, witness points and gap Jacobians (include/wbc_sim.h: wbc_sim_proximity) --------------------
+// The host side; the kernel is in wbc_proximity_kernel.hip, its argument struct in wbc_proximity.h.
+// The pair list and the primitives from the model the sim was created with (wbc_sim_create has checked the collision set's indices).
+// 0; 1: a tree the kernels cannot walk; 2: more sphere-box pairs on the root than PX_MAXBOX.
+static int prox_const_fill(const DevConst* hc, ProxConst& K, int32_t* pairs_out) {
+  const wbc_model& m = hc->model;
+  if (tree_walk_fill(m, K) != 0) return 1;
+  for (int b = 0; b < WBC_NB; ++b) {
+    K.anc[b] = 1u << b;
+    for (int a = b; a > 0; a = m.parent[a]) K.anc[b] |= 1u << m.parent[a];
+  }
+  int np = 0, nbox = 0;
+  for (int k = 0; k < WBC_NCP; ++k)
+    if (m.pr_kind[k] == WBC_PR_LIMBS) {
+      if (pairs_out) { pairs_out[4 * np] = WBC_PR_LIMBS; pairs_out[4 * np + 1] = m.pr_a[k]; pairs_out[4 * np + 2] = m.pr_b[k]; pairs_out[4 * np + 3] = 0; }
+      K.pair[np++] = WBC_PR_LIMBS | m.pr_a[k] << 8 | m.pr_b[k] << 16;
+    }
+  for (int k = 0; k < m.ncp && k < WBC_NCP; ++k)
+    if (m.cp_kind[k] == WBC_CP_BOX && m.cp_body2[k] == 0) {        // (a box on the free box actor has no generalised coordinate: not listed)
+      if (nbox == PX_MAXBOX) return 2;
+      if (m.cp_body[k] < 0 || m.cp_body[k] >= WBC_NB) return 1;
+      K.sb_body[nbox] = m.cp_body[k]; K.sb_rad[nbox] = m.cp_radius[k];
+      for (int j = 0; j < 3; ++j) { K.sb_pos[nbox][j] = m.cp_pos[k][j]; K.sb_centre[nbox][j] = m.cp_a[k][j]; K.sb_half[nbox][j] = m.cp_b[k][j]; }
+      if (pairs_out) { pairs_out[4 * np] = WBC_PR_STATIC; pairs_out[4 * np + 1] = m.cp_sph[k]; pairs_out[4 * np + 2] = m.cp_rb2[k]; pairs_out[4 * np + 3] = 0; }
+      K.pair[np++] = WBC_PR_STATIC | nbox << 8;
+      ++nbox;
+    }
+  for (int k = np; k < PX_MAXP; ++k) K.pair[k] = 0;
+  for (int k = nbox; k < PX_MAXBOX; ++k) {
+    K.sb_body[k] = 0; K.sb_rad[k] = 0.f;
+    for (int j = 0; j < 3; ++j) K.sb_pos[k][j] = K.sb_centre[k][j] = K.sb_half[k][j] = 0.f;
+  }
+  K.npairs = np;
+  for (int l = 0; l < WBC_NLIMB; ++l) {
+    const bool used = l < m.nlimb;
+    K.limb_body[l] = used ? m.limb_body[l] : 0;
+    const int ends[2] = {used ? hc->sph_slot[m.limb_s0[l]] : -1, used ? hc->sph_slot[m.limb_s1[l]] : -1};
+    for (int i = 0; i < 2; ++i) {
+      const int slot = ends[i];
+      if (used && (slot < 0 || slot >= WBC_NCP || m.cp_body[slot] < 0 || m.cp_body[slot] >= WBC_NB)) return 1;
+      K.end_body[l][i] = used ? m.cp_body[slot] : 0;
+      const int eb = K.end_body[l][i], lb = K.limb_body[l];
+      int link = eb == lb ? 0 : 3;
+      for (int k = 0; k < WBC_MAX_DEPTH && link == 3; ++k) {
+        if (K.path[lb][k] == eb) link = 1 | k << 4;
+        else if (K.path[eb][k] == lb) link = 2 | k << 4;
+      }
+      K.end_link[l][i] = link;
+      for (int j = 0; j < 3; ++j) K.end_pos[l][i][j] = used ? m.cp_pos[slot][j] : 0.f;
+    }
+    K.limb_rad[l][0] = used ? m.limb_radius[l] : 0.f; K.limb_rad[l][1] = used ? m.limb_cap0[l] : 0.f; K.limb_rad[l][2] = used ? m.limb_cap1[l] : 0.f;
+  }
+  return 0;
+}
+
+static int prox_pairs(const char* who, const wbc_sim* s, int32_t* out) {
+  WbCall c(who, const_cast<wbc_sim*>(s), nullptr);
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  ProxConst K;
+  const int rc = prox_const_fill(c.hc, K, out);
+  if (rc != 0) return rc == 1 ? c.no_tree() : c.fail(-3, "more sphere-box pairs on the root body than the kernel holds");
+  return K.npairs;
+}
+
+// The number of pairs P (0 for a model without self-collisions), or a negative error code.
+extern "C" int wbc_sim_proximity_pair_count(const wbc_sim* s) { return prox_pairs("wbc_sim_proximity_pair_count", s, nullptr); }
+
+// out (host int32 [P][4]): (kind, a, b, 0) per pair, include/wbc_sim.h. Returns P, or a negative error code.
+extern "C" int wbc_sim_proximity_pairs(const wbc_sim* s, int32_t* out) {
+  if (s && !out) { WbCall c("wbc_sim_proximity_pairs", const_cast<wbc_sim*>(s), nullptr); return c.fail(-1, "out is NULL"); }
+  return prox_pairs("wbc_sim_proximity_pairs", s, out);
+}
+
+// gap [N,P], normal [N,P,3], witness [N,P,2,3], jac [N,P,26] (device f32), nearest [N,k_nearest] (device int32), caller-owned, 4-byte
+// aligned, any may be NULL: include/wbc_sim.h.
+extern "C" int wbc_sim_proximity(wbc_sim* s, float* gap, float* normal, float* witness, float* jac, int32_t* nearest, int k_nearest, void* stream) {
+  WbCall c("wbc_sim_proximity", s, stream);
+  if (!s) return c.no_sim();
+  if (!gap && !normal && !witness && !jac && !nearest) return c.fail(-1, "gap, normal, witness, jac and nearest are all NULL");
+  if (((uintptr_t)gap | (uintptr_t)normal | (uintptr_t)witness | (uintptr_t)jac | (uintptr_t)nearest) & 3u)
+    return c.fail(-1, "gap / normal / witness / jac / nearest must be 4-byte aligned");
+  if (nearest && (k_nearest < 1 || k_nearest > 8)) return c.fail(-1, "k_nearest must be 1 .. 8");
+  if (!c.have) return c.no_state();
+  ProxConst K;
+  const int rc = prox_const_fill(c.hc, K, nullptr);
+  if (rc != 0) return rc == 1 ? c.no_tree() : c.fail(-3, "more sphere-box pairs on the root body than the kernel holds");
+  if (K.npairs == 0) return c.fail(-1, "the model has no self-collision pairs (self_collisions = False)");
+  if (c.n <= 0) return 0;
+  wbc_proximity_launch(K, c.root, c.dofs, c.n, gap, normal, witness, jac, nearest, nearest ? k_nearest : 0, stream);
+  return c.launched();
 }

@@ -202,6 +202,11 @@ SHOULDER_SLOT = 26
 DYN_SELF_SLOTS = list(range(27, 32)) + list(range(52, 64))
 DYN_BOX_SLOTS = [45, 46, 47]
 LEGS = ("FL", "FR", "RL", "RR")
+# Names of collision_set's limbs (by limb id) and robot spheres (by compact index), as WbcSim.proximity_pairs reports them.
+LIMB_NAMES = tuple(l + "_thigh" for l in LEGS) + tuple(l + "_calf" for l in LEGS) + ("upper_arm", "forearm", "hand")
+SPHERE_NAMES = (tuple(l + "_foot" for l in LEGS) + tuple(l + "_knee" for l in LEGS) + ("gripper", "elbow", "wrist")
+                + tuple(l + "_thigh_top" for l in LEGS) + tuple(f"trunk_corner{i}" for i in range(8)) + tuple(l + "_shank" for l in LEGS)
+                + ("shoulder",))
 
 
 def collision_set(m: RobotModel, foot_name: str = "foot", gripper_name: str = "wx250s/ee_gripper_link", self_collisions: bool = True,

@@ -537,6 +537,69 @@ class WbcSim:
               "wbc_sim_momentum_observer")
         return state
 
+    # ---- self-collision proximity: gaps, witness points and gap Jacobians (include/wbc_sim.h: wbc_sim_proximity) ------------------------
+    @property
+    def proximity_pair_ids(self) -> np.ndarray:
+        """int32 [P, 4]: (kind, a, b, 0) per pair as wbc_sim_proximity_pairs lists them (abi.PR_LIMBS: limb ids; abi.PR_STATIC: the
+        sphere's compact index and the box's rigid body). P = 0 for a model without self-collisions."""
+        ids = self.__dict__.get("_proximity_pair_ids")
+        if ids is None:
+            p = self.L.wbc_sim_proximity_pair_count(self.h)
+            if p < 0:
+                check(p, "wbc_sim_proximity_pair_count")
+            buf = (C.c_int32 * (4 * max(p, 1)))()
+            if p > 0 and self.L.wbc_sim_proximity_pairs(self.h, buf) != p:
+                check(-1, "wbc_sim_proximity_pairs")
+            ids = self._proximity_pair_ids = np.array(buf[:4 * p], dtype=np.int32).reshape(p, 4)
+        return ids
+
+    @property
+    def proximity_pairs(self):
+        """[(name_a, name_b)] per pair, in the order of every output of proximity(): collision_set's limb names for a limb pair, the
+        sphere's name and "trunk" for a sphere against the trunk box."""
+        name = lambda table, i, what: table[i] if 0 <= i < len(table) else f"{what}{i}"
+        return [(name(abi.LIMB_NAMES, a, "limb"), name(abi.LIMB_NAMES, b, "limb")) if kind == abi.PR_LIMBS
+                else (name(abi.SPHERE_NAMES, a, "sphere"), "trunk") for kind, a, b, _ in self.proximity_pair_ids.tolist()]
+
+    def proximity(self, gap: Optional[torch.Tensor] = None, normal: Optional[torch.Tensor] = None, witness: Optional[torch.Tensor] = None,
+                  jac: Optional[torch.Tensor] = None, k_nearest: int = 0, nearest: Optional[torch.Tensor] = None):
+        """One wbc_sim_proximity launch on the current stream into the tensors that are passed; returns the tensors it filled, in the
+        order (gap [N, P], normal [N, P, 3], witness [N, P, 2, 3], jac [N, P, 26], nearest int32 [N, k_nearest]): the signed distances
+        of the robot's own collision pairs (proximity_pairs), the unit vectors from b's closest point to a's, the two surface points
+        relative to the root's origin (world axes) and d gap / d q with d gap / dt = jac . nu. With no float tensor passed all four
+        are allocated and filled; k_nearest in 1 .. 8 (or a `nearest` tensor) adds the indices of the k smallest gaps per env."""
+        n, ncol, p = self.num_envs, 6 + abi.NDOF, len(self.proximity_pair_ids)
+        shapes = ((n, p), (n, p, 3), (n, p, 2, 3), (n, p, ncol))
+        outs = [gap, normal, witness, jac]
+        if all(t is None for t in outs) and nearest is None and p > 0:
+            outs = [torch.empty(sh, dtype=torch.float32, device=self.device) for sh in shapes]
+        if nearest is None and k_nearest:
+            nearest = torch.empty((n, int(k_nearest)), dtype=torch.int32, device=self.device)
+        for t, sh in zip(outs, shapes):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        if nearest is not None:
+            assert nearest.device == self.arena.device and nearest.dtype == torch.int32 and nearest.is_contiguous()
+            assert nearest.dim() == 2 and nearest.shape[0] == n, tuple(nearest.shape)
+        check(self.L.wbc_sim_proximity(self.h, *[t.data_ptr() if t is not None else None for t in outs + [nearest]],
+                                       int(nearest.shape[1]) if nearest is not None else 0, self._stream()), "wbc_sim_proximity")
+        return tuple(t for t in outs + [nearest] if t is not None)
+
+    def proximity_damper_rows(self, gap: torch.Tensor, jac: torch.Tensor, d_safe: float, d_influence: float, xi: float, dt: float,
+                              nu: Optional[torch.Tensor] = None):
+        """The velocity damper of the pairs inside the influence distance as rows on the accelerations, torch ops only: the gap rate
+        after one step, jac . (nu + dt nudot), may not fall below -xi (gap - d_safe) / (d_influence - d_safe), i.e. A nudot >= b with
+        A = dt jac [N, P, 26] and b = -xi (gap - d_safe) / (d_influence - d_safe) - jac . nu [N, P]. A pair with gap >= d_influence has
+        its row zeroed and b = -inf (never binding). nu f32 [N, 26] in the coordinates of jac; None: the sim's current velocities.
+        Handing the rows to the task-space QP (wbc_sim_task_inverse_dynamics_qp takes no extra rows yet) is the follow-up."""
+        assert d_influence > d_safe and dt > 0
+        if nu is None:
+            nu = torch.cat([self.tensor("ROOT_STATES")[:, 0, 7:13], self.tensor("DOF_STATE")[:, :, 1]], dim=1)
+        near = gap < d_influence
+        a = torch.where(near.unsqueeze(-1), jac * dt, torch.zeros_like(jac))
+        b = -xi * (gap - d_safe) / (d_influence - d_safe) - torch.einsum("npc,nc->np", jac, nu)
+        return a, torch.where(near, b, torch.full_like(b, float("-inf")))
+
     # ---- analytic derivatives of inverse and forward dynamics (include/wbc_sim.h: wbc_sim_inverse_dynamics_derivatives) ----------------
     def inverse_dynamics_derivatives(self, nudot: Optional[torch.Tensor] = None, dq: Optional[torch.Tensor] = None,
                                      dnu: Optional[torch.Tensor] = None, transposed: bool = False):

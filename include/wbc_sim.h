@@ -943,6 +943,41 @@ int wbc_sim_coriolis(wbc_sim* sim, float* cmat, float* mdot, float* vec, void* s
 #define WBC_OBSERVER_RESET 1
 int wbc_sim_momentum_observer(wbc_sim* sim, const float* tau, float gain, float dt, int flags, float* state, void* stream);
 
+/* Self-collision proximity: the signed gaps of the robot's own collision pairs, their closest points and d gap / d q, from the sim's
+ * current root / DoF state in one launch (wbc_proximity_kernel). The sim's state is read, never written.
+ * THE PAIRS are those of the model the sim was created with, in a fixed order: first the lanes whose pr_kind is WBC_PR_LIMBS, in lane
+ * order (44 in the shipped model), then the static pairs of cp_kind WBC_CP_BOX whose box rides on a robot body (3: the gripper, wrist and
+ * elbow spheres against the trunk box); P = 47. Pairs against the free box actor are not listed: the box has no generalised coordinate.
+ * wbc_sim_proximity_pair_count returns P (0 for a model built without self-collisions) or a negative error code;
+ * wbc_sim_proximity_pairs writes (kind, a, b, 0) per pair into out (host int32 [P][4]) and returns P: kind WBC_PR_LIMBS with the limb ids
+ * a, b; kind WBC_PR_STATIC with a = the sphere's compact index (cp_sph) and b = the box's rigid body (cp_rb2). Both run on the host alone (-1 for a NULL sim or out).
+ * GEOMETRY, that of the step kernel's exact test: a limb is the union of its shaft capsule (limb_radius about the segment between its end
+ * spheres' centres) and its end spheres (limb_cap0 / limb_cap1; 0: none). A limb pair's gap is the smallest over its feature pairs, in the
+ * order shaft-shaft, A's end spheres against B's shaft, A's shaft against B's end spheres, end sphere against end sphere (of equal gaps the
+ * earlier); for a feature pair with the core points c_a, c_b (the closest points of the two core segments or centres) gap = |c_a - c_b| -
+ * r_a - r_b. For a sphere against a box c_b is the box's closest point to the centre c_a, r_b = 0 and r_a = cp_radius; with the centre
+ * inside the box gap = -(depth to the nearest face) - r_a and the normal is that face's. pair_rest_offset and contact_margin are NOT
+ * subtracted: this is geometry, not the contact law's activation distance. Segments shorter than 1e-5 m count as points; parallel shafts
+ * (sin^2 of their angle <= 1e-7) take the first end of A as A's parameter, where gap and normal are unique and the core points are not.
+ * gap      device f32 [N, P].
+ * normal   device f32 [N, P, 3]: the unit vector n from c_b to c_a of the winning feature pair, world axes ((1, 0, 0) in base axes where
+ *          the core points coincide).
+ * witness  device f32 [N, P, 2, 3]: the surface points w_a = c_a - r_a n and w_b = c_b + r_b n, world axes, RELATIVE TO THE ROOT'S ORIGIN.
+ * jac      device f32 [N, P, 26] = d gap / d q in the coordinates of wbc_sim_body_dynamics: d gap / dt = jac . nu. Entry c is n . (column c
+ *          of the linear Jacobian of the point c_a riding on a's moving body minus that of c_b on b's), each lever taken from the joint's
+ *          own origin. Columns 0:6 (a self-distance does not see the root), the columns of every joint that moves neither body or both,
+ *          and the locked fingers' columns 24, 25 are exactly 0. A limb's moving body is limb_body, a sphere's cp_body, the trunk box's 0.
+ * nearest  device int32 [N, k_nearest], 1 <= k_nearest <= 8: the indices of the env's k_nearest smallest gaps in ascending order of
+ *          (gap, pair index), decided on the launch's own gap values (-1 beyond P). k_nearest is ignored where nearest is NULL.
+ * Any output may be NULL and is then not written; not all five. What is written does not depend on which others are asked for. Every
+ * pointer needs 4-byte alignment only. The root POSITION and every velocity are never read: every output is bit-identical under a
+ * translation of the robot. Nothing is allocated and nothing synchronises: safe under stream capture. -1 with a message in
+ * wbc_last_error() that names the entry point, nothing written: NULL sim; all outputs NULL; a misaligned pointer; k_nearest out of range;
+ * a model with P = 0. -3 / -2 and stream handling as wbc_sim_coriolis. */
+int wbc_sim_proximity_pair_count(const wbc_sim* sim);
+int wbc_sim_proximity_pairs(const wbc_sim* sim, int32_t* out);
+int wbc_sim_proximity(wbc_sim* sim, float* gap, float* normal, float* witness, float* jac, int32_t* nearest, int k_nearest, void* stream);
+
 /* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and
  * of nudot(q, nu, tau) in the coordinates of wbc_sim_body_dynamics, from the sim's current root / DoF state, WBC_T_BODY_PARAMS and all
  * three gravity components. The sim's state is read, never written.
