@@ -56,9 +56,6 @@ __device__ long long* g_ppo_dbg = nullptr;
 extern "C" void wbc_debug_set_ppo_timing(void* dev_buf) {
   long long* p = (long long*)dev_buf;
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ppo_dbg), &p, sizeof(p));
-#ifdef WBC_PPO_TIMING
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_mlp_dbg), &p, sizeof(p));
-#endif
 }
 
 #include "wbc_ppo_chain.h"
