@@ -13,6 +13,7 @@
 #include "wbc_stream_guard.h"
 #include "wbc_tree.h"
 #include "wbc_proximity.h"
+#include "wbc_estimator.h"
 
 #define ARM_N 6
 #define ARM_NLINK 9          // rigid bodies whose weight the reference compensates: the last 9 of the actor
@@ -4331,5 +4332,44 @@ extern "C" int wbc_sim_proximity(wbc_sim* s, float* gap, float* normal, float* w
   if (K.npairs == 0) return c.fail(-1, "the model has no self-collision pairs (self_collisions = False)");
   if (c.n <= 0) return 0;
   wbc_proximity_launch(K, c.root, c.dofs, c.n, gap, normal, witness, jac, nearest, nearest ? k_nearest : 0, stream);
+  return c.launched();
+}
+
+// ---- leg-odometry Kalman filter (include/wbc_sim.h: wbc_sim_leg_odometry) -----------------------------------------------------------------
+// The host side; the kernel is in wbc_estimator_kernel.hip, its argument structs in wbc_estimator.h.
+extern "C" int wbc_sim_leg_odometry(wbc_sim* s, const wbc_estimator_cfg* cfg, const float* quat, const float* gyro, const float* dof,
+                                    const float* accel, const float* contact, const float* foot_height, const int32_t* reset_mask,
+                                    const float* p_init, int flags, float* x, float* P, float* vel_body, float* nis, int32_t* status, void* stream) {
+  WbCall c("wbc_sim_leg_odometry", s, stream);
+  // the arguments first, so that every refusal below can be met (and tested) without a sim; then the sim
+  if (!cfg) return c.fail(-1, "cfg is NULL");
+  if (!contact || !x || !P) return c.fail(-1, "contact, x or P is NULL");
+  if (flags & ~WBC_ESTIMATOR_RESET) return c.fail(-1, "unknown flag bits");
+  auto positive = [](float v) { return v > 0.f && v <= 3.4e38f; };
+  if (!positive(cfg->dt)) return c.fail(-1, "dt must be finite and > 0");
+  if (!positive(cfg->sigma_p) || !positive(cfg->sigma_v) || !positive(cfg->sigma_f) || !positive(cfg->sigma_r) || !positive(cfg->sigma_rdot) ||
+      !positive(cfg->sigma_z))
+    return c.fail(-1, "every sigma must be finite and > 0");
+  if (!positive(cfg->p0_p) || !positive(cfg->p0_v) || !positive(cfg->p0_f)) return c.fail(-1, "every initial variance must be finite and > 0");
+  if (!(cfg->kappa >= 0.f) || !(cfg->kappa <= 3.4e38f)) return c.fail(-1, "kappa must be finite and >= 0");
+  if (((uintptr_t)quat | (uintptr_t)gyro | (uintptr_t)dof | (uintptr_t)accel | (uintptr_t)contact | (uintptr_t)foot_height | (uintptr_t)reset_mask |
+       (uintptr_t)p_init | (uintptr_t)x | (uintptr_t)P | (uintptr_t)vel_body | (uintptr_t)nis | (uintptr_t)status) & 3u)
+    return c.fail(-1, "every pointer must be 4-byte aligned");
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  const wbc_model& m = c.hc->model;
+  EstConst K;
+  if (tree_walk_fill(m, K) != 0 || !tree_rigid_ok(m)) return c.no_tree();
+  for (int f = 0; f < WBC_NFEET; ++f) {
+    const int rb = m.feet_rb[f];
+    if (rb < 0 || rb >= WBC_NRB) return c.no_tree();
+    K.foot_body[f] = m.rb_body[rb];
+    for (int j = 0; j < 3; ++j) K.foot_off[f][j] = m.rb_offset[rb][j];
+  }
+  for (int j = 0; j < 3; ++j) K.gravity[j] = c.hc->cfg.gravity[j];
+  if (c.n <= 0) return 0;
+  const EstArgs a = {c.root, dof ? dof : c.dofs, quat ? quat : c.root + 3, gyro, accel, contact, foot_height, p_init, reset_mask,
+                     quat ? 4 : 26, (flags & WBC_ESTIMATOR_RESET) ? 1 : 0, c.n, x, P, vel_body, nis, status};
+  wbc_estimator_launch(K, *cfg, a, stream);
   return c.launched();
 }

@@ -94,3 +94,16 @@ __device__ __forceinline__ void delassus_column_solve(const float (*A)[LA], cons
     x[i * pitch] = s * D[i];
   }
 }
+
+// L y = x in place by one lane, the forward half of delassus_column_solve alone (what a Kalman gain in square-root form needs: L^-1 B, never
+// L^-T): x[0], x[pitch], ... is a column of a row-major block in LDS.
+template <int LA>
+__device__ __forceinline__ void delassus_column_forward(const float (*A)[LA], const float* D, float* x, int pitch, int m) {
+#pragma nounroll
+  for (int i = 0; i < m; ++i) {
+    float s = x[i * pitch];
+#pragma unroll 8
+    for (int k = 0; k < i; ++k) s -= A[i][k] * x[k * pitch];
+    x[i * pitch] = s * D[i];
+  }
+}

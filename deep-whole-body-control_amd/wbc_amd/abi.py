@@ -112,6 +112,15 @@ OBSERVER_RESET = 1         # WBC_OBSERVER_RESET (wbc_sim_momentum_observer's own
 IDENT_RESET = 8            # WBC_IDENT_RESET (wbc_sim_identification_accumulate; distinct from the three above)
 IDENT_MAX_BODIES = 3       # WBC_IDENT_MAX_BODIES: 10 parameters each, P <= 30
 NPARAM = 10               # inertial parameters per moving body (include/wbc_sim.h: wbc_sim_inverse_dynamics_regressor)
+ESTIMATOR_RESET = 1        # WBC_ESTIMATOR_RESET (wbc_sim_leg_odometry's own flags word)
+ESTIMATOR_STATUS_OK, ESTIMATOR_STATUS_RESET, ESTIMATOR_STATUS_FAILED = 0, 1, 2   # WBC_ESTIMATOR_STATUS_*
+ESTIMATOR_NX = 18          # (p, v, four foot origins)
+
+
+class WbcEstimatorCfg(C.Structure):
+    """wbc_estimator_cfg (include/wbc_sim.h): the host scalars of wbc_sim_leg_odometry."""
+    _fields_ = [(name, f32) for name in ("dt", "sigma_p", "sigma_v", "sigma_f", "sigma_r", "sigma_rdot", "sigma_z", "kappa",
+                                          "p0_p", "p0_v", "p0_f")]
 
 
 class WbcTaskQpLimits(C.Structure):

@@ -37,6 +37,11 @@ def _quat_apply(q, v):
     return v + q[:, 3:] * t + torch.linalg.cross(xyz, t, dim=-1)
 
 
+def _quat_rotate_inverse(q, v):
+    """R(q)^T v."""
+    return _quat_apply(torch.cat([-q[:, :3], q[:, 3:]], dim=-1), v)
+
+
 def _orientation_error(desired, current):                                           # widowGo1.py orientation_error
     cc = torch.cat([-current[:, :3], current[:, 3:]], dim=-1)
     q_r = _quat_mul(desired, cc)
@@ -775,6 +780,12 @@ class WidowGo1(LeggedRobot):
         composite and the gripper body, the two that BODY_PARAMS randomises): see ParameterIdentifier."""
         return ParameterIdentifier(self, bodies, forget)
 
+    # ---- state estimation (no counterpart in the reference): include/wbc_sim.h: wbc_sim_leg_odometry ----
+    def base_state_estimator(self, **cfg) -> "BaseStateEstimator":
+        """A leg-odometry Kalman filter for the base's linear velocity and position from what the robot can sense, the classical
+        counterpart of what the policy has to infer: see BaseStateEstimator (cfg: its noise parameters and dt, default env.dt)."""
+        return BaseStateEstimator(self, **cfg)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])
@@ -1027,3 +1038,92 @@ class ParameterIdentifier:
         """f32 [N]: the estimated mass of the gripper body less its nominal mass (the gripper body must be listed)."""
         s = self.bodies.index(int(self.env.robot_model.gripper_piece["body"]))
         return self.estimate(prior_weight)[0][:, abi.NPARAM * s] - self.prior[:, s, 0]
+
+
+
+class BaseStateEstimator:
+    """The leg-odometry Kalman filter of wbc_sim_leg_odometry for every env: it owns the state x [N, 18] = (p, v, four foot origins) and
+    its covariance P [N, 18, 18] and advances them by one launch per update(). Keyword arguments are the fields of wbc_estimator_cfg
+    (include/wbc_sim.h); dt defaults to env.dt. The estimator starts reset at the true root position."""
+
+    DEFAULTS = dict(sigma_p=0.02, sigma_v=0.5, sigma_f=0.02, sigma_r=0.005, sigma_rdot=0.1, sigma_z=0.005, kappa=1000.0,
+                    p0_p=1e-4, p0_v=0.25, p0_f=1e-4)
+
+    def __init__(self, env, dt: float = None, **cfg):
+        unknown = set(cfg) - set(self.DEFAULTS)
+        assert not unknown, f"unknown estimator parameters: {sorted(unknown)}"
+        values = dict(self.DEFAULTS, **cfg)
+        self.env = env
+        self.cfg = abi.WbcEstimatorCfg(float(env.dt if dt is None else dt), *[float(values[k]) for k in self.DEFAULTS])
+        n, dev = env.num_envs, env.device
+        self.x = torch.zeros((n, abi.ESTIMATOR_NX), dtype=torch.float32, device=dev)
+        self.P = torch.zeros((n, abi.ESTIMATOR_NX, abi.ESTIMATOR_NX), dtype=torch.float32, device=dev)
+        self.base_lin_vel = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        self.nis = torch.zeros((n,), dtype=torch.float32, device=dev)
+        self.status = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self._gravity = torch.tensor(list(env.tcfg.gravity), dtype=torch.float32, device=dev)
+        self._plane_height = torch.zeros((n, 4), dtype=torch.float32, device=dev) if env.cfg.terrain.mesh_type in ("plane", None) else None
+        self._last_root_vel = env.root_states[:, 7:10].clone()
+        self.last_inputs = None
+        self.reset()
+
+    @property
+    def position(self) -> torch.Tensor:
+        """f32 [N, 3]: the estimated position of the trunk's origin, world axes (a view of x)."""
+        return self.x[:, 0:3]
+
+    @property
+    def velocity(self) -> torch.Tensor:
+        """f32 [N, 3]: the estimated velocity of the trunk's origin, world axes (a view of x); base_lin_vel is the same in trunk axes."""
+        return self.x[:, 3:6]
+
+    @property
+    def foot_positions(self) -> torch.Tensor:
+        """f32 [N, 4, 3]: the estimated foot origins, world axes, in feet_indices order (a view of x)."""
+        return self.x[:, 6:].view(-1, 4, 3)
+
+    def _launch(self, contact, reset_mask=None, reset=False, **inputs):
+        p_init = self.env.root_states[:, 0:3].contiguous() if (reset or reset_mask is not None) else None
+        self.last_inputs = dict(inputs, contact=contact, reset_mask=reset_mask, p_init=p_init, reset=reset)
+        self.env.sim.leg_odometry(self.cfg, self.x, self.P, contact, reset_mask=reset_mask, p_init=p_init, reset=reset,
+                                  vel_body=self.base_lin_vel, nis=self.nis, status=self.status, **inputs)
+
+    def reset(self, env_ids=None) -> None:
+        """Reset every env (env_ids None) or the listed ones to their true root position, zero velocity, the feet where the leg
+        kinematics put them and the initial covariance. One launch; the other envs are left as they are."""
+        env = self.env
+        contact = env.get_foot_contacts().to(torch.float32)
+        if env_ids is None:
+            self._last_root_vel.copy_(env.root_states[:, 7:10])
+            self._launch(contact, reset=True)
+            return
+        ids = torch.as_tensor(env_ids, dtype=torch.long, device=env.device)
+        self._last_root_vel[ids] = env.root_states[ids, 7:10]
+        keep = (self.x.clone(), self.P.clone(), self.base_lin_vel.clone(), self.nis.clone(), self.status.clone())
+        mask = torch.zeros((env.num_envs,), dtype=torch.int32, device=env.device)
+        mask[ids] = 1
+        self._launch(contact, reset_mask=mask)
+        rest = mask == 0                                                            # the launch also advanced the others: put them back
+        for t, k in zip((self.x, self.P, self.base_lin_vel, self.nis, self.status), keep):
+            t[rest] = k[rest]
+
+    def update(self, contact=None, accel=None, quat=None, gyro=None, dof=None, foot_height=None) -> torch.Tensor:
+        """One update over env.dt at the sim's current state, to be called once after every env.step(); returns base_lin_vel [N, 3].
+        Defaults: contact = env.get_foot_contacts(), the four flags the policy observes; accel = the specific force in trunk axes from
+        the finite difference of the root's world velocity since the previous update; quat, gyro, dof = the sim's state; foot_height =
+        0 on the plane and none (no height rows) on other terrain (the rows hold the foot ORIGINS to that height: pass the ground height plus
+        the foot sphere's radius to account for it). Pass tensors to put sensor noise in. Envs flagged in env.reset_buf
+        are reset at their true root position instead. The tensors handed to the kernel are kept in last_inputs."""
+        env = self.env
+        if contact is None:
+            contact = env.get_foot_contacts()
+        contact = contact.to(torch.float32).contiguous()
+        vel = env.root_states[:, 7:10]
+        if accel is None:
+            a_world = (vel - self._last_root_vel) / self.cfg.dt - self._gravity
+            accel = _quat_rotate_inverse(env.base_quat if quat is None else quat, a_world).contiguous()
+        self._last_root_vel.copy_(vel)
+        if foot_height is None:
+            foot_height = self._plane_height
+        self._launch(contact, reset_mask=env.reset_buf.to(torch.int32), accel=accel, quat=quat, gyro=gyro, dof=dof, foot_height=foot_height)
+        return self.base_lin_vel

@@ -585,6 +585,37 @@ class WbcSim:
                                        int(nearest.shape[1]) if nearest is not None else 0, self._stream()), "wbc_sim_proximity")
         return tuple(t for t in outs + [nearest] if t is not None)
 
+    # ---- leg-odometry Kalman filter (include/wbc_sim.h: wbc_sim_leg_odometry) --------------------------------------------------------------
+    def leg_odometry(self, cfg: "abi.WbcEstimatorCfg", x: torch.Tensor, P: torch.Tensor, contact: torch.Tensor,
+                     quat: Optional[torch.Tensor] = None, gyro: Optional[torch.Tensor] = None, dof: Optional[torch.Tensor] = None,
+                     accel: Optional[torch.Tensor] = None, foot_height: Optional[torch.Tensor] = None,
+                     reset_mask: Optional[torch.Tensor] = None, p_init: Optional[torch.Tensor] = None, reset: bool = False,
+                     vel_body: Optional[torch.Tensor] = None, nis: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None):
+        """One wbc_sim_leg_odometry launch on the current stream: one predict + correct of the caller-owned state x f32 [N, 18] = (p, v,
+        four foot origins) and covariance P f32 [N, 18, 18], in place. contact f32 [N, 4] in [0, 1]; quat [N, 4] (xyzw), gyro [N, 3]
+        (trunk axes) and dof [N, 20, 2], None: the sim's current state; accel [N, 3] the specific force in trunk axes (None: constant
+        velocity); foot_height [N, 4] the ground's world height under each foot (None: no height rows). reset=True resets every env,
+        reset_mask int32 [N] the envs whose entry is not 0, to p_init [N, 3] (None: 0). Returns the tensors it filled, in the order
+        (x, P, vel_body [N, 3] = R^T v, nis [N], status int32 [N]); with none of the last three passed all three are allocated."""
+        n = self.num_envs
+        outs = [vel_body, nis, status]
+        if all(t is None for t in outs):
+            outs = [torch.empty((n, 3), dtype=torch.float32, device=self.device), torch.empty((n,), dtype=torch.float32, device=self.device),
+                    torch.empty((n,), dtype=torch.int32, device=self.device)]
+        f32, i32 = torch.float32, torch.int32
+        for t, sh, dt in ((x, (n, abi.ESTIMATOR_NX), f32), (P, (n, abi.ESTIMATOR_NX, abi.ESTIMATOR_NX), f32), (contact, (n, 4), f32),
+                          (quat, (n, 4), f32), (gyro, (n, 3), f32), (dof, (n, abi.NDOF, 2), f32), (accel, (n, 3), f32),
+                          (foot_height, (n, 4), f32), (reset_mask, (n,), i32), (p_init, (n, 3), f32), (outs[0], (n, 3), f32),
+                          (outs[1], (n,), f32), (outs[2], (n,), i32)):
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        assert x is not None and P is not None and contact is not None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        check(self.L.wbc_sim_leg_odometry(self.h, C.byref(cfg), ptr(quat), ptr(gyro), ptr(dof), ptr(accel), ptr(contact), ptr(foot_height),
+                                          ptr(reset_mask), ptr(p_init), abi.ESTIMATOR_RESET if reset else 0, x.data_ptr(), P.data_ptr(),
+                                          ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), self._stream()), "wbc_sim_leg_odometry")
+        return tuple(t for t in [x, P] + outs if t is not None)
+
     def proximity_damper_rows(self, gap: torch.Tensor, jac: torch.Tensor, d_safe: float, d_influence: float, xi: float, dt: float,
                               nu: Optional[torch.Tensor] = None):
         """The velocity damper of the pairs inside the influence distance as rows on the accelerations, torch ops only: the gap rate

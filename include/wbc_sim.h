@@ -978,6 +978,51 @@ int wbc_sim_proximity_pair_count(const wbc_sim* sim);
 int wbc_sim_proximity_pairs(const wbc_sim* sim, int32_t* out);
 int wbc_sim_proximity(wbc_sim* sim, float* gap, float* normal, float* witness, float* jac, int32_t* nearest, int k_nearest, void* stream);
 
+/* One update of the leg-odometry Kalman filter, the classical estimator of what no sensor on the robot measures: the base's linear velocity
+ * and its position relative to the footholds, from the IMU and the leg kinematics (a stance foot does not move). One launch
+ * (wbc_leg_odometry_kernel); the sim's state is read, never written. Per env the caller owns
+ * x      device f32 [N, 18] = (p, v, p_1 .. p_4): position and velocity of the trunk's origin and the origins of the four feet (the rigid
+ *        bodies feet_rb, in that order), world axes;
+ * P      device f32 [N, 18, 18], its covariance. P is read as a symmetric matrix (its lower triangle is read) and written bit-symmetric.
+ * INPUTS of one update over a step cfg->dt that ends now; each of quat, gyro and dof may be NULL, which means the sim's current state:
+ * quat   device f32 [N, 4], xyzw: the trunk's orientation R (world <- trunk), normalised in the call. NULL: ROOT_STATES' quaternion.
+ * gyro   device f32 [N, 3]: the angular velocity w_b in trunk axes. NULL: ROOT_STATES' world angular velocity rotated by R^T.
+ * dof    device f32 [N, 20, 2]: (q, qd) in the layout of DOF_STATE. NULL: DOF_STATE.
+ * accel  device f32 [N, 3] or NULL: the specific force in trunk axes over the interval this call advances across; a = R accel + g with
+ *        wbc_task_cfg.gravity. NULL: a = 0, the constant-velocity model.
+ * contact      device f32 [N, 4], required: c_i, clamped to [0, 1]; 1 a stance foot, 0 a swing foot.
+ * foot_height  device f32 [N, 4] or NULL: the world height of the ground under each foot. NULL leaves the four height rows out (m = 24).
+ * With r_i = R fk_i(q) and rdot_i = R (w_b x fk_i(q) + J_i(q) qd) from the leg kinematics and s_i = 1 + kappa (1 - c_i):
+ *   predict   p <- p + v dt + a dt^2 / 2, v <- v + a dt, the feet unchanged; P- = A P A^T + Q with A = I + dt I_3 in the (p, v) block and
+ *             Q = dt diag(sigma_p^2 I_3, sigma_v^2 I_3, sigma_f^2 s_i I_3 per foot);
+ *   correct   twelve position rows (foot-major) -r_i - (p - p_i) of variance sigma_r^2 s_i, twelve velocity rows -rdot_i - v of variance
+ *             sigma_rdot^2 s_i, four height rows foot_height_i - p_i,z of variance sigma_z^2 s_i; S = C P- C^T + R_m = L L^T,
+ *             W = L^-1 C P-, y = L^-1 e: x+ = x- + W^T y, P+ = P- - W^T W, nis = |y|^2.
+ * Where a pivot of S fails the env keeps the predicted (x-, P-), nis = 0 and status WBC_ESTIMATOR_STATUS_FAILED; finite inputs give finite outputs.
+ * RESET: with WBC_ESTIMATOR_RESET in flags every env, with reset_mask (device int32 [N] or NULL) the envs whose entry is not 0:
+ * p = p_init (device f32 [N, 3]; NULL: 0), v = 0, p_i = p + r_i, P = diag(p0_p I_3, p0_v I_3, p0_f I_12), nis = 0, status
+ * WBC_ESTIMATOR_STATUS_RESET; such an env is neither predicted nor corrected in that call, and its x and P are not read.
+ * OUTPUTS besides x and P, each may be NULL and is then not written; what is written does not depend on which are asked for:
+ * vel_body  device f32 [N, 3] = R^T v, the estimate of BASE_LIN_VEL;   nis  device f32 [N];   status  device int32 [N].
+ * Every pointer needs 4-byte alignment only. Nothing is allocated and nothing synchronises: safe under stream capture. -1 with a message
+ * in wbc_last_error() that names the entry point, nothing written: NULL sim, cfg, contact, x or P; unknown flag bits; dt, a sigma or an
+ * initial variance that is not finite and > 0; kappa not finite or < 0; a misaligned pointer. -3 / -2 and stream handling as
+ * wbc_sim_coriolis. */
+typedef struct {
+  float dt;                                  /* s */
+  float sigma_p, sigma_v, sigma_f;           /* process noise densities of p, v and a stance foot's origin */
+  float sigma_r, sigma_rdot, sigma_z;        /* standard deviations of the position, velocity and height rows of a stance foot */
+  float kappa;                               /* swing inflation: variances of foot i times 1 + kappa (1 - c_i) */
+  float p0_p, p0_v, p0_f;                    /* the variances a reset starts from */
+} wbc_estimator_cfg;
+#define WBC_ESTIMATOR_RESET 1
+#define WBC_ESTIMATOR_STATUS_OK 0
+#define WBC_ESTIMATOR_STATUS_RESET 1
+#define WBC_ESTIMATOR_STATUS_FAILED 2
+int wbc_sim_leg_odometry(wbc_sim* sim, const wbc_estimator_cfg* cfg, const float* quat, const float* gyro, const float* dof, const float* accel,
+                         const float* contact, const float* foot_height, const int32_t* reset_mask, const float* p_init, int flags,
+                         float* x, float* P, float* vel_body, float* nis, int32_t* status, void* stream);
+
 /* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and
  * of nudot(q, nu, tau) in the coordinates of wbc_sim_body_dynamics, from the sim's current root / DoF state, WBC_T_BODY_PARAMS and all
  * three gravity components. The sim's state is read, never written.
