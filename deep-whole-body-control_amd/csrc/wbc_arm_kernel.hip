@@ -14,6 +14,7 @@
 #include "wbc_tree.h"
 #include "wbc_proximity.h"
 #include "wbc_estimator.h"
+#include "wbc_mpc.h"
 
 #define ARM_N 6
 #define ARM_NLINK 9          // rigid bodies whose weight the reference compensates: the last 9 of the actor
@@ -4371,5 +4372,67 @@ extern "C" int wbc_sim_leg_odometry(wbc_sim* s, const wbc_estimator_cfg* cfg, co
   const EstArgs a = {c.root, dof ? dof : c.dofs, quat ? quat : c.root + 3, gyro, accel, contact, foot_height, p_init, reset_mask,
                      quat ? 4 : 26, (flags & WBC_ESTIMATOR_RESET) ? 1 : 0, c.n, x, P, vel_body, nis, status};
   wbc_estimator_launch(K, *cfg, a, stream);
+  return c.launched();
+}
+
+// ---- convex centroidal MPC of the foot forces (include/wbc_sim.h: wbc_sim_centroidal_mpc) ------------------------------------------------
+// The host side; the kernel is in wbc_mpc_kernel.hip, its argument structs in wbc_mpc.h. Workspace: wbc_centroidal_kernel's com [N,9] and
+// inertia [N,7] rows.
+extern "C" size_t wbc_sim_centroidal_mpc_workspace_floats(int num_envs) {
+  return num_envs > 0 ? (size_t)num_envs * (MPC_CM_COM + MPC_CM_INR) : 0;
+}
+
+extern "C" int wbc_sim_centroidal_mpc(wbc_sim* s, const wbc_mpc_cfg* cfg, const float* x0, const float* mass, const float* inertia,
+                                      const float* foot_pos, int foot_pos_stages, const uint8_t* contact, const float* x_ref, float* warm,
+                                      int flags, float* forces, float* u, float* x_pred, float* base_acc, float* res, int32_t* status,
+                                      float* workspace, void* stream) {
+  WbCall c("wbc_sim_centroidal_mpc", s, stream);
+  // the arguments first, so that every refusal below can be met (and tested) without a sim; then the sim
+  if (!cfg) return c.fail(-1, "cfg is NULL");
+  if (!contact || !x_ref) return c.fail(-1, "contact or x_ref is NULL");
+  if (flags & ~(WBC_MPC_COLD | WBC_MPC_SHIFT)) return c.fail(-1, "unknown flag bits");
+  if (cfg->horizon < 1 || cfg->horizon > WBC_MPC_MAX_HORIZON) return c.fail(-1, "horizon must be in 1..16");
+  if (cfg->iters < 1 || cfg->iters > 1000) return c.fail(-1, "iters must be in 1..1000");
+  auto positive = [](float v) { return v > 0.f && v <= 3.4e38f; };
+  auto nonneg = [](float v) { return v >= 0.f && v <= 3.4e38f; };
+  if (!positive(cfg->dt) || !positive(cfg->rho) || !positive(cfg->mu) || !positive(cfg->tol))
+    return c.fail(-1, "dt, rho, mu and tol must be finite and > 0");
+  for (int j = 0; j < 3; ++j)
+    if (!positive(cfg->r[j])) return c.fail(-1, "every r must be finite and > 0");
+  for (int j = 0; j < MPC_NX; ++j)
+    if (!nonneg(cfg->q[j])) return c.fail(-1, "every q must be finite and >= 0");
+  if (!nonneg(cfg->fz_min)) return c.fail(-1, "fz_min must be finite and >= 0");
+  if (!(cfg->fz_max >= cfg->fz_min && cfg->fz_max <= 3.4e38f)) return c.fail(-1, "fz_max must be finite and >= fz_min");
+  if (foot_pos_stages != 1 && foot_pos_stages != cfg->horizon) return c.fail(-1, "foot_pos_stages must be 1 or the horizon");
+  if (((uintptr_t)x0 | (uintptr_t)mass | (uintptr_t)inertia | (uintptr_t)foot_pos | (uintptr_t)x_ref | (uintptr_t)warm | (uintptr_t)forces |
+       (uintptr_t)u | (uintptr_t)x_pred | (uintptr_t)base_acc | (uintptr_t)res | (uintptr_t)status | (uintptr_t)workspace) & 3u)
+    return c.fail(-1, "every float or int32 pointer must be 4-byte aligned");
+  const bool centroidal = !x0 || !mass || !inertia;
+  if (centroidal && !workspace) return c.fail(-1, "workspace is NULL while x0, mass or inertia is NULL");
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  const wbc_model& m = c.hc->model;
+  MpcConst K;
+  if (tree_walk_fill(m, K) != 0 || !tree_rigid_ok(m)) return c.no_tree();
+  for (int f = 0; f < WBC_NFEET; ++f) {
+    const int rb = m.feet_rb[f];
+    if (rb < 0 || rb >= WBC_NRB) return c.no_tree();
+    K.foot_body[f] = m.rb_body[rb];
+    for (int j = 0; j < 3; ++j) K.foot_off[f][j] = m.rb_offset[rb][j];
+  }
+  for (int j = 0; j < 3; ++j) K.gravity[j] = c.hc->cfg.gravity[j];
+  if (c.n <= 0) return 0;
+  float *com = nullptr, *inr = nullptr;
+  if (centroidal) {
+    TreeConst T;
+    if (tree_const_fill(m, T) != 0) return c.no_tree();
+    com = workspace;
+    inr = workspace + (size_t)c.n * MPC_CM_COM;
+    hipLaunchKernelGGL(wbc_centroidal_kernel, dim3((c.n + CM_EPW - 1) / CM_EPW), dim3(64), 0, (hipStream_t)stream, T, c.root, c.dofs, c.bp,
+                       (const float*)nullptr, c.n, com, (float*)nullptr, (float*)nullptr, inr);
+  }
+  const MpcArgs a = {c.root, c.dofs, com, inr, x0, mass, inertia, foot_pos, x_ref, contact, warm, forces, u, x_pred, base_acc, res, status,
+                     foot_pos_stages, flags, c.n};
+  wbc_mpc_launch(K, *cfg, a, stream);
   return c.launched();
 }

@@ -123,6 +123,18 @@ class WbcEstimatorCfg(C.Structure):
                                           "p0_p", "p0_v", "p0_f")]
 
 
+MPC_COLD, MPC_SHIFT = 1, 2   # WBC_MPC_COLD, WBC_MPC_SHIFT (wbc_sim_centroidal_mpc's own flags word)
+MPC_STATUS_OK, MPC_STATUS_ITERATIONS, MPC_STATUS_FAILED = 0, 1, 2   # WBC_MPC_STATUS_*
+MPC_MAX_HORIZON = 16       # WBC_MPC_MAX_HORIZON
+MPC_NX, MPC_NU, MPC_NZ = 12, 12, 20   # (theta, p, omega, v); four foot forces; five cone rows per foot
+
+
+class WbcMpcCfg(C.Structure):
+    """wbc_mpc_cfg (include/wbc_sim.h): the host scalars of wbc_sim_centroidal_mpc."""
+    _fields_ = [("horizon", C.c_int32), ("iters", C.c_int32)] + [(name, f32) for name in ("dt", "rho", "mu", "fz_min", "fz_max")] + [
+        ("q", f32 * 12), ("r", f32 * 3), ("tol", f32)]
+
+
 class WbcTaskQpLimits(C.Structure):
     """wbc_taskqp_limits (include/wbc_sim.h): the host scalars of wbc_sim_task_inverse_dynamics_qp; max_iter 0 = the default."""
     _fields_ = [("mu", f32), ("fn_min", f32), ("max_iter", i32)]

@@ -786,6 +786,12 @@ class WidowGo1(LeggedRobot):
         counterpart of what the policy has to infer: see BaseStateEstimator (cfg: its noise parameters and dt, default env.dt)."""
         return BaseStateEstimator(self, **cfg)
 
+    # ---- force planning (no counterpart in the reference): include/wbc_sim.h: wbc_sim_centroidal_mpc ----
+    def centroidal_mpc(self, horizon: int = 10, dt: float = None, **cfg) -> "CentroidalMPC":
+        """The convex model-predictive controller of the foot forces on the single-rigid-body model, the layer that produces the
+        base_acc whole_body_controller takes: see CentroidalMPC (cfg: the fields of wbc_mpc_cfg; dt None: env.dt)."""
+        return CentroidalMPC(self, horizon, dt, **cfg)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])
@@ -1127,3 +1133,130 @@ class BaseStateEstimator:
             foot_height = self._plane_height
         self._launch(contact, reset_mask=env.reset_buf.to(torch.int32), accel=accel, quat=quat, gyro=gyro, dof=dof, foot_height=foot_height)
         return self.base_lin_vel
+
+
+def trot_schedule(phase: torch.Tensor, period: float, duty: float, horizon: int, dt: float) -> torch.Tensor:
+    """u8 [N, horizon, 4]: the contact schedule of a diagonal-pair trot for wbc_sim_centroidal_mpc. phase f32 [N] in [0, 1) is where
+    each env's gait cycle of `period` seconds stands now; feet 0 and 3 (one diagonal, in feet_indices order) are in stance while the
+    cycle's fraction is below `duty`, feet 1 and 2 half a cycle later. Stage k is judged at its middle, (k + 1/2) dt. Torch ops only."""
+    k = torch.arange(horizon, dtype=torch.float32, device=phase.device)
+    frac = phase.to(torch.float32).unsqueeze(1) + (k + 0.5).unsqueeze(0) * (float(dt) / float(period))           # [N, H]
+    first = torch.remainder(frac, 1.0) < float(duty)
+    second = torch.remainder(frac + 0.5, 1.0) < float(duty)
+    return torch.stack([first, second, second, first], dim=-1).to(torch.uint8).contiguous()
+
+
+class CentroidalMPC:
+    """The convex MPC of wbc_sim_centroidal_mpc for every env: it owns the cfg and the warm-start buffer (z and y of the ADMM
+    iteration) and runs one launch per solve(). Keyword arguments are the fields of wbc_mpc_cfg (include/wbc_sim.h); q takes 12 and r
+    takes 3 numbers. Not covered: terrain normals other than world z, a friction coefficient per env, the gyroscopic term, foothold
+    optimisation, a force-reference term in the whole-body QP (whole_body_controller takes base_acc, not the forces)."""
+
+    DEFAULTS = dict(iters=40, rho=2.5e-6, mu=0.5, fz_min=0.0, fz_max=250.0,
+                    q=(25.0, 25.0, 10.0, 2.0, 2.0, 50.0, 0.0, 0.0, 0.3, 0.2, 0.2, 0.1), r=(1e-6, 1e-6, 1e-6), tol=1e-2)
+
+    def __init__(self, env, horizon: int = 10, dt: float = None, **cfg):
+        unknown = set(cfg) - set(self.DEFAULTS)
+        assert not unknown, f"unknown MPC parameters: {sorted(unknown)}"
+        v = dict(self.DEFAULTS, **cfg)
+        self.env = env
+        self.cfg = abi.WbcMpcCfg(int(horizon), int(v["iters"]), float(env.dt if dt is None else dt), float(v["rho"]), float(v["mu"]),
+                                 float(v["fz_min"]), float(v["fz_max"]), (abi.f32 * 12)(*[float(t) for t in v["q"]]),
+                                 (abi.f32 * 3)(*[float(t) for t in v["r"]]), float(v["tol"]))
+        n, dev, H = env.num_envs, env.device, int(horizon)
+        z = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)
+        self.warm = z(n, 2, H, abi.MPC_NZ)
+        self.forces, self.u, self.predicted, self.base_acc, self.residuals = z(n, 4, 3), z(n, H, 12), z(n, H, 12), z(n, 6), z(n, 2)
+        self.status = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self.x_ref = z(n, H, 12)
+        self._com = z(n, 9)
+        self._workspace = z(int(env.sim.L.wbc_sim_centroidal_mpc_workspace_floats(n)))
+        self._started = False
+        self.last_inputs = None
+
+    def reset(self, env_ids=None) -> None:
+        """Forget the warm start of every env (env_ids None) or of the listed ones: their next solve starts from zeros."""
+        if env_ids is None:
+            self.warm.zero_()
+            self._started = False
+        else:
+            self.warm[torch.as_tensor(env_ids, dtype=torch.long, device=self.env.device)] = 0.0
+
+    def reference(self, p0: torch.Tensor, yaw: torch.Tensor, vel_cmd=None, yaw_rate=None, height=None) -> torch.Tensor:
+        """x_ref f32 [N, H, 12] for stages 1..H from the centre of mass p0 [N, 3] and the heading yaw [N] now: the planar velocity
+        vel_cmd [N, 2] (heading frame; None: 0) turned to world axes, the yaw rate [N] (None: 0) about z and the height [N] or a float
+        (None: the current one) of the centre of mass; theta is relative to the heading at the call, so its reference is
+        (0, 0, yaw_rate k dt)."""
+        n, dev, H, dt = self.env.num_envs, self.env.device, int(self.cfg.horizon), float(self.cfg.dt)
+        t = torch.arange(1, H + 1, dtype=torch.float32, device=dev) * dt                                      # [H]
+        vc = torch.zeros((n, 2), dtype=torch.float32, device=dev) if vel_cmd is None else vel_cmd.to(torch.float32)
+        wz = torch.zeros((n,), dtype=torch.float32, device=dev) if yaw_rate is None else yaw_rate.to(torch.float32)
+        c, s = torch.cos(yaw), torch.sin(yaw)
+        vw = torch.stack([c * vc[:, 0] - s * vc[:, 1], s * vc[:, 0] + c * vc[:, 1]], dim=-1)                  # [N, 2]
+        x = self.x_ref
+        x.zero_()
+        x[:, :, 2] = wz[:, None] * t[None]
+        x[:, :, 3:5] = p0[:, None, 0:2] + vw[:, None] * t[None, :, None]
+        x[:, :, 5] = p0[:, None, 2] if height is None else torch.as_tensor(height, dtype=torch.float32, device=dev).expand(n)[:, None]
+        x[:, :, 8] = wz[:, None]
+        x[:, :, 9:11] = vw[:, None]
+        return x
+
+    def solve(self, contact_schedule: torch.Tensor, vel_cmd=None, yaw_rate=None, height=None, x_ref=None, foot_positions=None,
+              state=None, shift: bool = False) -> torch.Tensor:
+        """One MPC launch at the sim's current state; returns forces [N, 4, 3]. contact_schedule u8 (or bool) [N, H, 4], e.g.
+        trot_schedule(...). The reference is x_ref [N, H, 12] if given, else reference(...) from vel_cmd, yaw_rate and height (torch
+        ops and one wbc_sim_centroidal launch for the centre of mass). state: None for the sim's own state; a BaseStateEstimator, whose
+        position and velocity of the trunk's origin replace the sim's (the centre of mass's offset and relative velocity, the
+        orientation and the angular velocity stay the sim's) and whose foot_positions are used unless foot_positions is given; or an
+        x0 tensor [N, 12]. foot_positions [N, 4, 3] or [N, H, 4, 3] (world), None: the feet's current origins. The first solve
+        after a reset() is cold; later ones start from the last z and y, shifted by one stage with shift=True (one solve per
+        stage length). Results: .forces, .base_acc (for whole_body_controller(base_acc=...)), .u, .predicted, .residuals, .status."""
+        env = self.env
+        n, H = env.num_envs, int(self.cfg.horizon)
+        contact = contact_schedule.to(torch.uint8).contiguous()
+        x0 = None
+        if isinstance(state, BaseStateEstimator):
+            env.sim.centroidal(com=self._com)
+            root = env.root_states
+            yaw = self._yaw(env.base_quat)
+            x0 = torch.cat([self._heading_rotvec(env.base_quat, yaw), state.position + self._com[:, 0:3], root[:, 10:13],
+                            state.velocity + (self._com[:, 3:6] - root[:, 7:10])], dim=-1).contiguous()
+            if foot_positions is None:
+                foot_positions = state.foot_positions
+        elif state is not None:
+            x0 = state.to(torch.float32).contiguous()
+        if x_ref is None:
+            if x0 is None:
+                env.sim.centroidal(com=self._com)
+                p0, yaw = env.root_states[:, 0:3] + self._com[:, 0:3], self._yaw(env.base_quat)
+            else:
+                p0, yaw = x0[:, 3:6], self._yaw(env.base_quat)
+            x_ref = self.reference(p0, yaw, vel_cmd, yaw_rate, height)
+        x_ref = x_ref.to(torch.float32).contiguous()
+        fp = None
+        if foot_positions is not None:
+            fp = foot_positions.to(torch.float32).reshape(n, -1, 4, 3).contiguous()
+        self.last_inputs = dict(contact=contact, x_ref=x_ref, x0=x0, foot_pos=fp, cold=not self._started, shift=bool(shift and self._started))
+        env.sim.centroidal_mpc(self.cfg, contact, x_ref, x0=x0, foot_pos=fp, warm=self.warm, cold=not self._started,
+                               shift=bool(shift and self._started), forces=self.forces, u=self.u, x_pred=self.predicted,
+                               base_acc=self.base_acc, res=self.residuals, status=self.status, workspace=self._workspace)
+        self._started = True
+        return self.forces
+
+    @staticmethod
+    def _yaw(q: torch.Tensor) -> torch.Tensor:
+        """The yaw of R(q)'s x axis, q xyzw [N, 4]."""
+        x, y, z, w = q.unbind(-1)
+        return torch.atan2(2 * (x * y + w * z), 1 - 2 * (y * y + z * z))
+
+    @staticmethod
+    def _heading_rotvec(q: torch.Tensor, yaw: torch.Tensor) -> torch.Tensor:
+        """log(R(q) Rz(yaw)^T) as a rotation vector: q times the conjugate of the yaw quaternion, then the quaternion's logarithm."""
+        h = 0.5 * yaw
+        qz = torch.stack([torch.zeros_like(h), torch.zeros_like(h), -torch.sin(h), torch.cos(h)], dim=-1)
+        qr = _quat_mul(q, qz)
+        qr = qr * torch.where(qr[:, 3:] < 0, -1.0, 1.0)
+        sn = qr[:, :3].norm(dim=-1, keepdim=True)
+        ang = 2 * torch.atan2(sn, qr[:, 3:])
+        return qr[:, :3] * torch.where(sn > 1e-6, ang / sn.clamp_min(1e-12), torch.full_like(sn, 2.0))

@@ -616,6 +616,45 @@ class WbcSim:
                                           ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), self._stream()), "wbc_sim_leg_odometry")
         return tuple(t for t in [x, P] + outs if t is not None)
 
+    # ---- convex centroidal MPC of the foot forces (include/wbc_sim.h: wbc_sim_centroidal_mpc) ----------------------------------------------
+    def centroidal_mpc(self, cfg: "abi.WbcMpcCfg", contact: torch.Tensor, x_ref: torch.Tensor, x0: Optional[torch.Tensor] = None,
+                       mass: Optional[torch.Tensor] = None, inertia: Optional[torch.Tensor] = None, foot_pos: Optional[torch.Tensor] = None,
+                       warm: Optional[torch.Tensor] = None, cold: bool = False, shift: bool = False, forces: Optional[torch.Tensor] = None,
+                       u: Optional[torch.Tensor] = None, x_pred: Optional[torch.Tensor] = None, base_acc: Optional[torch.Tensor] = None,
+                       res: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+        """One wbc_sim_centroidal_mpc launch on the current stream (two when x0, mass or inertia is None: wbc_centroidal_kernel fills the
+        workspace first). contact u8 [N, H, 4] and x_ref f32 [N, H, 12] (stages 1..H) with H = cfg.horizon; x0 [N, 12], mass [N],
+        inertia [N, 3, 3], foot_pos [N, 1 or H, 4, 3], None: the sim's current state; warm f32 [N, 2, H, 20] (z then y) is read and
+        written unless cold (None: a cold start, nothing kept); shift moves it one stage to the left first. Returns the tensors it
+        filled, in the order (forces [N, 4, 3], u [N, H, 12], x_pred [N, H, 12], base_acc [N, 6], res [N, 2], status int32 [N]); with
+        none of them passed all six are allocated. workspace: f32 of wbc_sim_centroidal_mpc_workspace_floats(N) floats, allocated here
+        when it is needed and not passed."""
+        n, H = self.num_envs, int(cfg.horizon)
+        f32, i32 = torch.float32, torch.int32
+        shapes = ((n, 4, 3), (n, H, abi.MPC_NU), (n, H, abi.MPC_NX), (n, 6), (n, 2), (n,))
+        outs = [forces, u, x_pred, base_acc, res, status]
+        if all(t is None for t in outs):
+            outs = [torch.empty(sh, dtype=i32 if k == 5 else f32, device=self.device) for k, sh in enumerate(shapes)]
+        stages = int(foot_pos.shape[1]) if foot_pos is not None and foot_pos.dim() == 4 else 1
+        need_ws = x0 is None or mass is None or inertia is None
+        if need_ws and workspace is None:
+            workspace = torch.empty((int(self.L.wbc_sim_centroidal_mpc_workspace_floats(n)),), dtype=f32, device=self.device)
+        for t, sh, dt in [(contact, (n, H, 4), torch.uint8), (x_ref, (n, H, abi.MPC_NX), f32), (x0, (n, abi.MPC_NX), f32), (mass, (n,), f32),
+                          (inertia, (n, 3, 3), f32), (foot_pos, (n, stages, 4, 3), f32), (warm, (n, 2, H, abi.MPC_NZ), f32)] + [
+                              (t, sh, i32 if k == 5 else f32) for k, (t, sh) in enumerate(zip(outs, shapes))]:
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == sh, tuple(t.shape)
+        assert contact is not None and x_ref is not None
+        if workspace is not None:
+            assert workspace.device == self.arena.device and workspace.dtype == f32 and workspace.is_contiguous()
+            assert not need_ws or workspace.numel() >= int(self.L.wbc_sim_centroidal_mpc_workspace_floats(n))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        flags = (abi.MPC_COLD if cold else 0) | (abi.MPC_SHIFT if shift else 0)
+        check(self.L.wbc_sim_centroidal_mpc(self.h, C.byref(cfg), ptr(x0), ptr(mass), ptr(inertia), ptr(foot_pos), stages, ptr(contact),
+                                            ptr(x_ref), ptr(warm), flags, *[ptr(t) for t in outs], ptr(workspace), self._stream()),
+              "wbc_sim_centroidal_mpc")
+        return tuple(t for t in outs if t is not None)
+
     def proximity_damper_rows(self, gap: torch.Tensor, jac: torch.Tensor, d_safe: float, d_influence: float, xi: float, dt: float,
                               nu: Optional[torch.Tensor] = None):
         """The velocity damper of the pairs inside the influence distance as rows on the accelerations, torch ops only: the gap rate

@@ -1023,6 +1023,70 @@ int wbc_sim_leg_odometry(wbc_sim* sim, const wbc_estimator_cfg* cfg, const float
                          const float* contact, const float* foot_height, const int32_t* reset_mask, const float* p_init, int flags,
                          float* x, float* P, float* vel_body, float* nis, int32_t* status, void* stream);
 
+/* Convex model-predictive control of the foot forces on the single-rigid-body model (Di Carlo et al., IROS 2018), the layer that hands
+ * base_acc to the whole-body controller: one QP per env, one launch (wbc_centroidal_mpc_kernel) with a fixed iteration count, so that it
+ * takes the same time for every env and replays under graph capture. The sim's state is read, never written.
+ * PROBLEM per env, world axes, H = cfg->horizon stages of cfg->dt:
+ *   x = (theta, p, omega, v) in R^12: theta = log(R Rz(psi)^T) the rotation vector from the heading frame to the trunk (psi the yaw of R's
+ *       x axis at the call), p and v the centre of mass and its velocity, omega the angular velocity;
+ *   u_k = (f_1 .. f_4) in R^12, the forces on the four feet (feet_rb order), constant over stage k = 0 .. H-1;
+ *   x_{k+1} = A x_k + B_k u_k + d: A = I + dt (theta <- omega, p <- v), d = (0, dt^2/2 g, 0, dt g), foot i's block of B_k with
+ *       W = I_G^-1 [r_ki]x: rows theta, p, omega, v = dt^2/2 W, dt^2/(2m) 1, dt W, dt/m 1 where contact[k][i] != 0 and zero elsewhere
+ *       (the exact zero-order hold of the time-varying linear model without the gyroscopic term); r_ki = foot_pos_ki - pbar_k, pbar_0 = p
+ *       of x0, pbar_k = the position part of x_ref_k for k >= 1;
+ *   cost  sum_{k=1..H} 1/2 (x_k - x_ref_k)^T diag(q) (x_k - x_ref_k) + sum_{k=0..H-1} 1/2 u_k^T diag(r, r, r, r) u_k;
+ *   for every stance foot five rows lo <= C f <= hi: C = [[-1,0,mu],[1,0,mu],[0,-1,mu],[0,1,mu],[0,0,1]], lo = (0,0,0,0,fz_min),
+ *       hi = (inf,inf,inf,inf,fz_max); a swing foot's force is exactly 0.
+ * ALGORITHM (the kernel and tests/mpc_reference.py implement exactly this): ADMM on z = C u (20 rows per stage), scaled dual y.
+ *   Factor once per call: Rt = diag(r ..) + rho C^T C (diagonal: (2, 2, 4 mu^2 + 1) per foot); P_H = Q; for k = H-1 .. 0:
+ *       G_k = Rt + B_k^T P_{k+1} B_k = L L^T, K_k = G_k^-1 B_k^T P_{k+1} A and G_k^-1 itself by substitution on [B_k^T P_{k+1} A | 1],
+ *       P_k = Q_k + A^T P_{k+1} (A - B_k K_k) symmetrised (Q_0 = 0), and P_{k+1} d is kept.
+ *   Iterate cfg->iters times, no early exit:
+ *     1. rt_k = -rho C^T (z_k - y_k);
+ *     2. backward from p_H = -Q x_ref_H: s = p_{k+1} + P_{k+1} d, v = B_k^T s + rt_k, kappa_k = G_k^-1 v, p_k = -Q_k x_ref_k + A^T s - K_k^T v;
+ *     3. forward: u_k = -K_k x_k - kappa_k, x_{k+1} = A x_k + B_k u_k + d;
+ *     4. z_k <- clip(C u_k + y_k, lo, hi), y_k <- y_k + C u_k - z_k; the rows of swing feet are held at 0.
+ *   After the last iteration res = (max |C u - z| over stance rows, rho max |C^T (z - z_prev)|); forces = stage 0's u with f_z clipped to
+ *   [fz_min, fz_max] and then f_x, f_y to +-mu f_z (always feasible, u_0 where the residual is 0; a swing foot's is 0).
+ * INPUTS (device; every float pointer f32, 4-byte alignment):
+ *   contact  u8 [N,H,4], required;   x_ref  [N,H,12], stages 1 .. H, required;
+ *   x0       [N,12] or NULL: p = root position + wbc_sim_centroidal's offset, v = v_com, omega = the root's world angular velocity, theta as above;
+ *   mass [N], inertia [N,3,3] (world axes, about the centre of mass) or NULL: what wbc_sim_centroidal produces. When x0, mass or inertia
+ *       is NULL the entry point launches wbc_centroidal_kernel into workspace (wbc_sim_centroidal_mpc_workspace_floats(N) floats) first;
+ *   foot_pos [N,S,4,3], S = foot_pos_stages in {1, H} (1: one set for every stage), or NULL: the current origins of the four feet;
+ *   warm     [N,2,H,20] or NULL: z then y, read and written. WBC_MPC_COLD starts from zeros (implied by NULL), WBC_MPC_SHIFT shifts both
+ *       left by one stage and repeats the last before starting.
+ * OUTPUTS, each may be NULL; what is written never depends on which are asked for: forces [N,4,3], u [N,H,12], x_pred [N,H,12]
+ *   (x_1 .. x_H), base_acc [N,6] = (sum forces / m + g ; I_G^-1 sum r_0i x forces_i), linear then angular, world axes (what
+ *   wbc_sim_task_inverse_dynamics_qp's base task takes), res [N,2], status int32 [N]: WBC_MPC_STATUS_OK both residuals <= cfg->tol,
+ *   WBC_MPC_STATUS_ITERATIONS the iterate after cfg->iters iterations is above it (the outputs are the iterate's), WBC_MPC_STATUS_FAILED an input
+ *   of that env is not finite, m or det I_G is not positive or a pivot failed: every float output of the env and its warm entries are 0.
+ * Nothing is allocated, nothing synchronises. -1 with a message in wbc_last_error() that names the entry point, nothing written, checked
+ * BEFORE the sim: NULL cfg, contact or x_ref; unknown flag bits; horizon outside 1..WBC_MPC_MAX_HORIZON or iters outside 1..1000; dt, rho, mu,
+ * an r entry or tol not finite and > 0; a q entry not finite or < 0; fz_min not finite or < 0; fz_max not finite or < fz_min;
+ * foot_pos_stages other than 1 or H; a misaligned pointer; NULL workspace when x0, mass or inertia is NULL. Then NULL sim; -3 / -2 and
+ * stream handling as wbc_sim_coriolis. Not covered: terrain normals other than world z, per-env mu, the gyroscopic term, foothold
+ * optimisation. */
+#define WBC_MPC_MAX_HORIZON 16
+typedef struct {
+  int32_t horizon;                           /* H, 1..16 */
+  int32_t iters;                             /* 1..1000 */
+  float dt, rho, mu, fz_min, fz_max;
+  float q[12];                               /* >= 0 */
+  float r[3];                                /* > 0 */
+  float tol;                                 /* > 0: status only */
+} wbc_mpc_cfg;
+#define WBC_MPC_COLD 1
+#define WBC_MPC_SHIFT 2
+#define WBC_MPC_STATUS_OK 0
+#define WBC_MPC_STATUS_ITERATIONS 1
+#define WBC_MPC_STATUS_FAILED 2
+int wbc_sim_centroidal_mpc(wbc_sim* sim, const wbc_mpc_cfg* cfg, const float* x0, const float* mass, const float* inertia,
+                           const float* foot_pos, int foot_pos_stages, const uint8_t* contact, const float* x_ref, float* warm, int flags,
+                           float* forces, float* u, float* x_pred, float* base_acc, float* res, int32_t* status, float* workspace,
+                           void* stream);
+size_t wbc_sim_centroidal_mpc_workspace_floats(int num_envs);
+
 /* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and
  * of nudot(q, nu, tau) in the coordinates of wbc_sim_body_dynamics, from the sim's current root / DoF state, WBC_T_BODY_PARAMS and all
  * three gravity components. The sim's state is read, never written.
