@@ -14,6 +14,7 @@
 #include "wbc_tree.h"
 #include "wbc_proximity.h"
 #include "wbc_estimator.h"
+#include "wbc_footstep.h"
 #include "wbc_mpc.h"
 
 #define ARM_N 6
@@ -4434,5 +4435,66 @@ extern "C" int wbc_sim_centroidal_mpc(wbc_sim* s, const wbc_mpc_cfg* cfg, const 
   const MpcArgs a = {c.root, c.dofs, com, inr, x0, mass, inertia, foot_pos, x_ref, contact, warm, forces, u, x_pred, base_acc, res, status,
                      foot_pos_stages, flags, c.n};
   wbc_mpc_launch(K, *cfg, a, stream);
+  return c.launched();
+}
+
+// ---- gait clock, footholds and swing references (include/wbc_sim.h: wbc_sim_footstep_plan) -------------------------------------------------
+// The host side; the kernel is in wbc_footstep_kernel.hip, its argument structs in wbc_footstep.h.
+extern "C" int wbc_sim_footstep_plan(wbc_sim* s, const wbc_footstep_cfg* cfg, const float* base_pos, const float* base_vel, const float* quat,
+                                     const float* dof, const float* vel_cmd, const float* yaw_rate, const int32_t* reset_mask,
+                                     const float* phase_init, int flags, float* state, uint8_t* stance, float* contact, uint8_t* schedule,
+                                     float* foot_pos, float* foothold, float* swing_ref, float* swing_acc, int32_t* info, void* stream) {
+  WbCall c("wbc_sim_footstep_plan", s, stream);
+  // the arguments first, so that every refusal below can be met (and tested) without a sim; then the sim
+  if (!cfg) return c.fail(-1, "cfg is NULL");
+  if (!state) return c.fail(-1, "state is NULL");
+  if (flags & ~(WBC_FOOTSTEP_RESET | WBC_FOOTSTEP_HOLD)) return c.fail(-1, "unknown flag bits");
+  auto positive = [](float v) { return v > 0.f && v <= 3.4e38f; };
+  auto nonneg = [](float v) { return v >= 0.f && v <= 3.4e38f; };
+  if (cfg->horizon < 0 || cfg->horizon > WBC_MPC_MAX_HORIZON) return c.fail(-1, "horizon must be in 0..16");
+  if (cfg->search_radius < 0 || cfg->search_radius > WBC_FOOTSTEP_MAX_RADIUS) return c.fail(-1, "search_radius must be in 0..3");
+  if (!positive(cfg->dt) || !positive(cfg->period) || (cfg->horizon > 0 && !positive(cfg->mpc_dt)))
+    return c.fail(-1, "dt, period and mpc_dt must be finite and > 0");
+  if (!positive(cfg->search_step) || !positive(cfg->probe_radius)) return c.fail(-1, "search_step and probe_radius must be finite and > 0");
+  if (!positive(cfg->duty)) return c.fail(-1, "duty must be finite and > 0");
+  for (int f = 0; f < WBC_NFEET; ++f) {
+    if (!(cfg->offset[f] >= 0.f && cfg->offset[f] < 1.f)) return c.fail(-1, "every offset must be in [0, 1)");
+    if (!(fabsf(cfg->stance_offset[f][0]) <= 3.4e38f && fabsf(cfg->stance_offset[f][1]) <= 3.4e38f))
+      return c.fail(-1, "every stance_offset must be finite");
+  }
+  if (!nonneg(cfg->k_v) || !nonneg(cfg->kp) || !nonneg(cfg->kd)) return c.fail(-1, "the gains k_v, kp and kd must be finite and >= 0");
+  if (!nonneg(cfg->com_height) || !nonneg(cfg->swing_height)) return c.fail(-1, "the heights com_height and swing_height must be finite and >= 0");
+  if (!nonneg(cfg->max_reach)) return c.fail(-1, "max_reach must be finite and >= 0");
+  if (!nonneg(cfg->w_dist) || !nonneg(cfg->w_rough) || !nonneg(cfg->w_slope)) return c.fail(-1, "every weight must be finite and >= 0");
+  if (!nonneg(cfg->rough_max) || !nonneg(cfg->nz_min)) return c.fail(-1, "the thresholds rough_max and nz_min must be finite and >= 0");
+  if (!(cfg->latch >= 0.f && cfg->latch <= 1.f)) return c.fail(-1, "latch must be in [0, 1]");
+  if (((uintptr_t)base_pos | (uintptr_t)base_vel | (uintptr_t)quat | (uintptr_t)dof | (uintptr_t)vel_cmd | (uintptr_t)yaw_rate |
+       (uintptr_t)reset_mask | (uintptr_t)phase_init | (uintptr_t)state | (uintptr_t)contact | (uintptr_t)foot_pos | (uintptr_t)foothold |
+       (uintptr_t)swing_ref | (uintptr_t)swing_acc | (uintptr_t)info) & 3u)
+    return c.fail(-1, "every float or int32 pointer must be 4-byte aligned");
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  const wbc_model& m = c.hc->model;
+  FsConst K;
+  if (tree_walk_fill(m, K) != 0 || !tree_rigid_ok(m)) return c.no_tree();
+  for (int f = 0; f < WBC_NFEET; ++f) {
+    const int rb = m.feet_rb[f];
+    if (rb < 0 || rb >= WBC_NRB) return c.no_tree();
+    K.foot_body[f] = m.rb_body[rb];
+    for (int j = 0; j < 3; ++j) K.foot_off[f][j] = m.rb_offset[rb][j];
+  }
+  double g2 = 0.0;
+  for (int j = 0; j < 3; ++j) { K.gravity[j] = c.hc->cfg.gravity[j]; g2 += (double)K.gravity[j] * K.gravity[j]; }
+  K.k_c = g2 > 0.0 ? (float)(0.5 * sqrt((double)cfg->com_height / sqrt(g2))) : 0.f;
+  K.hf = c.hc->hf; K.hf_rows = c.hc->hf_rows; K.hf_cols = c.hc->hf_cols; K.hf_hs = c.hc->hf_hs; K.hf_vs = c.hc->hf_vs;
+  for (int j = 0; j < 3; ++j) K.hf_t[j] = c.hc->hf_t[j];
+  K.ground_z = c.hc->cfg.ground_z;
+  if (K.hf && (K.hf_rows < 2 || K.hf_cols < 2)) return c.fail(-3, "the heightfield has fewer than 2 x 2 samples");
+  if (c.n <= 0) return 0;
+  const FsArgs a = {c.root, dof ? dof : c.dofs, base_pos ? base_pos : c.root, base_vel ? base_vel : c.root + 7, quat ? quat : c.root + 3,
+                    vel_cmd, yaw_rate, phase_init, reset_mask, base_pos ? 3 : 26, base_vel ? 3 : 26, quat ? 4 : 26,
+                    (flags & WBC_FOOTSTEP_RESET) ? 1 : 0, (flags & WBC_FOOTSTEP_HOLD) ? 1 : 0, c.n, state, stance, schedule, contact, foot_pos,
+                    foothold, swing_ref, swing_acc, info};
+  wbc_footstep_launch(K, *cfg, a, stream);
   return c.launched();
 }

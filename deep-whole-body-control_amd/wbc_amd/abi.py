@@ -135,6 +135,20 @@ class WbcMpcCfg(C.Structure):
         ("q", f32 * 12), ("r", f32 * 3), ("tol", f32)]
 
 
+FOOTSTEP_NS = 32           # WBC_FOOTSTEP_NS: floats of planner state per env
+FOOTSTEP_MAX_RADIUS = 3    # WBC_FOOTSTEP_MAX_RADIUS
+FOOTSTEP_RESET, FOOTSTEP_HOLD = 1, 2   # WBC_FOOTSTEP_RESET / _HOLD (wbc_sim_footstep_plan's own flags word)
+FOOTSTEP_INFO_RESET, FOOTSTEP_INFO_FAILED, FOOTSTEP_INFO_NO_SAFE, FOOTSTEP_INFO_LIFT = 1, 2, 16, 256   # the last two << foot
+
+
+class WbcFootstepCfg(C.Structure):
+    """wbc_footstep_cfg (include/wbc_sim.h): the host scalars of wbc_sim_footstep_plan."""
+    _fields_ = [("dt", f32), ("period", f32), ("duty", f32), ("offset", f32 * 4), ("horizon", C.c_int32), ("mpc_dt", f32),
+                ("stance_offset", (f32 * 2) * 4)] + [(name, f32) for name in ("k_v", "com_height", "max_reach", "swing_height", "latch",
+                                                                             "kp", "kd")] + [("search_radius", C.c_int32)] + [
+        (name, f32) for name in ("search_step", "probe_radius", "w_dist", "w_rough", "w_slope", "rough_max", "nz_min")]
+
+
 class WbcTaskQpLimits(C.Structure):
     """wbc_taskqp_limits (include/wbc_sim.h): the host scalars of wbc_sim_task_inverse_dynamics_qp; max_iter 0 = the default."""
     _fields_ = [("mu", f32), ("fn_min", f32), ("max_iter", i32)]

@@ -792,6 +792,13 @@ class WidowGo1(LeggedRobot):
         base_acc whole_body_controller takes: see CentroidalMPC (cfg: the fields of wbc_mpc_cfg; dt None: env.dt)."""
         return CentroidalMPC(self, horizon, dt, **cfg)
 
+    # ---- gait layer (no counterpart in the reference): include/wbc_sim.h: wbc_sim_footstep_plan ----
+    def gait_planner(self, gait="trot", period: float = 0.5, duty: float = 0.5, horizon: int = 10, mpc_dt: float = None, **cfg) -> "FootstepPlanner":
+        """The gait clock, the terrain-aware footholds and the swing-foot references that tie base_state_estimator, centroidal_mpc and
+        whole_body_controller into a controller: see FootstepPlanner (gait: stand, trot, pace, bound, walk or four phase offsets; cfg:
+        the other fields of wbc_footstep_cfg; mpc_dt None: env.dt)."""
+        return FootstepPlanner(self, gait, period, duty, horizon, mpc_dt, **cfg)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])
@@ -1260,3 +1267,131 @@ class CentroidalMPC:
         sn = qr[:, :3].norm(dim=-1, keepdim=True)
         ang = 2 * torch.atan2(sn, qr[:, 3:])
         return qr[:, :3] * torch.where(sn > 1e-6, ang / sn.clamp_min(1e-12), torch.full_like(sn, 2.0))
+
+
+class FootstepPlanner:
+    """The gait layer of wbc_sim_footstep_plan for every env: it owns the cfg, the state [N, 32] (phase, and per foot the lift-off
+    position, the target foothold and a swing flag) and every output, and advances them by one launch per update(). gait is a name in
+    GAITS or four phase offsets in feet_indices order (FL, FR, RL, RR); keyword arguments are the other fields of wbc_footstep_cfg
+    (include/wbc_sim.h); dt defaults to env.dt, mpc_dt to env.dt, stance_offset [4, 2] to the feet's xy under the trunk at the default
+    joint angles. The planner starts reset at phase 0. Use it as
+        planner.update(vel_cmd, yaw_rate, state=estimator)
+        mpc.solve(planner.contact_schedule, vel_cmd, yaw_rate, foot_positions=planner.foot_positions, state=estimator)
+        env.whole_body_controller(base_acc=mpc.base_acc, swing_acc=planner.swing_acc, stance=planner.stance)
+    Not covered: early / late contact adaptation, a duty per foot, footholds searched for standing feet, collision of the swing path with
+    the terrain."""
+
+    GAITS = {"stand": (0.0, 0.0, 0.0, 0.0), "trot": (0.0, 0.5, 0.5, 0.0), "pace": (0.0, 0.5, 0.0, 0.5), "bound": (0.0, 0.0, 0.5, 0.5),
+             "walk": (0.0, 0.5, 0.75, 0.25)}
+    DEFAULTS = dict(k_v=0.03, com_height=0.3, max_reach=0.25, swing_height=0.08, latch=0.8, kp=400.0, kd=40.0, search_radius=2,
+                    search_step=0.04, probe_radius=0.03, w_dist=1.0, w_rough=10.0, w_slope=0.1, rough_max=0.03, nz_min=0.85)
+
+    def __init__(self, env, gait="trot", period: float = 0.5, duty: float = 0.5, horizon: int = 10, mpc_dt: float = None, dt: float = None,
+                 stance_offset=None, **cfg):
+        unknown = set(cfg) - set(self.DEFAULTS)
+        assert not unknown, f"unknown planner parameters: {sorted(unknown)}"
+        v = dict(self.DEFAULTS, **cfg)
+        self.env = env
+        if isinstance(gait, str):
+            assert gait in self.GAITS, f"gait must be one of {sorted(self.GAITS)} or four offsets"
+            offsets = self.GAITS[gait]
+            if gait == "stand":
+                duty = 1.0
+        else:
+            offsets = tuple(float(o) for o in gait)
+            assert len(offsets) == 4
+        if stance_offset is None:
+            stance_offset = self.default_stance_offset(env)
+        so = [[float(stance_offset[i][j]) for j in range(2)] for i in range(4)]
+        self.cfg = abi.WbcFootstepCfg(float(env.dt if dt is None else dt), float(period), float(duty), (abi.f32 * 4)(*offsets), int(horizon),
+                                      float(env.dt if mpc_dt is None else mpc_dt), ((abi.f32 * 2) * 4)(*[(abi.f32 * 2)(*r) for r in so]),
+                                      float(v["k_v"]), float(v["com_height"]), float(v["max_reach"]), float(v["swing_height"]),
+                                      float(v["latch"]), float(v["kp"]), float(v["kd"]), int(v["search_radius"]), float(v["search_step"]),
+                                      float(v["probe_radius"]), float(v["w_dist"]), float(v["w_rough"]), float(v["w_slope"]),
+                                      float(v["rough_max"]), float(v["nz_min"]))
+        n, dev, H = env.num_envs, env.device, int(horizon)
+        z = lambda *sh, dtype=torch.float32: torch.zeros(sh, dtype=dtype, device=dev)
+        self.state = z(n, abi.FOOTSTEP_NS)
+        self.stance, self.contact = z(n, 4, dtype=torch.uint8), z(n, 4)
+        self.contact_schedule, self.foot_positions = z(n, H, 4, dtype=torch.uint8), z(n, H, 4, 3)
+        self.footholds, self.swing_ref, self.swing_acc = z(n, 4, 3), z(n, 4, 9), z(n, 4, 3)
+        self.info = z(n, dtype=torch.int32)
+        self.reset()
+
+    @staticmethod
+    def default_stance_offset(env):
+        """[4][2]: the xy of the four foot origins relative to the trunk's origin, trunk axes, at the default joint angles (a walk down
+        each leg of the robot model)."""
+        m = env.robot_model
+        q = env.default_dof_pos.detach().cpu().numpy().reshape(-1).astype(np.float64)
+        out = []
+        for rb in [int(i) for i in env.feet_indices.tolist()]:
+            chain, b = [], int(m.rb_body[rb])
+            while b > 0:
+                chain.append(b)
+                b = int(m.parent[b])
+            E, p = np.eye(3), np.zeros(3)
+            for b in chain[::-1]:
+                p = p + E @ np.asarray(m.joint_xyz[b], dtype=np.float64)
+                ax, ang = int(m.axis[b]), q[int(m.body_dof[b])]
+                c, s_ = np.cos(ang), np.sin(ang)
+                Q = np.eye(3)
+                j, k = (ax + 1) % 3, (ax + 2) % 3
+                Q[j, j], Q[j, k], Q[k, j], Q[k, k] = c, -s_, s_, c
+                E = E @ Q
+            p = p + E @ np.asarray(m.rb_offset[rb], dtype=np.float64)
+            out.append([float(p[0]), float(p[1])])
+        return out
+
+    # the outputs under the names their consumers use
+    @property
+    def phase(self) -> torch.Tensor:
+        """f32 [N]: where each env's gait cycle stands (a view of state)."""
+        return self.state[:, 0]
+
+    @property
+    def swing_pos(self) -> torch.Tensor:
+        return self.swing_ref[:, :, 0:3]
+
+    @property
+    def swing_vel(self) -> torch.Tensor:
+        return self.swing_ref[:, :, 3:6]
+
+    @property
+    def swing_acc_ref(self) -> torch.Tensor:
+        """f32 [N, 4, 3]: the reference's own acceleration (swing_acc adds the PD on the tracking error to it)."""
+        return self.swing_ref[:, :, 6:9]
+
+    def _launch(self, **kw):
+        self.env.sim.footstep_plan(self.cfg, self.state, stance=self.stance, contact=self.contact, schedule=self.contact_schedule,
+                                   foot_pos=self.foot_positions, foothold=self.footholds, swing_ref=self.swing_ref, swing_acc=self.swing_acc,
+                                   info=self.info, **kw)
+
+    def reset(self, env_ids=None, phase=None) -> None:
+        """Reset every env (env_ids None) or the listed ones: phase = `phase` (a float or [N]; None: 0), no foot in swing, lift-off and
+        target at the feet's current origins. One launch with the clock held; the other envs' state is left as it is."""
+        env = self.env
+        n, dev = env.num_envs, env.device
+        p0 = None if phase is None else torch.as_tensor(phase, dtype=torch.float32, device=dev).expand(n).contiguous()
+        if env_ids is None:
+            self._launch(reset=True, hold=True, phase_init=p0)
+            return
+        mask = torch.zeros((n,), dtype=torch.int32, device=dev)
+        mask[torch.as_tensor(env_ids, dtype=torch.long, device=dev)] = 1
+        self._launch(reset_mask=mask, hold=True, phase_init=p0)
+
+    def update(self, vel_cmd=None, yaw_rate=None, state=None, hold: bool = False) -> torch.Tensor:
+        """One control step at the sim's current state; returns stance u8 [N, 4]. vel_cmd [N, 2] (heading frame) and yaw_rate [N], None:
+        0. state: None for the sim's own base position and velocity, or a BaseStateEstimator, whose position and velocity replace them
+        (orientation, angular velocity and joints stay the sim's). hold=True leaves the clock where it is. Envs flagged in env.reset_buf
+        are reset at phase 0. Results: .stance, .contact, .contact_schedule, .foot_positions, .footholds, .swing_pos / .swing_vel /
+        .swing_acc_ref, .swing_acc, .info."""
+        env = self.env
+        kw = {}
+        if isinstance(state, BaseStateEstimator):
+            kw = dict(base_pos=state.position.contiguous(), base_vel=state.velocity.contiguous())
+        else:
+            assert state is None, "state is a BaseStateEstimator or None"
+        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        self._launch(vel_cmd=f(vel_cmd), yaw_rate=f(yaw_rate), reset_mask=env.reset_buf.to(torch.int32), hold=hold, **kw)
+        return self.stance

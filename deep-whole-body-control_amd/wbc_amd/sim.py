@@ -655,6 +655,39 @@ class WbcSim:
               "wbc_sim_centroidal_mpc")
         return tuple(t for t in outs if t is not None)
 
+    # ---- gait clock, footholds and swing references (include/wbc_sim.h: wbc_sim_footstep_plan) ------------------------------------------------
+    FOOTSTEP_OUTPUTS = ("stance", "contact", "schedule", "foot_pos", "foothold", "swing_ref", "swing_acc", "info")
+
+    def footstep_plan(self, cfg: "abi.WbcFootstepCfg", state: torch.Tensor, base_pos: Optional[torch.Tensor] = None,
+                      base_vel: Optional[torch.Tensor] = None, quat: Optional[torch.Tensor] = None, dof: Optional[torch.Tensor] = None,
+                      vel_cmd: Optional[torch.Tensor] = None, yaw_rate: Optional[torch.Tensor] = None,
+                      reset_mask: Optional[torch.Tensor] = None, phase_init: Optional[torch.Tensor] = None, reset: bool = False,
+                      hold: bool = False, **outputs) -> None:
+        """One wbc_sim_footstep_plan launch on the current stream: one control step of the gait clock, the footholds and the swing
+        references on the caller-owned state f32 [N, 32], in place. base_pos, base_vel [N, 3], quat [N, 4] (xyzw) and dof [N, 20, 2],
+        None: the sim's current state; vel_cmd [N, 2] (heading frame) and yaw_rate [N], None: 0. reset=True resets every env,
+        reset_mask int32 [N] the envs whose entry is not 0, to the phase phase_init [N] (None: 0); hold=True leaves the clock where it is.
+        Outputs by keyword, each a caller-owned tensor that is filled (FOOTSTEP_OUTPUTS): stance u8 [N, 4], contact [N, 4], schedule u8
+        [N, H, 4], foot_pos [N, H, 4, 3], foothold [N, 4, 3], swing_ref [N, 4, 9], swing_acc [N, 4, 3], info int32 [N]."""
+        n, H = self.num_envs, int(cfg.horizon)
+        unknown = set(outputs) - set(self.FOOTSTEP_OUTPUTS)
+        assert not unknown, f"unknown outputs: {sorted(unknown)}"
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        shapes = dict(stance=((n, 4), u8), contact=((n, 4), f32), schedule=((n, H, 4), u8), foot_pos=((n, H, 4, 3), f32),
+                      foothold=((n, 4, 3), f32), swing_ref=((n, 4, 9), f32), swing_acc=((n, 4, 3), f32), info=((n,), i32))
+        checks = [(state, (n, abi.FOOTSTEP_NS), f32), (base_pos, (n, 3), f32), (base_vel, (n, 3), f32), (quat, (n, 4), f32),
+                  (dof, (n, abi.NDOF, 2), f32), (vel_cmd, (n, 2), f32), (yaw_rate, (n,), f32), (reset_mask, (n,), i32), (phase_init, (n,), f32)]
+        checks += [(outputs.get(k),) + shapes[k] for k in self.FOOTSTEP_OUTPUTS]
+        for t, sh, dt in checks:
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == sh, (tuple(t.shape), sh)
+        assert state is not None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None
+        flags = (abi.FOOTSTEP_RESET if reset else 0) | (abi.FOOTSTEP_HOLD if hold else 0)
+        check(self.L.wbc_sim_footstep_plan(self.h, C.byref(cfg), ptr(base_pos), ptr(base_vel), ptr(quat), ptr(dof), ptr(vel_cmd), ptr(yaw_rate),
+                                           ptr(reset_mask), ptr(phase_init), flags, state.data_ptr(),
+                                           *[ptr(outputs.get(k)) for k in self.FOOTSTEP_OUTPUTS], self._stream()), "wbc_sim_footstep_plan")
+
     def proximity_damper_rows(self, gap: torch.Tensor, jac: torch.Tensor, d_safe: float, d_influence: float, xi: float, dt: float,
                               nu: Optional[torch.Tensor] = None):
         """The velocity damper of the pairs inside the influence distance as rows on the accelerations, torch ops only: the gap rate

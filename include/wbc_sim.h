@@ -1087,6 +1087,88 @@ int wbc_sim_centroidal_mpc(wbc_sim* sim, const wbc_mpc_cfg* cfg, const float* x0
                            void* stream);
 size_t wbc_sim_centroidal_mpc_workspace_floats(int num_envs);
 
+/* One control step of the gait layer that ties the estimator, the MPC and the whole-body controller into a loop: a gait clock that decides
+ * which feet stand, Raibert footholds moved to safe terrain by a search over the heightfield, and minimum-jerk swing-foot references. One
+ * launch (wbc_footstep_plan_kernel); the sim's state is read, never written. Per env the caller owns
+ * state  device f32 [N, WBC_FOOTSTEP_NS = 32], read and written: [0] the phase in [0, 1); [1..3] reserved, written as 0; then per foot
+ *        (feet_rb order FL, FR, RL, RR) seven floats at 4 + 7 i: the lift-off position (3), the target foothold (3), a swing flag (0 or 1).
+ * INPUTS (device f32 unless said otherwise; each may be NULL):
+ * base_pos, base_vel  [N, 3]: position b and velocity v of the trunk's origin, world axes. NULL: ROOT_STATES' (a BaseStateEstimator's
+ *        position / velocity fit here).   quat [N, 4] xyzw, normalised in the call: R (world <- trunk). NULL: ROOT_STATES'.
+ * dof    [N, 20, 2] in the layout of DOF_STATE. NULL: DOF_STATE.   vel_cmd [N, 2]: the commanded planar velocity in the heading frame,
+ *        NULL: 0.   yaw_rate [N]: w_z, NULL: 0.   reset_mask int32 [N].   phase_init [N], NULL: 0.
+ * The foot origins and their velocities come from the leg kinematics of wbc_sim_leg_odometry: r_i = R fk_i(q), rdot_i = R (w_b x fk_i +
+ * J_i qd) with w_b = R^T (ROOT_STATES' world angular velocity): p_i = b + r_i, pd_i = v + rdot_i.
+ * PER ENV, in this order (T_st = duty period, T_sw = (1 - duty) period, frac(x) = x - floor(x)):
+ * 1 RESET (WBC_FOOTSTEP_RESET in flags: every env; otherwise the envs whose reset_mask entry is not 0; the env's state is then not read):
+ *   phase = phase_init, every swing flag 0, lift-off = target = p_i; info bit WBC_FOOTSTEP_INFO_RESET.
+ * 2 CLOCK  phi_i = frac(phase + offset_i). Foot i stands iff duty >= 1 or phi_i < duty; otherwise it swings with the swing fraction
+ *   s_i = (phi_i - duty) / (1 - duty). A foot whose flag is 0 and that swings now lifts off: lift-off <- p_i, flag <- 1 (info bit
+ *   WBC_FOOTSTEP_INFO_LIFT << i). A foot whose flag is 1 and that stands now touches down: flag <- 0, target <- p_i.
+ * 3 NOMINAL FOOTHOLD of the touchdown t seconds from now: t = (1 - s_i) T_sw for a swinging foot, t = (duty - phi_i) period + T_sw for a
+ *   standing one (duty >= 1: t = 0). With (c, s) = (R_00, R_10) / |(R_00, R_10)| the heading psi of R's x axis ((1, 0) where that axis is
+ *   vertical), Rz(psi_t) = Rz(psi) Rz(w_z t),
+ *   v_c = Rz(psi) vel_cmd:   hip = b_xy + v_c t + Rz(psi_t) stance_offset_i,
+ *   add = (T_st / 2) v_xy + k_v (v_xy - v_c) + (1/2) sqrt(com_height / |g|) (v_y w_z, -v_x w_z)     [Raibert; the last term (v x (0, 0, w_z))_xy]
+ *   scaled down to length max_reach where it is longer; nom = hip + add. g is wbc_task_cfg.gravity; with |g| = 0 the last term is left out.
+ * 4 TERRAIN SEARCH, only for a foot that swings now with s_i < latch (a swinging foot past the latch keeps the stored target): the
+ *   candidates c_ab = nom + (a, b) search_step, a, b in [-R, R], index (a + R)(2R + 1) + (b + R). h(x, y) and n(x, y) are the terrain's
+ *   surface height and unit normal exactly as the step kernel's contacts see them (terrain_query: the cell's triangle with u >= v or u < v,
+ *   indices clamped to the grid, the plane z = ground_z without a heightfield). Per candidate rough = the largest of |h(c +- probe_radius
+ *   e_x) - h(c)| and |h(c +- probe_radius e_y) - h(c)|, slope = 1 - n_z(c); it is rejected where rough > rough_max or n_z < nz_min;
+ *   cost = w_dist |c - nom|^2 + w_rough rough^2 + w_slope slope. target = the accepted candidate of least cost (the lowest index on a
+ *   tie) with z = h(c); all rejected: target = (nom, h(nom)) and info bit WBC_FOOTSTEP_INFO_NO_SAFE << i.
+ * 5 SWING REFERENCE of a swinging foot, b(s) = s^3 (10 - 15 s + 6 s^2), sdot = 1 / T_sw: xy = lift + (target - lift) b(s); with the apex
+ *   z_a = max(lift_z, target_z) + swing_height, z = lift_z + (z_a - lift_z) b(2 s) for s < 1/2 and z_a + (target_z - z_a) b(2 s - 1) otherwise;
+ *   velocity and acceleration are the analytic time derivatives (b' sdot, b'' sdot^2; in z with 2 sdot).     [the MIT Cheetah 3 swing shape]
+ * OUTPUTS, each may be NULL and is then not written; what is written never depends on which are asked for; they belong to the phase BEFORE step 6:
+ * stance u8 [N, 4], contact f32 [N, 4] (1.0 / 0.0);   swing_ref [N, 4, 9] = (pos, vel, acc), a standing foot (p_i, 0, 0);
+ * swing_acc [N, 4, 3] = acc + kp (pos - p_i) + kd (vel - pd_i), 0 for a standing foot (what the whole-body calls take as the feet's task);
+ * foothold [N, 4, 3]: a swinging foot's target; a standing foot's (nom, h(nom)) of step 3, one query and no search;
+ * schedule u8 [N, H, 4]: with x_ik = (phase + (k + 1/2) (mpc_dt / period)) + offset_i foot i stands in stage k iff duty >= 1 or
+ *   frac(x_ik) < duty (the fp32 statements of the Python trot_schedule, which trot offsets reproduce);
+ * foot_pos [N, H, 4, 3] (the MPC's foot_pos with foot_pos_stages = H): with m_ik = floor(x_ik) - floor(phase + offset_i) the number of
+ *   lift-offs between now and stage k, a stance stage with m = 0 (or duty >= 1) gets p_i, one with m >= 1 gets foothold_i + (m - 1) period
+ *   (v_c, 0); a swing stage gets the value of the foot's next stance stage in the horizon, failing that of its last one, failing that foothold_i;
+ * info int32 [N]: the bits below.
+ * 6 ADVANCE  phase <- frac(phase + dt / period) unless WBC_FOOTSTEP_HOLD is set.
+ * An env with a non-finite input (b, v, quat, the root's angular velocity, a leg joint's q or qd, vel_cmd, yaw_rate, the state it reads or
+ * its phase_init) writes zeros to every output but info = WBC_FOOTSTEP_INFO_FAILED and leaves its state as it was.
+ * Every pointer needs 4-byte alignment only (the u8 outputs none). Nothing is allocated and nothing synchronises: safe under stream capture.
+ * -1 with a message in wbc_last_error() that names the entry point, nothing written, checked BEFORE the sim: NULL cfg or state; unknown
+ * flag bits; dt, period, mpc_dt (when horizon > 0), search_step or probe_radius not finite and > 0; duty not finite or <= 0; an offset
+ * outside [0, 1); horizon outside 0..WBC_MPC_MAX_HORIZON; search_radius outside 0..WBC_FOOTSTEP_MAX_RADIUS; a stance_offset entry not
+ * finite; k_v, com_height, max_reach, swing_height, kp, kd, w_dist, w_rough, w_slope, rough_max or nz_min not finite or < 0; latch outside
+ * [0, 1]; a misaligned pointer. Then NULL sim; -3 / -2 and stream handling as wbc_sim_coriolis. Not covered: early / late contact
+ * adaptation, a duty per foot, footholds searched for standing feet, collision of the swing path with the terrain. */
+#define WBC_FOOTSTEP_NS 32          /* floats of state per env */
+#define WBC_FOOTSTEP_MAX_RADIUS 3   /* (2*3+1)^2 = 49 candidates <= 64 lanes */
+typedef struct {
+  float dt;                 /* control step, s */
+  float period, duty;       /* gait cycle s; stance fraction; duty >= 1: every foot always stands */
+  float offset[4];          /* per-foot phase offset in [0,1), feet_rb order FL,FR,RL,RR; trot = (0, .5, .5, 0) */
+  int32_t horizon;          /* H of the MPC outputs, 0..WBC_MPC_MAX_HORIZON (0: no per-stage outputs) */
+  float mpc_dt;             /* stage length of those outputs */
+  float stance_offset[4][2];/* nominal foot xy relative to the trunk origin, heading frame */
+  float k_v, com_height, max_reach;   /* Raibert feedback gain; h of the centrifugal term; clamp on |nominal - hip| */
+  float swing_height, latch;          /* apex clearance; swing fraction after which the target is frozen */
+  float kp, kd;                       /* swing PD on the reference */
+  int32_t search_radius;    /* R in 0..3: (2R+1)^2 candidates; 0: the nominal alone */
+  float search_step, probe_radius;
+  float w_dist, w_rough, w_slope, rough_max, nz_min;
+} wbc_footstep_cfg;
+#define WBC_FOOTSTEP_RESET 1
+#define WBC_FOOTSTEP_HOLD  2        /* do not advance the clock */
+#define WBC_FOOTSTEP_INFO_RESET 1
+#define WBC_FOOTSTEP_INFO_FAILED 2
+#define WBC_FOOTSTEP_INFO_NO_SAFE 16   /* << foot */
+#define WBC_FOOTSTEP_INFO_LIFT 256     /* << foot: the foot lifted off in this call */
+int wbc_sim_footstep_plan(wbc_sim* sim, const wbc_footstep_cfg* cfg, const float* base_pos, const float* base_vel, const float* quat,
+                          const float* dof, const float* vel_cmd, const float* yaw_rate, const int32_t* reset_mask,
+                          const float* phase_init, int flags, float* state,
+                          uint8_t* stance, float* contact, uint8_t* schedule, float* foot_pos, float* foothold,
+                          float* swing_ref, float* swing_acc, int32_t* info, void* stream);
+
 /* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and
  * of nudot(q, nu, tau) in the coordinates of wbc_sim_body_dynamics, from the sim's current root / DoF state, WBC_T_BODY_PARAMS and all
  * three gravity components. The sim's state is read, never written.
