@@ -15,6 +15,7 @@
 #include "wbc_proximity.h"
 #include "wbc_estimator.h"
 #include "wbc_footstep.h"
+#include "wbc_contact.h"
 #include "wbc_mpc.h"
 
 #define ARM_N 6
@@ -4496,5 +4497,64 @@ extern "C" int wbc_sim_footstep_plan(wbc_sim* s, const wbc_footstep_cfg* cfg, co
                     (flags & WBC_FOOTSTEP_RESET) ? 1 : 0, (flags & WBC_FOOTSTEP_HOLD) ? 1 : 0, c.n, state, stance, schedule, contact, foot_pos,
                     foothold, swing_ref, swing_acc, info};
   wbc_footstep_launch(K, *cfg, a, stream);
+  return c.launched();
+}
+
+// ---- contact detection from proprioception (include/wbc_sim.h: wbc_sim_contact_detect) -----------------------------------------------------
+// The host side; the kernel is in wbc_contact_kernel.hip, its argument struct in wbc_contact.h.
+extern "C" int wbc_sim_contact_detect(wbc_sim* s, const wbc_contact_cfg* cfg, const float* quat, const float* dof, const float* base_pos,
+                                      const float* tau_ext, int tau_ext_stride, const float* foot_force, const float* normal, const float* ground,
+                                      const float* phase, int phase_stride, const int32_t* reset_mask, const float* p_init, int flags, float* state,
+                                      float* prob, uint8_t* contact, uint8_t* stance, float* force, float* terms, int32_t* info, void* stream) {
+  WbCall c("wbc_sim_contact_detect", s, stream);
+  // the arguments first, so that every refusal below can be met (and tested) without a sim; then the sim
+  if (!cfg) return c.fail(-1, "cfg is NULL");
+  if (!state) return c.fail(-1, "state is NULL");
+  if (flags & ~WBC_CONTACT_RESET) return c.fail(-1, "unknown flag bits");
+  auto finite = [](float v) { return fabsf(v) <= 3.4e38f; };
+  auto positive = [](float v) { return v > 0.f && v <= 3.4e38f; };
+  auto nonneg = [](float v) { return v >= 0.f && v <= 3.4e38f; };
+  if (!positive(cfg->dt)) return c.fail(-1, "dt must be finite and > 0");
+  if (!positive(cfg->duty)) return c.fail(-1, "duty must be finite and > 0");
+  for (int f = 0; f < WBC_NFEET; ++f)
+    if (!(cfg->offset[f] >= 0.f && cfg->offset[f] < 1.f)) return c.fail(-1, "every offset must be in [0, 1)");
+  if (!positive(cfg->sigma_phase) || !positive(cfg->sigma_z) || !positive(cfg->sigma_f)) return c.fail(-1, "every sigma must be finite and > 0");
+  if (!finite(cfg->mu_z) || !finite(cfg->mu_f)) return c.fail(-1, "mu_z and mu_f must be finite");
+  if (!positive(cfg->var_phase) || !positive(cfg->var_z) || !positive(cfg->var_f)) return c.fail(-1, "every var must be finite and > 0");
+  if (!(cfg->alpha > 0.f && cfg->alpha <= 1.f)) return c.fail(-1, "alpha must be in (0, 1]");
+  if (!finite(cfg->p_on) || !finite(cfg->p_off)) return c.fail(-1, "p_on and p_off must be finite");
+  if (!(cfg->p_on > cfg->p_off)) return c.fail(-1, "p_on must be above p_off");
+  if (!nonneg(cfg->t_dwell)) return c.fail(-1, "t_dwell must be finite and >= 0");
+  if (!(cfg->early_min >= 0.f && cfg->early_min <= 1.f) || !(cfg->late_min >= 0.f && cfg->late_min <= 1.f))
+    return c.fail(-1, "early_min and late_min must be in [0, 1]");
+  if (!nonneg(cfg->damping)) return c.fail(-1, "damping must be finite and >= 0");
+  if (!tau_ext && !foot_force && !ground && !phase) return c.fail(-1, "no measurement source: tau_ext, foot_force, ground and phase are all NULL");
+  if (tau_ext && foot_force) return c.fail(-1, "tau_ext and foot_force are both given");
+  if (tau_ext && tau_ext_stride < WBC_NCOL) return c.fail(-1, "tau_ext_stride must be >= 26");
+  if (phase && phase_stride < 1) return c.fail(-1, "phase_stride must be >= 1");
+  if (((uintptr_t)quat | (uintptr_t)dof | (uintptr_t)base_pos | (uintptr_t)tau_ext | (uintptr_t)foot_force | (uintptr_t)normal | (uintptr_t)ground |
+       (uintptr_t)phase | (uintptr_t)reset_mask | (uintptr_t)p_init | (uintptr_t)state | (uintptr_t)prob | (uintptr_t)force | (uintptr_t)terms |
+       (uintptr_t)info) & 3u)
+    return c.fail(-1, "every float or int32 pointer must be 4-byte aligned");
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  const wbc_model& m = c.hc->model;
+  EstConst K;
+  if (tree_walk_fill(m, K) != 0 || !tree_rigid_ok(m)) return c.no_tree();
+  for (int f = 0; f < WBC_NFEET; ++f) {
+    const int rb = m.feet_rb[f];
+    if (rb < 0 || rb >= WBC_NRB) return c.no_tree();
+    K.foot_body[f] = m.rb_body[rb];
+    for (int j = 0; j < 3; ++j) K.foot_off[f][j] = m.rb_offset[rb][j];
+    const int32_t* path = K.path[K.foot_body[f]];                     // the kernel unrolls exactly CT_LEG_JOINTS joints per leg
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k)
+      if ((path[k] >= 0) != (k < CT_LEG_JOINTS)) return c.fail(-3, "a foot's leg does not have exactly three joints");
+  }
+  for (int j = 0; j < 3; ++j) K.gravity[j] = c.hc->cfg.gravity[j];
+  if (c.n <= 0) return 0;
+  const CtArgs a = {dof ? dof : c.dofs, quat ? quat : c.root + 3, base_pos ? base_pos : c.root, tau_ext, foot_force, normal, ground, phase, p_init,
+                    reset_mask, quat ? 4 : 26, base_pos ? 3 : 26, tau_ext_stride, phase_stride, (flags & WBC_CONTACT_RESET) ? 1 : 0, c.n,
+                    state, prob, contact, stance, force, terms, info};
+  wbc_contact_launch(K, *cfg, a, stream);
   return c.launched();
 }

@@ -149,6 +149,19 @@ class WbcFootstepCfg(C.Structure):
         (name, f32) for name in ("search_step", "probe_radius", "w_dist", "w_rough", "w_slope", "rough_max", "nz_min")]
 
 
+CONTACT_NS = 16            # WBC_CONTACT_NS: floats of detector state per env, (p, c, t, 0) per foot
+CONTACT_RESET = 1          # WBC_CONTACT_RESET (wbc_sim_contact_detect's own flags word)
+CONTACT_INFO_RESET, CONTACT_INFO_FAILED = 1, 2   # WBC_CONTACT_INFO_*; the five below << foot
+CONTACT_INFO_TOUCHDOWN, CONTACT_INFO_LIFTOFF, CONTACT_INFO_EARLY, CONTACT_INFO_LATE, CONTACT_INFO_FORCE_SINGULAR = 16, 256, 4096, 65536, 1048576
+
+
+class WbcContactCfg(C.Structure):
+    """wbc_contact_cfg (include/wbc_sim.h): the host scalars of wbc_sim_contact_detect."""
+    _fields_ = [("dt", f32), ("duty", f32), ("offset", f32 * 4)] + [(name, f32) for name in (
+        "sigma_phase", "mu_z", "sigma_z", "mu_f", "sigma_f", "var_phase", "var_z", "var_f", "alpha", "p_on", "p_off", "t_dwell", "early_min",
+        "late_min", "damping")]
+
+
 class WbcTaskQpLimits(C.Structure):
     """wbc_taskqp_limits (include/wbc_sim.h): the host scalars of wbc_sim_task_inverse_dynamics_qp; max_iter 0 = the default."""
     _fields_ = [("mu", f32), ("fn_min", f32), ("max_iter", i32)]

@@ -799,6 +799,13 @@ class WidowGo1(LeggedRobot):
         the other fields of wbc_footstep_cfg; mpc_dt None: env.dt)."""
         return FootstepPlanner(self, gait, period, duty, horizon, mpc_dt, **cfg)
 
+    # ---- contact detection (no counterpart in the reference): include/wbc_sim.h: wbc_sim_contact_detect ----
+    def contact_detector(self, planner: "FootstepPlanner" = None, gain: float = 50.0, **cfg) -> "ContactDetector":
+        """The probabilistic contact detector: which feet are on the ground, from the momentum observer's external joint torques, the
+        feet's heights and the gait clock of `planner` (None: no gait prior), without the simulator's force sensors: see ContactDetector
+        (gain: the observer's bandwidth in 1/s, capped at 0.9 / dt; cfg: the fields of wbc_contact_cfg; dt None: env.dt)."""
+        return ContactDetector(self, planner, gain, **cfg)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])
@@ -1395,3 +1402,99 @@ class FootstepPlanner:
         f = lambda t: None if t is None else t.to(torch.float32).contiguous()
         self._launch(vel_cmd=f(vel_cmd), yaw_rate=f(yaw_rate), reset_mask=env.reset_buf.to(torch.int32), hold=hold, **kw)
         return self.stance
+
+
+class ContactDetector:
+    """The probabilistic contact detector of wbc_sim_contact_detect for every env (Bledt et al., ICRA 2018): it owns the cfg, the detector
+    state [N, 16] = (p, c, t, 0) per foot, a momentum-observer state [N, 2, 26] of its own (not the sim's shared one) and every output, and
+    advances them by one observer update and one detector launch per update(). planner: a FootstepPlanner whose duty, offsets and phase
+    give the gait prior and the EARLY / LATE events (None: neither); gain: the observer's bandwidth in 1/s, capped at 0.9 / dt (the observer's
+    explicit update needs gain dt < 1; .gain holds the value in use); keyword arguments
+    are the other fields of wbc_contact_cfg (include/wbc_sim.h); dt defaults to env.dt. The detector starts reset with every foot in
+    contact. Use it as
+        det.update(torques=tau)                          # after the simulate calls that applied tau
+        est.update(contact=det.prob)
+        env.whole_body_controller(..., stance=det.stance)
+    Not covered: feeding the events back into the planner's clock, slip detection, terrain normals estimated rather than given, contacts
+    on links other than the feet."""
+
+    DEFAULTS = dict(sigma_phase=0.05, mu_z=0.01, sigma_z=0.01, mu_f=15.0, sigma_f=8.0, var_phase=0.25, var_z=0.05, var_f=0.05, alpha=0.5,
+                    p_on=0.6, p_off=0.4, t_dwell=0.04, early_min=0.5, late_min=0.2, damping=0.02)
+
+    def __init__(self, env, planner: "FootstepPlanner" = None, gain: float = 50.0, dt: float = None, **cfg):
+        unknown = set(cfg) - set(self.DEFAULTS)
+        assert not unknown, f"unknown detector parameters: {sorted(unknown)}"
+        v = dict(self.DEFAULTS, **cfg)
+        self.env, self.planner = env, planner
+        duty = float(planner.cfg.duty) if planner is not None else 1.0
+        offsets = [float(o) for o in planner.cfg.offset] if planner is not None else [0.0] * 4
+        self.gain = min(float(gain), 0.9 / float(env.dt if dt is None else dt))       # wbc_sim_momentum_observer asks for gain dt < 1
+        self.cfg = abi.WbcContactCfg(float(env.dt if dt is None else dt), duty, (abi.f32 * 4)(*offsets), *[float(v[k]) for k in self.DEFAULTS])
+        n, dev = env.num_envs, env.device
+        z = lambda *sh, dtype=torch.float32: torch.zeros(sh, dtype=dtype, device=dev)
+        self.state = z(n, abi.CONTACT_NS)
+        self.observer_state, self._observer_fresh = z(n, 2, 6 + abi.NDOF), z(n, 2, 6 + abi.NDOF)
+        self._tau = z(n, 6 + abi.NDOF)
+        self.prob, self.contact, self.stance = z(n, 4), z(n, 4, dtype=torch.uint8), z(n, 4, dtype=torch.uint8)
+        self.foot_forces, self.terms, self.info = z(n, 4, 3), z(n, 4, 4), z(n, dtype=torch.int32)
+        self._plane_ground = (torch.full((n, 4), float(abi.FOOT_RADIUS), dtype=torch.float32, device=dev)
+                              if env.cfg.terrain.mesh_type in ("plane", None) else None)
+        self.last_inputs = None
+        self.reset()
+
+    @property
+    def tau_ext(self) -> torch.Tensor:
+        """f32 [N, 26]: the observer's residual, the estimate of the external generalised forces (a strided view of observer_state)."""
+        return self.observer_state[:, 1]
+
+    def _observe(self, torques, reset_mask=None, reset=False) -> None:
+        """One observer update with the joint torques `torques` [N, 20] (None: env.torques); the envs in reset_mask (all with reset) restart
+        at the current momentum with residual 0."""
+        env = self.env
+        self._tau[:, 6:] = env.torques if torques is None else torques.to(torch.float32)
+        dt = float(self.cfg.dt)
+        env.sim.momentum_observer(self._tau, self.gain, dt, state=self.observer_state, reset=reset)
+        if reset_mask is not None and not reset:
+            env.sim.momentum_observer(self._tau, self.gain, dt, state=self._observer_fresh, reset=True)
+            self.observer_state.copy_(torch.where((reset_mask != 0)[:, None, None], self._observer_fresh, self.observer_state))
+
+    def _launch(self, foot_force=None, ground=None, base_pos=None, reset_mask=None, reset=False) -> None:
+        phase = self.planner.state[:, 0] if self.planner is not None else None
+        tau_ext = None if foot_force is not None else self.tau_ext
+        self.last_inputs = dict(tau_ext=tau_ext, foot_force=foot_force, ground=ground, base_pos=base_pos, phase=phase, reset_mask=reset_mask, reset=reset)
+        self.env.sim.contact_detect(self.cfg, self.state, base_pos=base_pos, tau_ext=tau_ext, foot_force=foot_force, ground=ground, phase=phase,
+                                    reset_mask=reset_mask, reset=reset, prob=self.prob, contact=self.contact, stance=self.stance,
+                                    force=self.foot_forces, terms=self.terms, info=self.info)
+
+    def reset(self, env_ids=None) -> None:
+        """Reset every env (env_ids None) or the listed ones: p = 1, every foot in contact, the dwell time served, the observer at the
+        current momentum with residual 0. The other envs' states are left as they are."""
+        env = self.env
+        if env_ids is None:
+            self._observe(None, reset=True)
+            self._launch(ground=self._plane_ground, reset=True)
+            return
+        mask = torch.zeros((env.num_envs,), dtype=torch.int32, device=env.device)
+        mask[torch.as_tensor(env_ids, dtype=torch.long, device=env.device)] = 1
+        tensors = (self.state, self.observer_state, self.prob, self.contact, self.stance, self.foot_forces, self.terms, self.info)
+        keep = [t.clone() for t in tensors]
+        self._observe(None, reset_mask=mask)
+        self._launch(ground=self._plane_ground, reset_mask=mask)
+        rest = mask == 0                                                            # the launches also advanced the others: put them back
+        for t, k in zip(tensors, keep):
+            t[rest] = k[rest]
+
+    def update(self, torques=None, foot_force=None, ground=None, base_pos=None) -> torch.Tensor:
+        """One observer update and one detector launch at the sim's current state, to be called once per control step after the simulate
+        calls; returns prob [N, 4]. torques [N, 20]: the joint torques that were applied, what set_dof_forces takes (None: env.torques).
+        foot_force [N, 4, 3] (world): a measured foot force, used instead of the observer's estimate. ground [N, 4]: the height of a
+        resting foot's origin; None: the foot sphere's radius above z = 0 on the plane, no height term on other terrain. base_pos
+        [N, 3]: the trunk's position (a BaseStateEstimator's), None: the sim's. duty, offsets and phase are the planner's. Envs flagged
+        in env.reset_buf are reset. Results: .prob, .contact, .stance, .foot_forces, .terms, .info; the tensors handed to the kernel are
+        kept in last_inputs."""
+        env = self.env
+        mask = env.reset_buf.to(torch.int32)
+        self._observe(torques, reset_mask=mask)
+        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        self._launch(foot_force=f(foot_force), ground=self._plane_ground if ground is None else f(ground), base_pos=f(base_pos), reset_mask=mask)
+        return self.prob

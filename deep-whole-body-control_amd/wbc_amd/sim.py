@@ -688,6 +688,50 @@ class WbcSim:
                                            ptr(reset_mask), ptr(phase_init), flags, state.data_ptr(),
                                            *[ptr(outputs.get(k)) for k in self.FOOTSTEP_OUTPUTS], self._stream()), "wbc_sim_footstep_plan")
 
+    # ---- contact detection from proprioception (include/wbc_sim.h: wbc_sim_contact_detect) -------------------------------------------------
+    CONTACT_OUTPUTS = ("prob", "contact", "stance", "force", "terms", "info")
+
+    def contact_detect(self, cfg: "abi.WbcContactCfg", state: torch.Tensor, quat: Optional[torch.Tensor] = None,
+                       dof: Optional[torch.Tensor] = None, base_pos: Optional[torch.Tensor] = None, tau_ext: Optional[torch.Tensor] = None,
+                       foot_force: Optional[torch.Tensor] = None, normal: Optional[torch.Tensor] = None, ground: Optional[torch.Tensor] = None,
+                       phase: Optional[torch.Tensor] = None, reset_mask: Optional[torch.Tensor] = None, p_init: Optional[torch.Tensor] = None,
+                       reset: bool = False, **outputs) -> None:
+        """One wbc_sim_contact_detect launch on the current stream: one control step of the probabilistic contact detector on the
+        caller-owned state f32 [N, 16] = (p, c, t, 0) per foot, in place. quat [N, 4] (xyzw), dof [N, 20, 2] and base_pos [N, 3], None:
+        the sim's current state. tau_ext [N, 26]: the external generalised forces, rows contiguous and the envs any stride >= 26 apart, so
+        that a momentum observer's state[:, 1] is taken as it stands, without a copy; or foot_force [N, 4, 3] (world), not both; normal
+        [N, 4, 3] (None: world z); ground [N, 4]: the height of a resting foot's origin (None: no height term); phase [N], the envs any
+        stride apart (a FootstepPlanner's state[:, 0] fits; None: no gait prior, no EARLY / LATE). reset=True resets every env, reset_mask
+        int32 [N] the envs whose entry is not 0, to p_init [N, 4] (None: 1). Outputs by keyword, each a caller-owned tensor that is filled
+        (CONTACT_OUTPUTS): prob [N, 4], contact u8 [N, 4], stance u8 [N, 4], force [N, 4, 3], terms [N, 4, 4], info int32 [N]."""
+        n = self.num_envs
+        unknown = set(outputs) - set(self.CONTACT_OUTPUTS)
+        assert not unknown, f"unknown outputs: {sorted(unknown)}"
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        shapes = dict(prob=((n, 4), f32), contact=((n, 4), u8), stance=((n, 4), u8), force=((n, 4, 3), f32), terms=((n, 4, 4), f32), info=((n,), i32))
+        checks = [(state, (n, abi.CONTACT_NS), f32), (quat, (n, 4), f32), (dof, (n, abi.NDOF, 2), f32), (base_pos, (n, 3), f32),
+                  (foot_force, (n, 4, 3), f32), (normal, (n, 4, 3), f32), (ground, (n, 4), f32), (reset_mask, (n,), i32), (p_init, (n, 4), f32)]
+        checks += [(outputs.get(k),) + shapes[k] for k in self.CONTACT_OUTPUTS]
+        for t, sh, dt in checks:
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == sh, (tuple(t.shape), sh)
+        assert state is not None
+        ncol = 6 + abi.NDOF
+        tau_stride = phase_stride = 0
+        if tau_ext is not None:                                                        # rows contiguous, envs any stride >= 26 apart
+            assert tau_ext.device == self.arena.device and tau_ext.dtype == f32 and tuple(tau_ext.shape) == (n, ncol), tuple(tau_ext.shape)
+            assert tau_ext.stride(1) == 1 and (n == 1 or tau_ext.stride(0) >= ncol), tau_ext.stride()
+            tau_stride = int(tau_ext.stride(0)) if n > 1 else ncol
+        if phase is not None:
+            assert phase.device == self.arena.device and phase.dtype == f32 and tuple(phase.shape) == (n,), tuple(phase.shape)
+            assert n == 1 or phase.stride(0) >= 1, phase.stride()
+            phase_stride = int(phase.stride(0)) if n > 1 else 1
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None
+        check(self.L.wbc_sim_contact_detect(self.h, C.byref(cfg), ptr(quat), ptr(dof), ptr(base_pos), ptr(tau_ext), tau_stride, ptr(foot_force),
+                                            ptr(normal), ptr(ground), ptr(phase), phase_stride, ptr(reset_mask), ptr(p_init),
+                                            abi.CONTACT_RESET if reset else 0, state.data_ptr(),
+                                            *[ptr(outputs.get(k)) for k in self.CONTACT_OUTPUTS], self._stream()), "wbc_sim_contact_detect")
+
     def proximity_damper_rows(self, gap: torch.Tensor, jac: torch.Tensor, d_safe: float, d_influence: float, xi: float, dt: float,
                               nu: Optional[torch.Tensor] = None):
         """The velocity damper of the pairs inside the influence distance as rows on the accelerations, torch ops only: the gap rate

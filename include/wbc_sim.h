@@ -1169,6 +1169,102 @@ int wbc_sim_footstep_plan(wbc_sim* sim, const wbc_footstep_cfg* cfg, const float
                           uint8_t* stance, float* contact, uint8_t* schedule, float* foot_pos, float* foothold,
                           float* swing_ref, float* swing_acc, int32_t* info, void* stream);
 
+/* One control step of the probabilistic contact detector (Bledt, Wensing, Ingersoll, Kim, "Contact Model Fusion for Event-Based Locomotion
+ * in Unstructured Terrains", ICRA 2018): which feet are on the ground, from proprioception alone. Per foot a force term (from the
+ * momentum observer's external joint torques or from a measured foot force), a height term and the gait clock's prior are fused into a
+ * contact probability, low-passed, and turned into a flag with hysteresis and a dwell time, and into touchdown / lift-off / early / late
+ * events. One launch (wbc_contact_detect_kernel); the sim's state is read, never written. Per env the caller owns
+ * state  device f32 [N, WBC_CONTACT_NS = 16], read and written: four floats per foot (feet_rb order FL, FR, RL, RR) at 4 i: the filtered
+ *        probability p_i, the flag c_i (0.0 or 1.0; read as c_i != 0), the seconds t_i since the flag last switched, a reserved 0 (written
+ *        as 0, never read).
+ * INPUTS (device f32 unless said otherwise; each may be NULL):
+ * quat [N, 4] xyzw, normalised in the call: R (world <- trunk). NULL: ROOT_STATES'.   dof [N, 20, 2] in the layout of DOF_STATE (the
+ *        velocities are not read). NULL: DOF_STATE.   base_pos [N, 3]: the trunk origin b, world axes. NULL: ROOT_STATES' (a
+ *        BaseStateEstimator's position fits here). It is read whether or not `ground` is given.
+ * tau_ext with tau_ext_stride (floats between envs, >= 26): the estimate of the external generalised forces in the 26 coordinates of
+ *        wbc_sim_body_dynamics; row 6 + d belongs to DoF d. The stride lets the residual plane of wbc_sim_momentum_observer's [N, 2, 26]
+ *        state be passed as it stands (state + 26, stride 52). Rows 0:6 are never read, nor the rows of joints that are in no leg.
+ * foot_force [N, 4, 3], world axes: a measured foot force, which replaces the estimate. tau_ext and foot_force together are refused;
+ *        with neither the force term is left out.
+ * normal [N, 4, 3]: the ground's normal under each foot, normalised in the call. NULL: world z.
+ * ground [N, 4]: the world height of a foot ORIGIN at rest on the ground under it (the convention of foot_height in
+ *        wbc_sim_leg_odometry). NULL leaves the height term out.
+ * phase [N] with phase_stride (floats between envs, >= 1): the gait clock; element 0 of wbc_sim_footstep_plan's state fits (stride
+ *        WBC_FOOTSTEP_NS). NULL leaves the gait prior and step 7's EARLY / LATE out.
+ * reset_mask int32 [N].   p_init [N, 4], NULL: 1.
+ * At least one of {tau_ext or foot_force, ground, phase} must be given.
+ * PER ENV AND FOOT i, in this order (frac(x) = x - floor(x); Phi(x) = (1/2) (1 + erf(x / sqrt 2))):
+ * 1 RESET (WBC_CONTACT_RESET in flags: every env; otherwise the envs whose reset_mask entry is not 0; the env's state is then not read):
+ *   p = p_init_i, c = 1 if p >= 1/2 else 0, t = t_dwell; info bit WBC_CONTACT_INFO_RESET. The env then goes through steps 2 .. 7 of this
+ *   very call with that state.
+ * 2 KINEMATICS  the leg walk of wbc_sim_leg_odometry from the trunk to the foot: fk_i(q) in trunk axes, the foot origin P_i = b + R fk_i,
+ *   and the 3 x 3 leg Jacobian J_i in world axes: column k = R (a_k x (fk_i - o_k)), a_k the axis and o_k the origin of the leg's k-th
+ *   actuated joint (k = 0, 1, 2 from the trunk down), both in trunk axes. These are the columns of the whole-body Jacobian's linear rows
+ *   for that foot and those DoFs.
+ * 3 FORCE  with tau_i = the three rows of tau_ext that belong to the leg's joints and delta = damping,
+ *   f_i = J_i (J_i^T J_i + delta^2 I)^-1 tau_i, which is J_i^-T tau_i where J_i is regular and delta = 0, and stays bounded (by
+ *   |tau_i| / (2 delta)) at a straight knee. A = J_i^T J_i + delta^2 I = L L^T is factorised row by row (l00 = sqrt(a00), l10 = a10 / l00,
+ *   d1 = a11 - l10^2, l11 = sqrt(d1), l20 = a20 / l00, l21 = (a21 - l20 l10) / l11, d2 = a22 - l20^2 - l21^2, l22 = sqrt(d2)), L z = tau_i
+ *   forwards, L^T y = z backwards, f_i = (J_0 y_0 + J_1 y_1) + J_2 y_2 over the columns. Where a pivot (a00, d1, d2) is not a positive
+ *   finite number, or f_i comes out not finite, f_i = 0 and info bit WBC_CONTACT_INFO_FORCE_SINGULAR << i. With foot_force, f_i is that
+ *   input. n_i = normal_i / |normal_i| (NULL: (0, 0, 1)), f_n = f_i . n_i.
+ * 4 TERMS
+ *   height  P_z = Phi((mu_z - (P_i,z - ground_i)) / sigma_z);
+ *   force   P_f = Phi((f_n - mu_f) / sigma_f);
+ *   prior   phi_i = frac(phase + offset_i). Foot i is scheduled to stand iff duty >= 1 or phi_i < duty (wbc_sim_footstep_plan's rule).
+ *           With k = sigma_phase sqrt 2 and G(s) = (1/2) [erf(s / k) + erf((1 - s) / k)]:
+ *           scheduled stance, s = phi_i / duty (the stance fraction):                 P_phi = G(s);
+ *           scheduled swing,  s = (phi_i - duty) / (1 - duty) (the swing fraction):   P_phi = 1 - G(s).
+ * 5 FUSION  the one-step Kalman fusion of the paper with A = 0, an inverse-variance mean over the terms present, summed in the order
+ *   prior, height, force:  P = (sum_k P_k / var_k) / (sum_k 1 / var_k);  then  p <- p + alpha (P - p).
+ * 6 FLAG  t <- t + dt. If c = 0, p >= p_on and t >= t_dwell: c <- 1, t <- 0, info bit WBC_CONTACT_INFO_TOUCHDOWN << i. Else if c = 1,
+ *   p <= p_off and t >= t_dwell: c <- 0, t <- 0, info bit WBC_CONTACT_INFO_LIFTOFF << i.
+ * 7 EVENTS (with phase only), on the c of step 6: WBC_CONTACT_INFO_EARLY << i while the foot is scheduled to swing with s >= early_min
+ *   and c = 1; WBC_CONTACT_INFO_LATE << i while it is scheduled to stand with s >= late_min and c = 0.
+ * OUTPUTS, each may be NULL and is then not written; what is written never depends on which are asked for:
+ * prob f32 [N, 4] = p (what wbc_sim_leg_odometry takes as contact);   contact u8 [N, 4] = c;
+ * stance u8 [N, 4]: what the whole-body calls take: (scheduled stance or EARLY) and not LATE; without phase it equals c;
+ * force f32 [N, 4, 3] = f_i (the input where foot_force was given, 0 without a force input);
+ * terms f32 [N, 4, 4] = (P_phi, P_z, P_f, P), 0 where a term is absent;   info int32 [N]: the bits below.
+ * An env with a non-finite input (quat, b, a leg joint's q, the rows of tau_ext it reads, foot_force, normal (or a zero normal), ground,
+ * phase, the p, c, t of the state it reads or its p_init) writes zeros to every output but info = WBC_CONTACT_INFO_FAILED and leaves its
+ * state as it was.
+ * Every pointer needs 4-byte alignment only (the u8 outputs none). Nothing is allocated and nothing synchronises: safe under stream capture.
+ * -1 with a message in wbc_last_error() that names the entry point, nothing written, checked BEFORE the sim: NULL cfg or state; unknown
+ * flag bits; dt, duty, sigma_phase, sigma_z, sigma_f, var_phase, var_z or var_f not finite and > 0; an offset outside [0, 1); mu_z or mu_f
+ * not finite; alpha outside (0, 1]; p_on or p_off not finite, or p_on <= p_off; t_dwell or damping not finite or < 0; early_min or
+ * late_min outside [0, 1]; no measurement source; both force inputs; tau_ext_stride < 26 or phase_stride < 1 where the pointer is given; a
+ * misaligned pointer. Then NULL sim; -3 (also: a foot whose leg does not have exactly three joints) / -2 and stream handling as
+ * wbc_sim_coriolis. Not covered: feeding the events back into the planner's clock, slip detection, terrain normals estimated rather than
+ * given, contacts on links other than the feet. */
+#define WBC_CONTACT_NS 16           /* floats of state per env */
+typedef struct {
+  float dt;                         /* control step, s */
+  float duty;                       /* the planner's stance fraction; duty >= 1: every foot is always scheduled to stand */
+  float offset[4];                  /* the planner's per-foot phase offsets in [0, 1) */
+  float sigma_phase;                /* width of the gait prior, in units of the stance / swing fraction */
+  float mu_z, sigma_z;              /* height term: mean and width of the foot origin's height above `ground`, m */
+  float mu_f, sigma_f;              /* force term: mean and width of the normal force, N */
+  float var_phase, var_z, var_f;    /* fusion variances */
+  float alpha;                      /* low-pass weight of the filtered probability, (0, 1] */
+  float p_on, p_off;                /* hysteresis thresholds, p_on > p_off */
+  float t_dwell;                    /* minimum seconds between flag switches, >= 0 */
+  float early_min, late_min;        /* swing / stance fractions from which EARLY / LATE are judged, [0, 1] */
+  float damping;                    /* delta of the damped force solve, >= 0 */
+} wbc_contact_cfg;
+#define WBC_CONTACT_RESET 1
+#define WBC_CONTACT_INFO_RESET 1
+#define WBC_CONTACT_INFO_FAILED 2
+#define WBC_CONTACT_INFO_TOUCHDOWN 16            /* << foot */
+#define WBC_CONTACT_INFO_LIFTOFF 256             /* << foot */
+#define WBC_CONTACT_INFO_EARLY 4096              /* << foot */
+#define WBC_CONTACT_INFO_LATE 65536              /* << foot */
+#define WBC_CONTACT_INFO_FORCE_SINGULAR 1048576  /* << foot */
+int wbc_sim_contact_detect(wbc_sim* sim, const wbc_contact_cfg* cfg, const float* quat, const float* dof, const float* base_pos,
+                           const float* tau_ext, int tau_ext_stride, const float* foot_force, const float* normal, const float* ground,
+                           const float* phase, int phase_stride, const int32_t* reset_mask, const float* p_init, int flags, float* state,
+                           float* prob, uint8_t* contact, uint8_t* stance, float* force, float* terms, int32_t* info, void* stream);
+
 /* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and
  * of nudot(q, nu, tau) in the coordinates of wbc_sim_body_dynamics, from the sim's current root / DoF state, WBC_T_BODY_PARAMS and all
  * three gravity components. The sim's state is read, never written.

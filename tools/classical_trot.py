@@ -2,10 +2,15 @@
 (task QP) -> set_dof_forces -> simulate, every layer one HIP launch, and report what happened. Nothing here is tuned: the gains are the
 defaults of BaseStateEstimator, FootstepPlanner, CentroidalMPC and whole_body_controller.
 
-  python tools/classical_trot.py [--envs 64] [--seconds 4] [--speed 0.3] [--gait trot]
+  python tools/classical_trot.py [--envs 64] [--seconds 4] [--speed 0.3] [--gait trot] [--detector]
 
 Prints, once per simulated second and at the end: the share of envs still upright (trunk z axis within 0.5 rad of vertical and the trunk
-above 0.15 m), the mean forward speed of the upright envs against the command, and the MPC / QP / planner status counts."""
+above 0.15 m), the mean forward speed of the upright envs against the command, and the MPC / QP / planner status counts.
+
+--detector (default off) puts the contact detector (env.contact_detector: momentum observer + wbc_sim_contact_detect) into the loop: the
+estimator takes det.prob instead of the planner's schedule and the whole-body controller det.stance instead of planner.stance. It then
+also prints how often det.contact agrees with env.get_foot_contacts() and the counts of EARLY / LATE foot-steps. Feeding the touchdown
+events back into the planner's clock is not covered: the planner still swings and places the feet by its own schedule."""
 import argparse
 import os
 import sys
@@ -17,6 +22,7 @@ ap.add_argument("--seconds", type=float, default=4.0)
 ap.add_argument("--speed", type=float, default=0.3)
 ap.add_argument("--gait", default="trot")
 ap.add_argument("--settle", type=float, default=0.5, help="seconds of standing (gait stand) before the gait starts")
+ap.add_argument("--detector", action="store_true", help="contact flags from proprioception instead of the planner's schedule")
 a = ap.parse_args()
 
 sys.path.insert(0, os.path.join(ROOT, "deep-whole-body-control_amd"))
@@ -43,6 +49,8 @@ wz = torch.zeros(n, device=dev)
 decimation = int(env.cfg.control.decimation)
 steps, settle = int(round(a.seconds / env.dt)), int(round(a.settle / env.dt))
 counts = dict(mpc=Counter(), qp=Counter(), no_safe=0, failed=0)
+dets = {id(stand): env.contact_detector(planner=stand), id(walk): env.contact_detector(planner=walk)} if a.detector else None
+agree, events, tau = [0, 0], dict(early=0, late=0, touchdown=0, liftoff=0), None
 x_start = env.root_states[:, 0].clone()
 
 
@@ -64,11 +72,19 @@ for k in range(steps):
     if k == settle:
         planner = walk
         planner.reset()
+        if a.detector:
+            dets[id(walk)].reset()
     c = cmd if k >= settle else zero
-    est.update(contact=planner.contact)
+    if a.detector:
+        det = dets[id(planner)]
+        det.update(torques=tau)                                                        # tau: what the last simulate calls applied (None at the start: env.torques)
+        est.update(contact=det.prob)
+    else:
+        est.update(contact=planner.contact)
     planner.update(c, wz, state=est)
     mpc.solve(planner.contact_schedule, c, wz, foot_positions=planner.foot_positions, state=est)
-    tau, nudot, lam, info = env.whole_body_controller(base_acc=mpc.base_acc, swing_acc=planner.swing_acc, stance=planner.stance)
+    tau, nudot, lam, info = env.whole_body_controller(base_acc=mpc.base_acc, swing_acc=planner.swing_acc,
+                                                      stance=det.stance if a.detector else planner.stance)
     env.sim.set_dof_forces(tau.contiguous())
     for _ in range(decimation):
         env.sim.simulate()
@@ -76,8 +92,16 @@ for k in range(steps):
     counts["qp"].update(info["status"].cpu().tolist())
     counts["no_safe"] += int(((planner.info >> 4) & 15 != 0).sum())
     counts["failed"] += int((planner.info & 2 != 0).sum())
+    if a.detector and k >= settle:
+        up = upright()
+        agree[0] += int((det.contact.bool() == env.get_foot_contacts())[up].sum()); agree[1] += 4 * int(up.sum())
+        for name, shift in (("touchdown", 4), ("liftoff", 8), ("early", 12), ("late", 16)):
+            events[name] += int(sum(((det.info >> (shift + i)) & 1).sum() for i in range(4)))
     if (k + 1) % int(round(1.0 / env.dt)) == 0:
         report(f"t = {(k + 1) * env.dt:.2f} s", k)
 report("end", steps - 1)
 print(f"MPC status counts (0 ok, 1 iterations, 2 failed): {dict(counts['mpc'])}; QP status counts (0 optimal, 1 / 2 clamped): {dict(counts['qp'])}; "
       f"planner: {counts['no_safe']} env-steps with NO_SAFE, {counts['failed']} FAILED", flush=True)
+if a.detector:
+    print(f"detector: det.contact equals get_foot_contacts() in {agree[0] / max(agree[1], 1):.3f} of the upright foot-steps; foot-steps flagged "
+          f"EARLY {events['early']}, LATE {events['late']}; TOUCHDOWN events {events['touchdown']}, LIFTOFF events {events['liftoff']}", flush=True)
