@@ -16,6 +16,7 @@
 #include "wbc_estimator.h"
 #include "wbc_footstep.h"
 #include "wbc_contact.h"
+#include "wbc_legctl.h"
 #include "wbc_mpc.h"
 
 #define ARM_N 6
@@ -4556,5 +4557,88 @@ extern "C" int wbc_sim_contact_detect(wbc_sim* s, const wbc_contact_cfg* cfg, co
                     reset_mask, quat ? 4 : 26, base_pos ? 3 : 26, tau_ext_stride, phase_stride, (flags & WBC_CONTACT_RESET) ? 1 : 0, c.n,
                     state, prob, contact, stance, force, terms, info};
   wbc_contact_launch(K, *cfg, a, stream);
+  return c.launched();
+}
+
+// ---- leg controller: stance forces and swing references to joint torques (include/wbc_sim.h: wbc_sim_leg_control) --------------------------
+// The host side; the kernel is in wbc_legctl_kernel.hip, its argument struct in wbc_legctl.h.
+extern "C" int wbc_sim_leg_control(wbc_sim* s, const wbc_leg_control_cfg* cfg, const float* quat, const float* dof, const float* base_pos,
+                                   const float* base_vel, const float* ang_vel, const float* forces, const float* swing_ref, const float* stance,
+                                   const float* tau_bias, int tau_bias_stride, const float* mass_matrix, int mass_matrix_stride,
+                                   const float* acc_bias, int acc_bias_stride, const float* arm_q_des, const float* tau_limit, int flags,
+                                   float* tau, float* leg_force, float* foot, int32_t* info, void* stream) {
+  WbCall c("wbc_sim_leg_control", s, stream);
+  // the arguments first, so that every refusal below can be met (and tested) without a sim; then the sim
+  if (!cfg) return c.fail(-1, "cfg is NULL");
+  if (flags & ~WBC_LEGCTL_CLIP) return c.fail(-1, "unknown flag bits");
+  auto finite = [](float v) { return fabsf(v) <= 3.4e38f; };
+  auto nonneg = [](float v) { return v >= 0.f && v <= 3.4e38f; };
+  for (int j = 0; j < 3; ++j)
+    if (!nonneg(cfg->kp[j]) || !nonneg(cfg->kd[j])) return c.fail(-1, "every kp and kd must be finite and >= 0");
+  if (!nonneg(cfg->kd_stance)) return c.fail(-1, "kd_stance must be finite and >= 0");
+  if (!nonneg(cfg->damping)) return c.fail(-1, "damping must be finite and >= 0");
+  for (int j = 0; j < LC_ARM_DOFS; ++j) {
+    if (!nonneg(cfg->kp_arm[j]) || !nonneg(cfg->kd_arm[j])) return c.fail(-1, "every kp_arm and kd_arm must be finite and >= 0");
+    if (!finite(cfg->arm_q_default[j])) return c.fail(-1, "every arm_q_default must be finite");
+  }
+  if (!nonneg(cfg->fz_min)) return c.fail(-1, "fz_min must be finite and >= 0");
+  if (!(cfg->fz_max >= cfg->fz_min && cfg->fz_max <= 3.4e38f)) return c.fail(-1, "fz_max must be finite and >= fz_min");
+  if (!nonneg(cfg->mu)) return c.fail(-1, "mu must be finite and >= 0");
+  if (tau_bias && tau_bias_stride < WBC_NCOL) return c.fail(-1, "tau_bias_stride must be >= 26");
+  if (mass_matrix && mass_matrix_stride < WBC_NCOL * WBC_NCOL) return c.fail(-1, "mass_matrix_stride must be >= 676");
+  if (acc_bias && acc_bias_stride < WBC_NRB * 6) return c.fail(-1, "acc_bias_stride must be >= 162");
+  if (((uintptr_t)quat | (uintptr_t)dof | (uintptr_t)base_pos | (uintptr_t)base_vel | (uintptr_t)ang_vel | (uintptr_t)forces | (uintptr_t)swing_ref |
+       (uintptr_t)stance | (uintptr_t)tau_bias | (uintptr_t)mass_matrix | (uintptr_t)acc_bias | (uintptr_t)arm_q_des | (uintptr_t)tau_limit |
+       (uintptr_t)tau | (uintptr_t)leg_force | (uintptr_t)foot | (uintptr_t)info) & 3u)
+    return c.fail(-1, "every pointer must be 4-byte aligned");
+  if (mass_matrix && !swing_ref) return c.fail(-1, "mass_matrix is given without swing_ref");
+  if (!tau && !leg_force && !foot && !info) return c.fail(-1, "every output is NULL");
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  const wbc_model& m = c.hc->model;
+  EstConst K;
+  if (tree_walk_fill(m, K) != 0 || !tree_rigid_ok(m)) return c.no_tree();
+  LcArgs a = {dof ? dof : c.dofs, quat ? quat : c.root + 3, base_pos ? base_pos : c.root, base_vel ? base_vel : c.root + 7,
+              ang_vel ? ang_vel : c.root + 10, forces, swing_ref, stance, tau_bias, mass_matrix, acc_bias, arm_q_des, tau_limit,
+              quat ? 4 : 26, base_pos ? 3 : 26, base_vel ? 3 : 26, ang_vel ? 3 : 26, tau_bias_stride, mass_matrix_stride, acc_bias_stride,
+              (flags & WBC_LEGCTL_CLIP) ? 1 : 0, c.n};
+  a.tau = tau; a.leg_force = leg_force; a.foot = foot; a.info = info;
+  bool in_leg[WBC_NDOF] = {};
+  for (int f = 0; f < WBC_NFEET; ++f) {
+    const int rb = m.feet_rb[f];
+    if (rb < 0 || rb >= WBC_NRB) return c.no_tree();
+    a.foot_rb[f] = rb;
+    K.foot_body[f] = m.rb_body[rb];
+    for (int j = 0; j < 3; ++j) K.foot_off[f][j] = m.rb_offset[rb][j];
+    const int32_t* path = K.path[K.foot_body[f]];                     // the kernel unrolls exactly LC_LEG_JOINTS joints per leg
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k) {
+      if ((path[k] >= 0) != (k < LC_LEG_JOINTS)) return c.fail(-3, "a foot's leg does not have exactly three joints");
+      if (path[k] < 0) continue;
+      const int d = K.dof[path[k]];
+      if (d < 0 || d >= WBC_NDOF || in_leg[d]) return c.fail(-3, "a foot's leg does not have exactly three joints of its own");
+      in_leg[d] = true;
+    }
+  }
+  for (int j = 0; j < 3; ++j) K.gravity[j] = c.hc->cfg.gravity[j];
+  // the live DoFs in DoF order: their columns of tau_limit; those in no leg are the arm's; the rest (the locked fingers) get 0
+  bool driven[WBC_NDOF] = {};
+  for (int b = 1; b < WBC_NB; ++b)
+    if (K.dof[b] >= 0 && K.dof[b] < WBC_NDOF) driven[K.dof[b]] = true;
+  int nlive = 0, narm = 0, nfinger = 0;
+  const int max_finger = (int)(sizeof(a.finger_dof) / sizeof(a.finger_dof[0]));
+  for (int d = 0; d < WBC_NDOF; ++d) {
+    a.limit_col[d] = -1;
+    if (!driven[d]) {
+      if (nfinger < max_finger) a.finger_dof[nfinger] = d;
+      ++nfinger;
+      continue;
+    }
+    if (nlive < LC_NLIMIT) a.limit_col[d] = nlive;
+    ++nlive;
+    if (!in_leg[d]) { if (narm < LC_ARM_DOFS) a.arm_dof[narm] = d; ++narm; }
+  }
+  if (narm != LC_ARM_DOFS || nfinger != max_finger || nlive != LC_NLIMIT) return c.fail(-3, "the model does not have exactly six arm DoFs beside the legs and the locked fingers");
+  if (c.n <= 0) return 0;
+  wbc_legctl_launch(K, *cfg, a, stream);
   return c.launched();
 }

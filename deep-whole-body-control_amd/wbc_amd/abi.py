@@ -162,6 +162,17 @@ class WbcContactCfg(C.Structure):
         "late_min", "damping")]
 
 
+LEGCTL_CLIP = 1            # WBC_LEGCTL_CLIP (wbc_sim_leg_control's own flags word)
+LEGCTL_INFO_FAILED = 2     # WBC_LEGCTL_INFO_*; the three below << foot (SATURATED << 4: the arm)
+LEGCTL_INFO_FORCE_CLIPPED, LEGCTL_INFO_FF_SINGULAR, LEGCTL_INFO_SATURATED = 16, 256, 4096
+
+
+class WbcLegControlCfg(C.Structure):
+    """wbc_leg_control_cfg (include/wbc_sim.h): the host scalars of wbc_sim_leg_control."""
+    _fields_ = [("kp", f32 * 3), ("kd", f32 * 3), ("kd_stance", f32), ("damping", f32), ("fz_min", f32), ("fz_max", f32), ("mu", f32),
+                ("kp_arm", f32 * 6), ("kd_arm", f32 * 6), ("arm_q_default", f32 * 6)]
+
+
 class WbcTaskQpLimits(C.Structure):
     """wbc_taskqp_limits (include/wbc_sim.h): the host scalars of wbc_sim_task_inverse_dynamics_qp; max_iter 0 = the default."""
     _fields_ = [("mu", f32), ("fn_min", f32), ("max_iter", i32)]

@@ -806,6 +806,13 @@ class WidowGo1(LeggedRobot):
         (gain: the observer's bandwidth in 1/s, capped at 0.9 / dt; cfg: the fields of wbc_contact_cfg; dt None: env.dt)."""
         return ContactDetector(self, planner, gain, **cfg)
 
+    # ---- leg controller (no counterpart in the reference): include/wbc_sim.h: wbc_sim_leg_control ----
+    def leg_controller(self, **cfg) -> "LegController":
+        """The controller below the MPC: stance legs push with the planned foot forces (tau = -J^T f), swing legs follow the planner's
+        references by a Cartesian impedance with the acceleration feed-forward, the arm holds a posture: see LegController (cfg: the
+        fields of wbc_leg_control_cfg, plus bias, tau_limit and clip)."""
+        return LegController(self, **cfg)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])
@@ -1498,3 +1505,101 @@ class ContactDetector:
         f = lambda t: None if t is None else t.to(torch.float32).contiguous()
         self._launch(foot_force=f(foot_force), ground=self._plane_ground if ground is None else f(ground), base_pos=f(base_pos), reset_mask=mask)
         return self.prob
+
+
+class LegController:
+    """The leg controller of wbc_sim_leg_control for every env (Di Carlo et al. and Bledt et al., IROS 2018): it owns the cfg and every
+    output and turns foot forces and swing references into joint torques by one launch per update(), after one inverse-dynamics launch
+    for the bias torques and, with the feed-forward, the mass-matrix refresh and one body-accelerations launch. Keyword arguments are the
+    fields of wbc_leg_control_cfg (include/wbc_sim.h): kp, kd (three numbers each, or one for all axes), kd_stance, damping, fz_min,
+    fz_max, mu, kp_arm, kd_arm, arm_q_default (six numbers each); and bias ("h": Coriolis and gravity torques, "g": gravity alone, None:
+    none), tau_limit ([N, 18], [18] or None for the config's torque limits; False: no clamp) and clip (clip the forces to the pyramid
+    of fz_min, fz_max and mu). The swing gains are UNTUNED placeholders; the arm's gains default to the task config's PD stiffness and
+    damping of its joints, its targets to the default posture. Use it as
+        mpc.solve(planner.contact_schedule, ..., state=est)
+        tau = ctl.update(forces=mpc.forces, swing_ref=planner.swing_ref, stance=planner.contact, state=est)
+        env.sim.set_dof_forces(tau)
+    Not covered: normals other than world z in the clip, the base's acceleration in the feed-forward, joint-space position targets for
+    the legs, a task-space arm."""
+
+    DEFAULTS = dict(kp=(400.0, 400.0, 400.0), kd=(8.0, 8.0, 8.0), kd_stance=0.2, damping=0.02, fz_min=0.0, fz_max=250.0, mu=0.5,
+                    kp_arm=None, kd_arm=None, arm_q_default=None)
+
+    def __init__(self, env, bias="h", tau_limit=None, clip: bool = False, **cfg):
+        unknown = set(cfg) - set(self.DEFAULTS)
+        assert not unknown, f"unknown leg-controller parameters: {sorted(unknown)}"
+        assert bias in ("h", "g", None), "bias is 'h', 'g' or None"
+        v = dict(self.DEFAULTS, **cfg)
+        self.env, self.bias, self.clip = env, bias, bool(clip)
+        n, dev = env.num_envs, env.device
+        self.leg_dofs, self.arm_dofs = self.dof_groups(env)
+        arm = self.arm_dofs
+        three = lambda t: tuple(float(x) for x in (t if hasattr(t, "__len__") else (t,) * 3))
+        six = lambda t, default: tuple(float(x) for x in (default if t is None else t))
+        kp_arm = six(v["kp_arm"], [float(env.p_gains[d]) for d in arm])
+        kd_arm = six(v["kd_arm"], [float(env.d_gains[d]) for d in arm])
+        q_arm = six(v["arm_q_default"], [float(env.default_dof_pos[d]) for d in arm])
+        assert len(kp_arm) == len(kd_arm) == len(q_arm) == 6
+        self.cfg = abi.WbcLegControlCfg((abi.f32 * 3)(*three(v["kp"])), (abi.f32 * 3)(*three(v["kd"])), float(v["kd_stance"]), float(v["damping"]),
+                                        float(v["fz_min"]), float(v["fz_max"]), float(v["mu"]), (abi.f32 * 6)(*kp_arm), (abi.f32 * 6)(*kd_arm),
+                                        (abi.f32 * 6)(*q_arm))
+        if tau_limit is False:
+            self.tau_limit = None
+        elif tau_limit is None:
+            live = sorted([d for leg in self.leg_dofs for d in leg] + list(arm))        # the 18 revolute joints in DoF order
+            self.tau_limit = env.torque_limits[live].to(torch.float32).expand(n, -1).contiguous()
+        else:
+            self.tau_limit = torch.as_tensor(tau_limit, dtype=torch.float32, device=dev).expand(n, 18).contiguous()
+        z = lambda *sh, dtype=torch.float32: torch.zeros(sh, dtype=dtype, device=dev)
+        self.tau, self.leg_force, self.foot, self.info = z(n, abi.NDOF), z(n, 4, 3), z(n, 4, 6), z(n, dtype=torch.int32)
+        self._bias, self._acc = z(n, 6 + abi.NDOF), z(n, abi.NRB, 6)
+        self.last_inputs = None
+
+    @staticmethod
+    def dof_groups(env):
+        """(legs, arm): the DoFs of each leg's three joints from the trunk down, in feet_indices order, and the six DoFs that drive a
+        body but are in no leg, in DoF order (a walk up the robot model from each foot)."""
+        m = env.robot_model
+        legs = []
+        for rb in [int(i) for i in env.feet_indices.tolist()]:
+            chain, b = [], int(m.rb_body[rb])
+            while b > 0:
+                chain.append(int(m.body_dof[b]))
+                b = int(m.parent[b])
+            legs.append(tuple(chain[::-1]))
+        in_leg = {d for leg in legs for d in leg}
+        driven = sorted({int(m.body_dof[b]) for b in range(1, len(m.parent))})
+        return legs, [d for d in driven if d not in in_leg]
+
+    def update(self, forces=None, swing_ref=None, stance=None, state=None, arm_q_des=None, feedforward: bool = True) -> torch.Tensor:
+        """One control step at the sim's current state; returns tau [N, 20] for sim.set_dof_forces. forces [N, 4, 3] (world; a
+        CentroidalMPC's .forces; None: 0), swing_ref [N, 4, 9] (a FootstepPlanner's; None: no swing term), stance [N, 4] (the planner's
+        .contact or a ContactDetector's .prob, any dtype; None: every foot stands). state: None for the sim's own base position and
+        velocity, or a BaseStateEstimator, whose position and velocity replace them. arm_q_des [N, 6]: the arm's targets (None: the
+        cfg's). feedforward (with swing_ref only): the swing legs' J^T Lambda (a_ref - Jdot nu), from the refreshed env.mm_whole and one
+        body-accelerations launch. Results: .tau, .leg_force (what each leg pushes with), .foot (p, pd) and .info; the tensors handed
+        to the kernel are kept in last_inputs."""
+        env = self.env
+        kw = {}
+        if isinstance(state, BaseStateEstimator):
+            kw = dict(base_pos=state.position.contiguous(), base_vel=state.velocity.contiguous())
+        else:
+            assert state is None, "state is a BaseStateEstimator or None"
+        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        tau_bias = None
+        if self.bias == "h":
+            env.sim.inverse_dynamics(tau=self._bias)
+            tau_bias = self._bias
+        elif self.bias == "g":
+            env.sim.inverse_dynamics(grav=self._bias)
+            tau_bias = self._bias
+        mm = acc = None
+        if feedforward and swing_ref is not None:
+            env.refresh_mass_matrix_tensors()
+            mm = env.mm_whole
+            acc = env.sim.body_accelerations(None, out=self._acc)
+        kw.update(forces=f(forces), swing_ref=f(swing_ref), stance=f(stance), tau_bias=tau_bias, mass_matrix=mm, acc_bias=acc,
+                  arm_q_des=f(arm_q_des), tau_limit=self.tau_limit, clip=self.clip)
+        self.last_inputs = dict(kw)
+        env.sim.leg_control(self.cfg, tau=self.tau, leg_force=self.leg_force, foot=self.foot, info=self.info, **kw)
+        return self.tau

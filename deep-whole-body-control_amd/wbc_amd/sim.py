@@ -732,6 +732,47 @@ class WbcSim:
                                             abi.CONTACT_RESET if reset else 0, state.data_ptr(),
                                             *[ptr(outputs.get(k)) for k in self.CONTACT_OUTPUTS], self._stream()), "wbc_sim_contact_detect")
 
+    # ---- leg controller (include/wbc_sim.h: wbc_sim_leg_control) ----------------------------------------------------------------------------
+    LEGCTL_OUTPUTS = ("tau", "leg_force", "foot", "info")
+
+    def leg_control(self, cfg: "abi.WbcLegControlCfg", quat: Optional[torch.Tensor] = None, dof: Optional[torch.Tensor] = None,
+                    base_pos: Optional[torch.Tensor] = None, base_vel: Optional[torch.Tensor] = None, ang_vel: Optional[torch.Tensor] = None,
+                    forces: Optional[torch.Tensor] = None, swing_ref: Optional[torch.Tensor] = None, stance: Optional[torch.Tensor] = None,
+                    tau_bias: Optional[torch.Tensor] = None, mass_matrix: Optional[torch.Tensor] = None, acc_bias: Optional[torch.Tensor] = None,
+                    arm_q_des: Optional[torch.Tensor] = None, tau_limit: Optional[torch.Tensor] = None, clip: bool = False, **outputs) -> None:
+        """One wbc_sim_leg_control launch on the current stream: the joint torques of the stance legs from the planned foot forces
+        (-J^T f), of the swing legs from a Cartesian impedance on swing_ref with the acceleration feed-forward, and of the arm from a joint
+        PD. quat [N, 4] (xyzw), dof [N, 20, 2], base_pos, base_vel and ang_vel [N, 3] (world), None: the sim's current state. forces
+        [N, 4, 3] (None: 0), swing_ref [N, 4, 9] (None: no swing term), stance f32 [N, 4] weights in [0, 1] (None: 1). tau_bias [N, 26],
+        mass_matrix [N, 26, 26] and acc_bias [N, 27, 6] are taken as they stand: an env's rows contiguous, the envs any stride at or
+        above the size apart (a plane of a wider buffer, env.mm_whole, body_accelerations(None)). arm_q_des [N, 6] (None: the cfg's
+        default), tau_limit [N, 18] (None: no clamp); clip=True clips the forces to the cfg's pyramid first. Outputs by keyword, each a
+        caller-owned tensor that is filled (LEGCTL_OUTPUTS): tau [N, 20], leg_force [N, 4, 3], foot [N, 4, 6], info int32 [N]."""
+        n, ncol = self.num_envs, 6 + abi.NDOF
+        unknown = set(outputs) - set(self.LEGCTL_OUTPUTS)
+        assert not unknown, f"unknown outputs: {sorted(unknown)}"
+        f32, i32 = torch.float32, torch.int32
+        shapes = dict(tau=((n, abi.NDOF), f32), leg_force=((n, 4, 3), f32), foot=((n, 4, 6), f32), info=((n,), i32))
+        checks = [(quat, (n, 4), f32), (dof, (n, abi.NDOF, 2), f32), (base_pos, (n, 3), f32), (base_vel, (n, 3), f32), (ang_vel, (n, 3), f32),
+                  (forces, (n, 4, 3), f32), (swing_ref, (n, 4, 9), f32), (stance, (n, 4), f32), (arm_q_des, (n, 6), f32), (tau_limit, (n, 18), f32)]
+        checks += [(outputs.get(k),) + shapes[k] for k in self.LEGCTL_OUTPUTS]
+        for t, sh, dt in checks:
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == sh, (tuple(t.shape), sh)
+        strides = {}
+        for name, t, sh in (("tau_bias", tau_bias, (ncol,)), ("mass_matrix", mass_matrix, (ncol, ncol)), ("acc_bias", acc_bias, (abi.NRB, 6))):
+            strides[name] = 0
+            if t is not None:                                                          # an env's rows contiguous, the envs any stride >= the size apart
+                size = int(torch.Size(sh).numel())
+                assert t.device == self.arena.device and t.dtype == f32 and tuple(t.shape) == (n,) + sh, (name, tuple(t.shape))
+                assert t[0].is_contiguous() and (n == 1 or t.stride(0) >= size), (name, t.stride())
+                strides[name] = int(t.stride(0)) if n > 1 else size
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None
+        check(self.L.wbc_sim_leg_control(self.h, C.byref(cfg), ptr(quat), ptr(dof), ptr(base_pos), ptr(base_vel), ptr(ang_vel), ptr(forces),
+                                         ptr(swing_ref), ptr(stance), ptr(tau_bias), strides["tau_bias"], ptr(mass_matrix), strides["mass_matrix"],
+                                         ptr(acc_bias), strides["acc_bias"], ptr(arm_q_des), ptr(tau_limit), abi.LEGCTL_CLIP if clip else 0,
+                                         *[ptr(outputs.get(k)) for k in self.LEGCTL_OUTPUTS], self._stream()), "wbc_sim_leg_control")
+
     def proximity_damper_rows(self, gap: torch.Tensor, jac: torch.Tensor, d_safe: float, d_influence: float, xi: float, dt: float,
                               nu: Optional[torch.Tensor] = None):
         """The velocity damper of the pairs inside the influence distance as rows on the accelerations, torch ops only: the gap rate

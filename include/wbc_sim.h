@@ -1265,6 +1265,86 @@ int wbc_sim_contact_detect(wbc_sim* sim, const wbc_contact_cfg* cfg, const float
                            const float* phase, int phase_stride, const int32_t* reset_mask, const float* p_init, int flags, float* state,
                            float* prob, uint8_t* contact, uint8_t* stance, float* force, float* terms, int32_t* info, void* stream);
 
+/* One control step of the leg controller that turns the MPC's foot forces and the planner's swing references into joint torques, the
+ * layer that Di Carlo et al. ("Dynamic Locomotion in the MIT Cheetah 3 Through Convex Model-Predictive Control", IROS 2018) and Bledt et
+ * al. ("MIT Cheetah 3: Design and Control of a Robust, Dynamic Quadruped Robot", IROS 2018) run below their force planner: a stance leg
+ * maps its planned force through the leg Jacobian (tau = -J^T f), a swing leg runs a Cartesian impedance on its reference with the
+ * feed-forward J^T Lambda (a_ref - Jdot qd) + C qd + g, the arm holds a posture by a joint PD. One launch (wbc_leg_control_kernel); the
+ * sim's state is read, never written; the call keeps no state of its own.
+ * INPUTS (device f32; each may be NULL):
+ * quat [N, 4] xyzw, normalised in the call: R (world <- trunk).   dof [N, 20, 2] in the layout of DOF_STATE.   base_pos, base_vel [N, 3]:
+ *        position b and velocity v of the trunk's origin.   ang_vel [N, 3]: the trunk's angular velocity. All in world axes; NULL:
+ *        ROOT_STATES' / DOF_STATE's, as in wbc_sim_footstep_plan (a BaseStateEstimator's position and velocity fit base_pos / base_vel).
+ * forces [N, 4, 3]: the force ON each foot, world axes, as wbc_sim_centroidal_mpc writes it (feet_rb order FL, FR, RL, RR). NULL: 0.
+ * swing_ref [N, 4, 9] = (pos, vel, acc) per foot, as wbc_sim_footstep_plan writes it. NULL: no swing term (F_i = 0 in step 4); acc is
+ *        read only where mass_matrix is given.
+ * stance [N, 4]: the stance weight of each foot, clamped to [0, 1] in the call (wbc_sim_footstep_plan's contact and
+ *        wbc_sim_contact_detect's prob fit). NULL: 1.
+ * tau_bias with tau_bias_stride (floats between envs, >= 26): row 6 + d is added to DoF d's torque; the tau of wbc_sim_inverse_dynamics
+ *        fits (h with nudot NULL, or its grav output g). NULL: 0. Rows 0:6 and the fingers' rows are never read.
+ * mass_matrix with mass_matrix_stride (>= 676): the [N, 26, 26] tensor of wbc_sim_body_dynamics as it stands; of each env only the
+ *        3 x 3 block M_i (rows and columns 6 + the leg's own three DoFs) of every leg is read. NULL: no acceleration feed-forward (step 6
+ *        is left out). mass_matrix without swing_ref is refused.
+ * acc_bias with acc_bias_stride (>= 162): the [N, 27, 6] tensor of wbc_sim_body_accelerations(nudot = NULL) as it stands, Jdot nu of
+ *        every rigid-body origin; only rows 0:3 of rigid body feet_rb[i] are read, and only where mass_matrix is given. NULL: 0.
+ * arm_q_des [N, 6]: the arm's joint targets, the arm's DoFs in DoF order. NULL: cfg.arm_q_default.
+ * tau_limit [N, 18]: in the layout wbc_sim_task_inverse_dynamics_qp takes (the 18 revolute joints in DoF order), >= 0. NULL: no clamp.
+ * Entries that are never read may hold NaN.
+ * PER ENV AND FOOT i (feet_rb order), in this order; d_0, d_1, d_2 are the DoFs of the leg's joints from the trunk down:
+ * 1 KINEMATICS  the leg walk of wbc_sim_contact_detect step 2: fk_i(q) in trunk axes, the columns c_k = a_k x (fk_i - o_k) of the leg
+ *   Jacobian in trunk axes (a_k the axis, o_k the origin of the leg's k-th joint), p_i = b + R fk_i and J_i = R [c_0 c_1 c_2] in world
+ *   axes; the foot's velocity in the planner's convention, pd_i = v + R (w_b x fk_i + ((c_0 qd_0 + c_1 qd_1) + c_2 qd_2)) with
+ *   w_b = R^T ang_vel.
+ * 2 WEIGHT  w_i = min(max(stance_i, 0), 1).
+ * 3 STANCE FORCE  f_i = forces_i. With WBC_LEGCTL_CLIP in flags the output rule of wbc_sim_centroidal_mpc applies: f_z <- min(max(f_z,
+ *   fz_min), fz_max), then f_x <- min(max(f_x, -mu f_z), mu f_z) and the same for f_y; info bit WBC_LEGCTL_INFO_FORCE_CLIPPED << i where
+ *   w_i > 0 and a component changed.
+ * 4 SWING FORCE  F_i = kp o (pos_ref - p_i) + kd o (vel_ref - pd_i), o the product per world axis (kp[3], kd[3]); 0 without swing_ref.
+ * 5 FEEDBACK TORQUE  G_i = (1 - w_i) F_i - w_i f_i, the force the leg is to push the foot with; tau_fb,k = J_i[:, k] . G_i.
+ * 6 FEED-FORWARD (with mass_matrix only)  a = acc_ref - acc_bias_i (the foot's commanded acceleration less Jdot nu), delta = damping,
+ *   A = J_i^T J_i + delta^2 I = L L^T factorised row by row as in wbc_sim_contact_detect step 3 (l00 = sqrt(a00), l10 = a10 / l00,
+ *   d1 = a11 - l10^2, l11 = sqrt(d1), l20 = a20 / l00, l21 = (a21 - l20 l10) / l11, d2 = a22 - l20^2 - l21^2, l22 = sqrt(d2)), L z = J_i^T a
+ *   forwards, L^T qdd = z backwards: qdd = A^-1 J_i^T a, the joint accelerations that give the foot the acceleration a while the trunk's
+ *   own acceleration is taken as ZERO; |qdd| <= |a| / (2 delta) at a straight knee. tau_ff,k = (1 - w_i) ((M_i[k,0] qdd_0 + M_i[k,1] qdd_1)
+ *   + M_i[k,2] qdd_2). For a regular J_i and delta = 0 this is Cheetah 3's J_i^T Lambda_i (a_ref - Jdot qd), Lambda_i = (J_i M_i^-1
+ *   J_i^T)^-1. Where a pivot (a00, d1, d2) is not a positive finite number or qdd is not finite: tau_ff = 0 and info bit
+ *   WBC_LEGCTL_INFO_FF_SINGULAR << i.
+ * 7 LEG JOINTS  tau_dk = ((tau_fb,k + tau_ff,k) + tau_bias[6 + d_k]) - (w_i kd_stance) qd_dk.
+ * 8 ARM, once per env, for the six DoFs d that are in no leg and are not the locked fingers, j = 0 .. 5 in DoF order:
+ *   tau_d = (tau_bias[6 + d] + kp_arm[j] (q_des,j - q_d)) - kd_arm[j] qd_d.
+ * 9 LIMIT (with tau_limit only)  every torque tau <- min(max(tau, -limit), limit); info bit WBC_LEGCTL_INFO_SATURATED << i for leg i and
+ *   << 4 for the arm where one changed. The fingers' entries of tau are exactly 0.
+ * OUTPUTS, each may be NULL and is then not written (not all four); what is written never depends on which are asked for:
+ * tau f32 [N, 20], what wbc_sim_set_dof_forces takes;   leg_force f32 [N, 4, 3] = G_i;   foot f32 [N, 4, 6] = (p_i, pd_i);
+ * info int32 [N]: the bits below.
+ * An env with a non-finite input that it reads (a tau_limit entry that is negative counts as one), or with an output that comes out
+ * not finite, writes zeros to every output but info = WBC_LEGCTL_INFO_FAILED.
+ * Every pointer needs 4-byte alignment only. Nothing is allocated and nothing synchronises: safe under stream capture.
+ * -1 with a message in wbc_last_error() that names the entry point, nothing written, checked BEFORE the sim: NULL cfg; unknown flag bits;
+ * a kp, kd, kd_stance, kp_arm, kd_arm or damping entry not finite or < 0; fz_min not finite or < 0, fz_max not finite or < fz_min, mu not
+ * finite or < 0; an arm_q_default entry not finite; a stride below its minimum where its pointer is given; a misaligned pointer;
+ * mass_matrix without swing_ref; every output NULL. Then NULL sim; -3 (also: a foot whose leg does not have exactly three joints, or an
+ * arm DoF count other than six) / -2 and stream handling as wbc_sim_coriolis. Not covered: normals other than world z in the clip, the
+ * base's acceleration in the feed-forward, joint-space position targets for the legs, a task-space arm. */
+typedef struct {
+  float kp[3], kd[3];               /* swing impedance per world axis, N/m and N s/m, >= 0 */
+  float kd_stance;                  /* joint damping of a stance leg, N m s/rad, >= 0 */
+  float damping;                    /* delta of the damped feed-forward solve, >= 0 */
+  float fz_min, fz_max, mu;         /* the clip of WBC_LEGCTL_CLIP: 0 <= fz_min <= fz_max, mu >= 0 */
+  float kp_arm[6], kd_arm[6];       /* the arm's joint PD, the arm's DoFs in DoF order, >= 0 */
+  float arm_q_default[6];           /* the arm's targets where arm_q_des is NULL */
+} wbc_leg_control_cfg;
+#define WBC_LEGCTL_CLIP 1
+#define WBC_LEGCTL_INFO_FAILED 2
+#define WBC_LEGCTL_INFO_FORCE_CLIPPED 16         /* << foot */
+#define WBC_LEGCTL_INFO_FF_SINGULAR 256          /* << foot */
+#define WBC_LEGCTL_INFO_SATURATED 4096           /* << foot; << 4: the arm */
+int wbc_sim_leg_control(wbc_sim* sim, const wbc_leg_control_cfg* cfg, const float* quat, const float* dof, const float* base_pos,
+                        const float* base_vel, const float* ang_vel, const float* forces, const float* swing_ref, const float* stance,
+                        const float* tau_bias, int tau_bias_stride, const float* mass_matrix, int mass_matrix_stride,
+                        const float* acc_bias, int acc_bias_stride, const float* arm_q_des, const float* tau_limit, int flags,
+                        float* tau, float* leg_force, float* foot, int32_t* info, void* stream);
+
 /* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and
  * of nudot(q, nu, tau) in the coordinates of wbc_sim_body_dynamics, from the sim's current root / DoF state, WBC_T_BODY_PARAMS and all
  * three gravity components. The sim's state is read, never written.

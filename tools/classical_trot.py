@@ -2,7 +2,7 @@
 (task QP) -> set_dof_forces -> simulate, every layer one HIP launch, and report what happened. Nothing here is tuned: the gains are the
 defaults of BaseStateEstimator, FootstepPlanner, CentroidalMPC and whole_body_controller.
 
-  python tools/classical_trot.py [--envs 64] [--seconds 4] [--speed 0.3] [--gait trot] [--detector]
+  python tools/classical_trot.py [--envs 64] [--seconds 4] [--speed 0.3] [--gait trot] [--detector] [--controller qp|leg] [--height H]
 
 Prints, once per simulated second and at the end: the share of envs still upright (trunk z axis within 0.5 rad of vertical and the trunk
 above 0.15 m), the mean forward speed of the upright envs against the command, and the MPC / QP / planner status counts.
@@ -10,7 +10,13 @@ above 0.15 m), the mean forward speed of the upright envs against the command, a
 --detector (default off) puts the contact detector (env.contact_detector: momentum observer + wbc_sim_contact_detect) into the loop: the
 estimator takes det.prob instead of the planner's schedule and the whole-body controller det.stance instead of planner.stance. It then
 also prints how often det.contact agrees with env.get_foot_contacts() and the counts of EARLY / LATE foot-steps. Feeding the touchdown
-events back into the planner's clock is not covered: the planner still swings and places the feet by its own schedule."""
+events back into the planner's clock is not covered: the planner still swings and places the feet by its own schedule.
+
+--controller leg (default qp) replaces the whole-body task QP by the leg controller (env.leg_controller: wbc_sim_leg_control), the layer the
+MPC's source paper runs: stance legs push with mpc.forces (tau = -J^T f), swing legs follow planner.swing_ref by a Cartesian impedance
+with the acceleration feed-forward, the arm holds its default posture; the stance weights are planner.contact, or det.prob with
+--detector. It then prints the counts of the controller's info bits instead of the QP's status. --height H hands the MPC a reference
+height of the centre of mass (default: the current one, so that nothing pulls a sagging trunk back up)."""
 import argparse
 import os
 import sys
@@ -23,6 +29,8 @@ ap.add_argument("--speed", type=float, default=0.3)
 ap.add_argument("--gait", default="trot")
 ap.add_argument("--settle", type=float, default=0.5, help="seconds of standing (gait stand) before the gait starts")
 ap.add_argument("--detector", action="store_true", help="contact flags from proprioception instead of the planner's schedule")
+ap.add_argument("--controller", choices=("qp", "leg"), default="qp", help="whole-body task QP, or the leg controller on the MPC's forces")
+ap.add_argument("--height", type=float, default=None, help="reference height of the centre of mass for the MPC (default: the current one)")
 a = ap.parse_args()
 
 sys.path.insert(0, os.path.join(ROOT, "deep-whole-body-control_amd"))
@@ -48,7 +56,8 @@ cmd = torch.tensor([[a.speed, 0.0]], device=dev).expand(n, 2).contiguous()
 wz = torch.zeros(n, device=dev)
 decimation = int(env.cfg.control.decimation)
 steps, settle = int(round(a.seconds / env.dt)), int(round(a.settle / env.dt))
-counts = dict(mpc=Counter(), qp=Counter(), no_safe=0, failed=0)
+counts = dict(mpc=Counter(), qp=Counter(), no_safe=0, failed=0, leg=Counter())
+ctl = env.leg_controller() if a.controller == "leg" else None
 dets = {id(stand): env.contact_detector(planner=stand), id(walk): env.contact_detector(planner=walk)} if a.detector else None
 agree, events, tau = [0, 0], dict(early=0, late=0, touchdown=0, liftoff=0), None
 x_start = env.root_states[:, 0].clone()
@@ -82,14 +91,22 @@ for k in range(steps):
     else:
         est.update(contact=planner.contact)
     planner.update(c, wz, state=est)
-    mpc.solve(planner.contact_schedule, c, wz, foot_positions=planner.foot_positions, state=est)
-    tau, nudot, lam, info = env.whole_body_controller(base_acc=mpc.base_acc, swing_acc=planner.swing_acc,
-                                                      stance=det.stance if a.detector else planner.stance)
+    mpc.solve(planner.contact_schedule, c, wz, height=a.height, foot_positions=planner.foot_positions, state=est)
+    if ctl is not None:
+        tau = ctl.update(forces=mpc.forces, swing_ref=planner.swing_ref, stance=det.prob if a.detector else planner.contact, state=est)
+    else:
+        tau, nudot, lam, info = env.whole_body_controller(base_acc=mpc.base_acc, swing_acc=planner.swing_acc,
+                                                          stance=det.stance if a.detector else planner.stance)
     env.sim.set_dof_forces(tau.contiguous())
     for _ in range(decimation):
         env.sim.simulate()
     counts["mpc"].update(mpc.status.cpu().tolist())
-    counts["qp"].update(info["status"].cpu().tolist())
+    if ctl is not None:
+        word = ctl.info
+        counts["leg"].update(dict(failed=int((word & 2 != 0).sum()), ff_singular=int(((word >> 8) & 15 != 0).sum()),
+                                  saturated_leg=int(((word >> 12) & 15 != 0).sum()), saturated_arm=int(((word >> 16) & 1 != 0).sum())))
+    else:
+        counts["qp"].update(info["status"].cpu().tolist())
     counts["no_safe"] += int(((planner.info >> 4) & 15 != 0).sum())
     counts["failed"] += int((planner.info & 2 != 0).sum())
     if a.detector and k >= settle:
@@ -100,7 +117,9 @@ for k in range(steps):
     if (k + 1) % int(round(1.0 / env.dt)) == 0:
         report(f"t = {(k + 1) * env.dt:.2f} s", k)
 report("end", steps - 1)
-print(f"MPC status counts (0 ok, 1 iterations, 2 failed): {dict(counts['mpc'])}; QP status counts (0 optimal, 1 / 2 clamped): {dict(counts['qp'])}; "
+second = (f"leg controller, env-steps with the bit: {dict(counts['leg'])}" if ctl is not None else
+          f"QP status counts (0 optimal, 1 / 2 clamped): {dict(counts['qp'])}")
+print(f"MPC status counts (0 ok, 1 iterations, 2 failed): {dict(counts['mpc'])}; {second}; "
       f"planner: {counts['no_safe']} env-steps with NO_SAFE, {counts['failed']} FAILED", flush=True)
 if a.detector:
     print(f"detector: det.contact equals get_foot_contacts() in {agree[0] / max(agree[1], 1):.3f} of the upright foot-steps; foot-steps flagged "
