@@ -17,6 +17,7 @@
 #include "wbc_footstep.h"
 #include "wbc_contact.h"
 #include "wbc_legctl.h"
+#include "wbc_attitude.h"
 #include "wbc_mpc.h"
 
 #define ARM_N 6
@@ -4640,5 +4641,45 @@ extern "C" int wbc_sim_leg_control(wbc_sim* s, const wbc_leg_control_cfg* cfg, c
   if (narm != LC_ARM_DOFS || nfinger != max_finger || nlive != LC_NLIMIT) return c.fail(-3, "the model does not have exactly six arm DoFs beside the legs and the locked fingers");
   if (c.n <= 0) return 0;
   wbc_legctl_launch(K, *cfg, a, stream);
+  return c.launched();
+}
+
+// ---- attitude filter (include/wbc_sim.h: wbc_sim_attitude_filter) ---------------------------------------------------------------------------
+// The host side; the kernel is in wbc_attitude_kernel.hip, its argument struct in wbc_attitude.h.
+extern "C" int wbc_sim_attitude_filter(wbc_sim* s, const wbc_attitude_cfg* cfg, const float* gyro, const float* accel, const float* aux_body,
+                                       const float* aux_world, const float* aux_sigma, int num_aux, const int32_t* reset_mask,
+                                       const float* q_init, int flags, float* q, float* b, float* P, float* gyro_out, float* gravity_body,
+                                       float* nis, int32_t* status, void* stream) {
+  WbCall c("wbc_sim_attitude_filter", s, stream);
+  // the arguments first, so that every refusal below can be met (and tested) without a sim; then the sim
+  if (!cfg) return c.fail(-1, "cfg is NULL");
+  if (!q || !b || !P) return c.fail(-1, "q, b or P is NULL");
+  if (num_aux < 0 || num_aux > WBC_ATTITUDE_MAX_AUX) return c.fail(-1, "num_aux must be in 0 .. 4");
+  if (num_aux > 0 && (!aux_body || !aux_world || !aux_sigma)) return c.fail(-1, "num_aux > 0 needs aux_body, aux_world and aux_sigma");
+  if (flags & ~WBC_ATTITUDE_RESET) return c.fail(-1, "unknown flag bits");
+  auto positive = [](float v) { return v > 0.f && v <= 3.4e38f; };
+  if (!positive(cfg->dt)) return c.fail(-1, "dt must be finite and > 0");
+  if (!positive(cfg->sigma_g) || !positive(cfg->sigma_b) || !positive(cfg->sigma_a)) return c.fail(-1, "every sigma must be finite and > 0");
+  if (!positive(cfg->p0_theta) || !positive(cfg->p0_b)) return c.fail(-1, "every initial variance must be finite and > 0");
+  if (!(cfg->kappa_a >= 0.f) || !(cfg->kappa_a <= 3.4e38f)) return c.fail(-1, "kappa_a must be finite and >= 0");
+  if (((uintptr_t)gyro | (uintptr_t)accel | (uintptr_t)aux_body | (uintptr_t)aux_world | (uintptr_t)aux_sigma | (uintptr_t)reset_mask |
+       (uintptr_t)q_init | (uintptr_t)q | (uintptr_t)b | (uintptr_t)P | (uintptr_t)gyro_out | (uintptr_t)gravity_body | (uintptr_t)nis |
+       (uintptr_t)status) & 3u)
+    return c.fail(-1, "every pointer must be 4-byte aligned");
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  AtArgs a = {c.root, gyro, accel, aux_body, aux_world, aux_sigma, q_init, reset_mask, num_aux, (flags & WBC_ATTITUDE_RESET) ? 1 : 0, c.n};
+  const float* g = c.hc->cfg.gravity;
+  a.gnorm = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+  if (!positive(a.gnorm)) return c.fail(-1, "gravity is zero");
+  for (int j = 0; j < 3; ++j) a.up[j] = -g[j] / a.gnorm;
+  // the half turn's axis: normalise(c x up), c the world x axis where |up_x| <= 0.9 and the world y axis otherwise
+  const bool cx = fabsf(a.up[0]) <= 0.9f;
+  const float h[3] = {cx ? 0.f : a.up[2], cx ? -a.up[2] : 0.f, cx ? a.up[1] : -a.up[0]};
+  const float hn = sqrtf(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
+  for (int j = 0; j < 3; ++j) a.half[j] = h[j] / hn;
+  a.q = q; a.b = b; a.P = P; a.gyro_out = gyro_out; a.gravity_body = gravity_body; a.nis = nis; a.status = status;
+  if (c.n <= 0) return 0;
+  wbc_attitude_launch(*cfg, a, stream);
   return c.launched();
 }

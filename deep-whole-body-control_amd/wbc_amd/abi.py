@@ -173,6 +173,23 @@ class WbcLegControlCfg(C.Structure):
                 ("kp_arm", f32 * 6), ("kd_arm", f32 * 6), ("arm_q_default", f32 * 6)]
 
 
+ATTITUDE_RESET = 1          # WBC_ATTITUDE_RESET (wbc_sim_attitude_filter's own flags word)
+ATTITUDE_MAX_AUX = 4        # WBC_ATTITUDE_MAX_AUX
+ATTITUDE_ANTIPARALLEL = 1e-6  # WBC_ATTITUDE_ANTIPARALLEL
+ATTITUDE_STATUS_MASK = 15   # WBC_ATTITUDE_STATUS_MASK: status & mask is one of the four codes below
+ATTITUDE_STATUS_OK, ATTITUDE_STATUS_RESET, ATTITUDE_STATUS_FAILED, ATTITUDE_STATUS_FAILED_PIVOT = 0, 1, 2, 3   # WBC_ATTITUDE_STATUS_*
+ATTITUDE_INFO_ZERO, ATTITUDE_INFO_PIVOT = 16, 512   # WBC_ATTITUDE_INFO_*, << measurement (0 the accelerometer, 1 + k aux k)
+ATTITUDE_INFO_HALF_TURN = 16384
+
+
+class WbcAttitudeCfg(C.Structure):
+    """wbc_attitude_cfg (include/wbc_sim.h): the host scalars of wbc_sim_attitude_filter."""
+    _fields_ = [(name, f32) for name in ("dt", "sigma_g", "sigma_b", "sigma_a", "kappa_a", "p0_theta", "p0_b")]
+
+
+AttitudeCfg = WbcAttitudeCfg
+
+
 class WbcTaskQpLimits(C.Structure):
     """wbc_taskqp_limits (include/wbc_sim.h): the host scalars of wbc_sim_task_inverse_dynamics_qp; max_iter 0 = the default."""
     _fields_ = [("mu", f32), ("fn_min", f32), ("max_iter", i32)]

@@ -813,6 +813,18 @@ class WidowGo1(LeggedRobot):
         fields of wbc_leg_control_cfg, plus bias, tau_limit and clip)."""
         return LegController(self, **cfg)
 
+    # ---- attitude estimation (no counterpart in the reference): include/wbc_sim.h: wbc_sim_attitude_filter ----
+    def attitude_estimator(self, **cfg) -> "AttitudeEstimator":
+        """The attitude filter: the trunk's orientation and the gyro's bias from the gyro, the accelerometer and optional heading
+        vectors, the estimate of what the other layers take as quat and gyro: see AttitudeEstimator (cfg: the fields of
+        wbc_attitude_cfg; dt None: env.dt)."""
+        return AttitudeEstimator(self, **cfg)
+
+    def imu(self, gyro_bias=0.0, gyro_noise: float = 0.0, accel_noise: float = 0.0, heading_noise: float = None, seed: int = 0) -> "ImuModel":
+        """A small IMU model on the sim's state: gyro, accelerometer and (with heading_noise not None) a heading vector in trunk axes,
+        with a constant gyro bias and seeded Gaussian noise: see ImuModel."""
+        return ImuModel(self, gyro_bias, gyro_noise, accel_noise, heading_noise, seed)
+
     # ---- torque supervision (WG:1178-1181, 1201-1242): default off (WGC:173) ------------------------------------
     def _refresh_arm_dynamics(self):
         self.mm, self.ee_j_eef, self._g_torque = self.sim.arm_dynamics(self._arm_link_rb, self.robot_model.rb_mass[-9:])
@@ -1603,3 +1615,123 @@ class LegController:
         self.last_inputs = dict(kw)
         env.sim.leg_control(self.cfg, tau=self.tau, leg_force=self.leg_force, foot=self.foot, info=self.info, **kw)
         return self.tau
+
+
+class AttitudeEstimator:
+    """The attitude filter of wbc_sim_attitude_filter for every env (a multiplicative extended Kalman filter; Markley, JGCD 2003): it owns
+    the orientation quat [N, 4] (xyzw), the gyro bias [N, 3], the covariance P [N, 6, 6] of (dtheta, db) and every output, and advances
+    them by one launch per update(). Keyword arguments are the fields of wbc_attitude_cfg (include/wbc_sim.h); dt defaults to env.dt. The
+    defaults are UNTUNED. The estimator starts reset at the sim's quaternion. Use it as
+        gyro, accel, heading = imu.read()                # after env.step() or the simulate calls
+        att.update(gyro=gyro, accel=accel, aux=(heading, imu.heading_world, 0.05))
+        est.update(quat=att.quat, gyro=att.gyro, accel=accel)
+    Not covered: yaw from the leg kinematics (without an aux vector the heading drifts with the gyro's bias about gravity), the covariance
+    reset after the multiplicative update, an accelerometer bias, the lever arm of an IMU away from the trunk's origin, and a quat argument
+    for the planner, the detector and the leg controller classes, which keep reading the sim's quaternion."""
+
+    DEFAULTS = dict(sigma_g=0.005, sigma_b=1e-4, sigma_a=0.02, kappa_a=100.0, p0_theta=0.25, p0_b=1e-3)
+
+    def __init__(self, env, dt: float = None, **cfg):
+        unknown = set(cfg) - set(self.DEFAULTS)
+        assert not unknown, f"unknown attitude parameters: {sorted(unknown)}"
+        v = dict(self.DEFAULTS, **cfg)
+        self.env = env
+        self.cfg = abi.WbcAttitudeCfg(float(env.dt if dt is None else dt), *[float(v[k]) for k in self.DEFAULTS])
+        n, dev = env.num_envs, env.device
+        z = lambda *sh, dtype=torch.float32: torch.zeros(sh, dtype=dtype, device=dev)
+        self.quat, self.bias, self.P = z(n, 4), z(n, 3), z(n, 6, 6)
+        self.quat[:, 3] = 1.0
+        self.gyro, self.gravity_body, self.status = z(n, 3), z(n, 3), z(n, dtype=torch.int32)
+        self.nis = z(n, 1)
+        self.last_inputs = None
+        self.reset()
+
+    def _launch(self, gyro=None, accel=None, aux=None, reset_mask=None, q_init=None, reset=False) -> None:
+        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        n, dev = self.env.num_envs, self.env.device
+        body = world = sigma = None
+        if aux is not None:
+            body, world, sigma = aux
+            body = f(body).reshape(n, -1, 3)
+            k = body.shape[1]
+            world = f(torch.as_tensor(world, dtype=torch.float32, device=dev)).expand(n, k, 3).contiguous()
+            sigma = f(torch.as_tensor(sigma, dtype=torch.float32, device=dev)).expand(n, k).contiguous()
+        k = 0 if body is None else int(body.shape[1])
+        if tuple(self.nis.shape) != (n, 1 + k):
+            self.nis = torch.zeros((n, 1 + k), dtype=torch.float32, device=dev)
+        kw = dict(gyro=f(gyro), accel=f(accel), aux_body=body, aux_world=world, aux_sigma=sigma, reset_mask=reset_mask, q_init=f(q_init), reset=reset)
+        self.last_inputs = dict(kw)
+        self.env.sim.attitude_filter(self.cfg, self.quat, self.bias, self.P, gyro_out=self.gyro, gravity_body=self.gravity_body, nis=self.nis,
+                                     status=self.status, **kw)
+
+    def reset(self, env_ids=None, quat=None, from_accel: bool = False, accel=None) -> None:
+        """Reset every env (env_ids None) or the listed ones: zero bias, the initial covariance, and the orientation quat [N, 4] (None: the
+        sim's quaternion; with from_accel the tilt of accel [N, 3] -- None: the identity -- and zero yaw). One launch; the other envs are
+        left as they are."""
+        env = self.env
+        q_init = None if from_accel else (env.base_quat if quat is None else quat)
+        if env_ids is None:
+            self._launch(accel=accel if from_accel else None, q_init=q_init, reset=True)
+            return
+        mask = torch.zeros((env.num_envs,), dtype=torch.int32, device=env.device)
+        mask[torch.as_tensor(env_ids, dtype=torch.long, device=env.device)] = 1
+        tensors = (self.quat, self.bias, self.P, self.gyro, self.gravity_body, self.status)
+        keep = [t.clone() for t in tensors]
+        self._launch(accel=accel if from_accel else None, q_init=q_init, reset_mask=mask)
+        rest = mask == 0                                                            # the launch also advanced the others: put them back
+        for t, k in zip(tensors, keep):
+            t[rest] = k[rest]
+
+    def update(self, gyro=None, accel=None, aux=None) -> torch.Tensor:
+        """One update over env.dt at the sim's current state, to be called once per control step; returns quat [N, 4]. gyro [N, 3] and
+        accel [N, 3] in trunk axes, what ImuModel.read() returns (gyro None: the sim's angular velocity, no bias; accel None: no
+        gravity row); aux: (body [N, K, 3] or [N, 3], world [K, 3] or [3], sigma [K] or a number) direction measurements, K <= 4. Envs
+        flagged in env.reset_buf are reset at the sim's quaternion. Results: .quat, .bias, .P, .gyro (= gyro - bias), .gravity_body,
+        .nis, .status; the tensors handed to the kernel are kept in last_inputs."""
+        env = self.env
+        self._launch(gyro=gyro, accel=accel, aux=aux, reset_mask=env.reset_buf.to(torch.int32), q_init=env.base_quat)
+        return self.quat
+
+
+class ImuModel:
+    """An IMU on the trunk's origin read from the sim's state, torch ops only: read() returns (gyro, accel, heading) in trunk axes.
+    gyro = R^T omega + bias + noise, with a constant per-env bias (gyro_bias: a number, three numbers or [N, 3]); accel = the specific
+    force R^T ((v - v_prev) / dt - g) + noise from the finite difference of the root's world velocity between two reads (what
+    BaseStateEstimator.update computes inline); heading = R^T heading_world + noise, the world x axis (None without heading_noise). The
+    noises are standard deviations per component and sample, drawn from a torch.Generator on the device seeded with `seed`."""
+
+    def __init__(self, env, gyro_bias=0.0, gyro_noise: float = 0.0, accel_noise: float = 0.0, heading_noise: float = None, seed: int = 0):
+        self.env = env
+        n, dev = env.num_envs, env.device
+        self.gyro_bias = torch.as_tensor(gyro_bias, dtype=torch.float32, device=dev).expand(n, 3).clone() if hasattr(gyro_bias, "__len__") \
+            else torch.full((n, 3), float(gyro_bias), dtype=torch.float32, device=dev)
+        self.gyro_noise, self.accel_noise, self.heading_noise = float(gyro_noise), float(accel_noise), heading_noise
+        self.heading_world = torch.tensor([1.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+        self.generator = torch.Generator(device=dev)
+        self.generator.manual_seed(int(seed))
+        self._gravity = torch.tensor(list(env.tcfg.gravity), dtype=torch.float32, device=dev)
+        self._last_root_vel = env.root_states[:, 7:10].clone()
+
+    def _noise(self, std: float) -> torch.Tensor:
+        n, dev = self.env.num_envs, self.env.device
+        return std * torch.randn((n, 3), dtype=torch.float32, device=dev, generator=self.generator)
+
+    def reset(self) -> None:
+        """Forget the previous velocity: the next read's acceleration is that of a trunk at rest."""
+        self._last_root_vel.copy_(self.env.root_states[:, 7:10])
+
+    def read(self, dt: float = None):
+        """(gyro [N, 3], accel [N, 3], heading [N, 3] or None) at the sim's current state; dt: the time since the previous read (None:
+        env.dt). Envs flagged in env.reset_buf read the acceleration of a trunk at rest."""
+        env = self.env
+        dt = float(env.dt if dt is None else dt)
+        quat, vel = env.base_quat, env.root_states[:, 7:10]
+        last = torch.where(env.reset_buf.bool()[:, None], vel, self._last_root_vel)
+        a_world = (vel - last) / dt - self._gravity
+        self._last_root_vel.copy_(vel)
+        gyro = _quat_rotate_inverse(quat, env.root_states[:, 10:13]) + self.gyro_bias + self._noise(self.gyro_noise)
+        accel = _quat_rotate_inverse(quat, a_world) + self._noise(self.accel_noise)
+        heading = None
+        if self.heading_noise is not None:
+            heading = _quat_rotate_inverse(quat, self.heading_world.expand(env.num_envs, 3)) + self._noise(float(self.heading_noise))
+        return gyro.contiguous(), accel.contiguous(), heading

@@ -773,6 +773,40 @@ class WbcSim:
                                          ptr(acc_bias), strides["acc_bias"], ptr(arm_q_des), ptr(tau_limit), abi.LEGCTL_CLIP if clip else 0,
                                          *[ptr(outputs.get(k)) for k in self.LEGCTL_OUTPUTS], self._stream()), "wbc_sim_leg_control")
 
+    # ---- attitude filter (include/wbc_sim.h: wbc_sim_attitude_filter) ------------------------------------------------------------------------
+    ATTITUDE_OUTPUTS = ("gyro_out", "gravity_body", "nis", "status")
+
+    def attitude_filter(self, cfg: "abi.WbcAttitudeCfg", q: torch.Tensor, b: torch.Tensor, P: torch.Tensor,
+                        gyro: Optional[torch.Tensor] = None, accel: Optional[torch.Tensor] = None, aux_body: Optional[torch.Tensor] = None,
+                        aux_world: Optional[torch.Tensor] = None, aux_sigma: Optional[torch.Tensor] = None,
+                        reset_mask: Optional[torch.Tensor] = None, q_init: Optional[torch.Tensor] = None, reset: bool = False, **outputs) -> None:
+        """One wbc_sim_attitude_filter launch on the current stream: one predict + correct of the caller-owned orientation q f32 [N, 4]
+        (xyzw), gyro bias b f32 [N, 3] and covariance P f32 [N, 6, 6] of the error state (dtheta, db), in place. gyro [N, 3] in trunk axes
+        (None: the sim's angular velocity, no bias); accel [N, 3] the specific force in trunk axes (None: no gravity row); aux_body and
+        aux_world [N, K, 3] with aux_sigma [N, K], K <= 4: further directions measured in trunk axes and known in world axes (sigma <= 0:
+        skipped). reset=True resets every env, reset_mask int32 [N] the envs whose entry is not 0, to q_init [N, 4] (None: from accel, or
+        the identity). Outputs by keyword, each a caller-owned tensor that is filled (ATTITUDE_OUTPUTS): gyro_out [N, 3] = gyro - b,
+        gravity_body [N, 3], nis [N, 1 + K], status int32 [N]."""
+        n = self.num_envs
+        unknown = set(outputs) - set(self.ATTITUDE_OUTPUTS)
+        assert not unknown, f"unknown outputs: {sorted(unknown)}"
+        f32, i32 = torch.float32, torch.int32
+        k = 0 if aux_sigma is None else int(aux_sigma.shape[1])
+        assert (aux_body is None) == (aux_world is None) == (aux_sigma is None), "aux_body, aux_world and aux_sigma go together"
+        shapes = dict(gyro_out=((n, 3), f32), gravity_body=((n, 3), f32), nis=((n, 1 + k), f32), status=((n,), i32))
+        checks = [(q, (n, 4), f32), (b, (n, 3), f32), (P, (n, 6, 6), f32), (gyro, (n, 3), f32), (accel, (n, 3), f32), (aux_body, (n, k, 3), f32),
+                  (aux_world, (n, k, 3), f32), (aux_sigma, (n, k), f32), (reset_mask, (n,), i32), (q_init, (n, 4), f32)]
+        checks += [(outputs.get(name),) + shapes[name] for name in self.ATTITUDE_OUTPUTS]
+        for t, sh, dt in checks:
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == sh, (tuple(t.shape), sh)
+        assert q is not None and b is not None and P is not None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None
+        check(self.L.wbc_sim_attitude_filter(self.h, C.byref(cfg), ptr(gyro), ptr(accel), ptr(aux_body), ptr(aux_world), ptr(aux_sigma), k,
+                                             ptr(reset_mask), ptr(q_init), abi.ATTITUDE_RESET if reset else 0, q.data_ptr(), b.data_ptr(),
+                                             P.data_ptr(), *[ptr(outputs.get(name)) for name in self.ATTITUDE_OUTPUTS], self._stream()),
+              "wbc_sim_attitude_filter")
+
     def proximity_damper_rows(self, gap: torch.Tensor, jac: torch.Tensor, d_safe: float, d_influence: float, xi: float, dt: float,
                               nu: Optional[torch.Tensor] = None):
         """The velocity damper of the pairs inside the influence distance as rows on the accelerations, torch ops only: the gap rate

@@ -1345,6 +1345,88 @@ int wbc_sim_leg_control(wbc_sim* sim, const wbc_leg_control_cfg* cfg, const floa
                         const float* acc_bias, int acc_bias_stride, const float* arm_q_des, const float* tau_limit, int flags,
                         float* tau, float* leg_force, float* foot, int32_t* info, void* stream);
 
+/* One update of the attitude filter, the estimator of what wbc_sim_leg_odometry, wbc_sim_footstep_plan, wbc_sim_contact_detect and
+ * wbc_sim_leg_control take as `quat` and `gyro`: the trunk's orientation and the gyro's bias from the gyro, the accelerometer's gravity
+ * direction and up to WBC_ATTITUDE_MAX_AUX further direction measurements (a compass, say). A multiplicative extended Kalman filter on
+ * the unit quaternion (Markley, "Attitude error representations for Kalman filtering", JGCD 2003; the error-state algebra of Trawny and
+ * Roumeliotis, "Indirect Kalman filter for 3D attitude estimation", 2005). OURS, not the papers': quaternions are xyzw (Hamilton product,
+ * scalar last) and R(q) maps trunk axes to world axes as everywhere in this header (Trawny and Roumeliotis use the JPL product and the
+ * opposite map); the error is a rotation vector in TRUNK axes applied on the right, R_true = R(q) exp([dtheta]x) (Markley applies his
+ * on the other side); the bias error is db = b_true - b; the correction runs as sequential 3-row updates in square-root form (W = L^-1 H P),
+ * not with one gain matrix. One launch (wbc_attitude_filter_kernel); the sim's state is read, never written. Per env the caller owns
+ * q      device f32 [N, 4], xyzw, unit: taken as stored (not normalised on reading), written normalised;
+ * b      device f32 [N, 3], the gyro's bias in trunk axes, rad/s;
+ * P      device f32 [N, 6, 6], the covariance of the error state (dtheta, db). P is read as a symmetric matrix (its lower triangle is
+ *        read) and written bit-symmetric.
+ * INPUTS of one update over a step cfg->dt that ends now:
+ * gyro   device f32 [N, 3] or NULL: the measured angular velocity in trunk axes. NULL: ROOT_STATES' world angular velocity rotated by
+ *        R^T of ROOT_STATES' quaternion, normalised (wbc_sim_leg_odometry's rule).
+ * accel  device f32 [N, 3] or NULL: the specific force in trunk axes, wbc_sim_leg_odometry's convention (a = R accel + g with
+ *        wbc_task_cfg.gravity, which must not be zero). NULL: no gravity row.
+ * aux_body, aux_world  device f32 [N, K, 3], aux_sigma device f32 [N, K], K = num_aux in 0 .. WBC_ATTITUDE_MAX_AUX (all three NULL or
+ *        unread with K = 0): a direction measured in trunk axes, the same direction known in world axes (both normalised in the call)
+ *        and the standard deviation of each component of the normalised measurement. An entry whose sigma is <= 0 is skipped and its
+ *        vectors are never read.
+ * With exp(phi) = (phi / |phi| sin(|phi| / 2), cos(|phi| / 2)), and for |phi| < 1e-4 the series (phi / 2 (1 - |phi|^2 / 24), 1 - |phi|^2 / 8)
+ * (so that exp(0) = (0, 0, 0, 1) exactly and q (x) exp(0) has q's bits), normalise(q) = q / sqrt(q . q) and gn = |gravity|:
+ *   predict   w = gyro - b, dq = exp(w dt), q- = normalise(q (x) dq); with A = R(dq)^T and G = A P_tb:
+ *             P-_tt = A P_tt A^T - dt (G + G^T) + dt^2 P_bb + dt sigma_g^2 I, P-_tb = G - dt P_bb, P-_bb = P_bb + dt sigma_b^2 I
+ *             (= Phi P Phi^T + Q with Phi = [[A, -dt I], [0, I]], Q = dt diag(sigma_g^2 I, sigma_b^2 I));
+ *   correct   one 3-row update per measurement j, the accelerometer (j = 0) first, then aux 0 .. K-1 (j = 1 + k), each on the result
+ *             of the one before: world unit vector w_j (the accelerometer's: -gravity / gn; aux: aux_world / |aux_world|), measured
+ *             u (accel; aux_body), m = u / |u|, mh = R(q)^T w_j, e = m - mh, H = [[mh]x, 0] (d mh / d dtheta = [mh]x), per-component
+ *             variance r = sigma^2; the accelerometer's r = sigma_a^2 (1 + kappa_a ((|accel| - gn) / gn)^2): a trunk that accelerates
+ *             or falls is trusted less, continuously, with no gate. S = H P H^T + r I = L L^T row by row as in wbc_sim_contact_detect
+ *             step 3; W = L^-1 H P, y = L^-1 e, dx = W^T y; q <- normalise(q (x) exp(dx[0:3])), b <- b + dx[3:6], P <- P - W^T W,
+ *             nis_j = |y|^2. The reset of the covariance after the multiplicative update (its Jacobian I - [dx_theta / 2]x) is
+ *             first order in the correction and left out.
+ *             A measurement with u . u = 0 (in fp32) is skipped: nis_j = 0 and status bit WBC_ATTITUDE_INFO_ZERO << j (an aux
+ *             entry whose aux_world has zero length likewise). One where a pivot of S is not a positive finite number is skipped and the
+ *             state from before it is kept: nis_j = 0, bit WBC_ATTITUDE_INFO_PIVOT << j, status code WBC_ATTITUDE_STATUS_FAILED_PIVOT.
+ * RESET: with WBC_ATTITUDE_RESET in flags every env, with reset_mask (device int32 [N] or NULL) the envs whose entry is not 0:
+ * b = 0, P = diag(p0_theta I_3, p0_b I_3), nis = 0, status code WBC_ATTITUDE_STATUS_RESET, and
+ *   q = normalise(q_init) with q_init (device f32 [N, 4] or NULL) given;
+ *   else, with accel given and accel . accel != 0, the shortest rotation with R(q) m = w_0: q = normalise((m x w_0, 1 + m . w_0)), which
+ *   fixes the tilt and turns about no vertical axis (zero yaw); where 1 + m . w_0 < WBC_ATTITUDE_ANTIPARALLEL (the trunk upside down, the
+ *   shortest rotation undefined) q = (h, 0), a half turn about h = normalise(c x w_0), c the world x axis where |w_0,x| <= 0.9 and the
+ *   world y axis otherwise, with bit WBC_ATTITUDE_INFO_HALF_TURN;
+ *   else q = (0, 0, 0, 1) (a zero accel with bit WBC_ATTITUDE_INFO_ZERO).
+ * Such an env is neither predicted nor corrected in that call; its q, b, P and the aux inputs are not read.
+ * An env that reads a value that is not finite (gyro and accel are read by every env; the aux vectors and sigma of an entry that is not
+ * skipped, q, b and P's lower triangle by an env that is not reset; q_init by one that is) or whose new state comes out not finite keeps
+ * its state, gets zeros in every float output and status WBC_ATTITUDE_STATUS_FAILED alone; no other env is affected.
+ * OUTPUTS besides q, b and P, each may be NULL and is then not written; what is written does not depend on which are asked for:
+ * gyro_out      device f32 [N, 3] = gyro - b with the b that leaves: what wbc_sim_leg_odometry takes as gyro;
+ * gravity_body  device f32 [N, 3] = R(q)^T gravity / gn with the q that leaves: the estimate of the policy's projected gravity;
+ * nis           device f32 [N, 1 + K], 0 for a row that was skipped or not given;
+ * status        device int32 [N]: a code in the bits WBC_ATTITUDE_STATUS_MASK, OR'ed with the WBC_ATTITUDE_INFO_* bits.
+ * Every pointer needs 4-byte alignment only. Nothing is allocated and nothing synchronises: safe under stream capture. -1 with a message
+ * in wbc_last_error() that names the entry point, nothing written, checked before the sim: NULL cfg, q, b or P; num_aux out of range or
+ * > 0 with a NULL aux pointer; unknown flag bits; dt, a sigma or an initial variance that is not finite and > 0; kappa_a not finite or
+ * < 0; a misaligned pointer. Then NULL sim; zero gravity. -3 / -2 and stream handling as wbc_sim_coriolis. */
+#define WBC_ATTITUDE_MAX_AUX 4
+typedef struct {
+  float dt;                                  /* s */
+  float sigma_g, sigma_b;                    /* noise densities of the gyro (rad/s/sqrt(Hz)) and of the bias's random walk */
+  float sigma_a;                             /* standard deviation of each component of the normalised accelerometer direction */
+  float kappa_a;                             /* inflation of sigma_a^2 by the squared relative excess of |accel| over |gravity| */
+  float p0_theta, p0_b;                      /* the variances a reset starts from */
+} wbc_attitude_cfg;
+#define WBC_ATTITUDE_RESET 1
+#define WBC_ATTITUDE_ANTIPARALLEL 1e-6f
+#define WBC_ATTITUDE_STATUS_MASK 15
+#define WBC_ATTITUDE_STATUS_OK 0
+#define WBC_ATTITUDE_STATUS_RESET 1
+#define WBC_ATTITUDE_STATUS_FAILED 2
+#define WBC_ATTITUDE_STATUS_FAILED_PIVOT 3
+#define WBC_ATTITUDE_INFO_ZERO 16                /* << j: measurement j (0 the accelerometer, 1 + k aux k) had zero length */
+#define WBC_ATTITUDE_INFO_PIVOT 512              /* << j: measurement j's innovation matrix had a failed pivot */
+#define WBC_ATTITUDE_INFO_HALF_TURN 16384        /* the reset from the accelerometer took the half turn */
+int wbc_sim_attitude_filter(wbc_sim* sim, const wbc_attitude_cfg* cfg, const float* gyro, const float* accel, const float* aux_body,
+                            const float* aux_world, const float* aux_sigma, int num_aux, const int32_t* reset_mask, const float* q_init,
+                            int flags, float* q, float* b, float* P, float* gyro_out, float* gravity_body, float* nis, int32_t* status,
+                            void* stream);
+
 /* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and
  * of nudot(q, nu, tau) in the coordinates of wbc_sim_body_dynamics, from the sim's current root / DoF state, WBC_T_BODY_PARAMS and all
  * three gravity components. The sim's state is read, never written.

@@ -3,6 +3,7 @@
 defaults of BaseStateEstimator, FootstepPlanner, CentroidalMPC and whole_body_controller.
 
   python tools/classical_trot.py [--envs 64] [--seconds 4] [--speed 0.3] [--gait trot] [--detector] [--controller qp|leg] [--height H]
+                                 [--attitude [--gyro-bias B]]
 
 Prints, once per simulated second and at the end: the share of envs still upright (trunk z axis within 0.5 rad of vertical and the trunk
 above 0.15 m), the mean forward speed of the upright envs against the command, and the MPC / QP / planner status counts.
@@ -16,7 +17,13 @@ events back into the planner's clock is not covered: the planner still swings an
 MPC's source paper runs: stance legs push with mpc.forces (tau = -J^T f), swing legs follow planner.swing_ref by a Cartesian impedance
 with the acceleration feed-forward, the arm holds its default posture; the stance weights are planner.contact, or det.prob with
 --detector. It then prints the counts of the controller's info bits instead of the QP's status. --height H hands the MPC a reference
-height of the centre of mass (default: the current one, so that nothing pulls a sagging trunk back up)."""
+height of the centre of mass (default: the current one, so that nothing pulls a sagging trunk back up).
+
+--attitude (default off) puts the attitude filter (env.attitude_estimator: wbc_sim_attitude_filter) into the loop on an IMU model
+(env.imu: gyro noise 0.002 rad/s, accelerometer noise 0.05 m/s^2, a heading vector with noise 0.01, and --gyro-bias B rad/s on every
+axis): the leg-odometry estimator takes att.quat, att.gyro and the IMU's accelerometer instead of the sim's true orientation and angular
+velocity. The planner, the detector and the controllers keep reading the sim's quaternion. It then also prints, once per simulated
+second, the tilt and heading errors of att.quat against the sim's quaternion and the bias error."""
 import argparse
 import os
 import sys
@@ -31,6 +38,8 @@ ap.add_argument("--settle", type=float, default=0.5, help="seconds of standing (
 ap.add_argument("--detector", action="store_true", help="contact flags from proprioception instead of the planner's schedule")
 ap.add_argument("--controller", choices=("qp", "leg"), default="qp", help="whole-body task QP, or the leg controller on the MPC's forces")
 ap.add_argument("--height", type=float, default=None, help="reference height of the centre of mass for the MPC (default: the current one)")
+ap.add_argument("--attitude", action="store_true", help="orientation and gyro for the leg odometry from the attitude filter on an IMU model")
+ap.add_argument("--gyro-bias", type=float, default=0.0, help="constant gyro bias of the IMU model, rad/s on every axis (with --attitude)")
 a = ap.parse_args()
 
 sys.path.insert(0, os.path.join(ROOT, "deep-whole-body-control_amd"))
@@ -60,6 +69,8 @@ counts = dict(mpc=Counter(), qp=Counter(), no_safe=0, failed=0, leg=Counter())
 ctl = env.leg_controller() if a.controller == "leg" else None
 dets = {id(stand): env.contact_detector(planner=stand), id(walk): env.contact_detector(planner=walk)} if a.detector else None
 agree, events, tau = [0, 0], dict(early=0, late=0, touchdown=0, liftoff=0), None
+att = env.attitude_estimator() if a.attitude else None
+imu = env.imu(gyro_bias=a.gyro_bias, gyro_noise=0.002, accel_noise=0.05, heading_noise=0.01, seed=2) if a.attitude else None
 x_start = env.root_states[:, 0].clone()
 
 
@@ -74,6 +85,19 @@ def report(label, k):
     vx = env.root_states[:, 7][up].mean().item() if bool(up.any()) else float("nan")
     print(f"{label}: upright {float(up.float().mean()):.3f}, mean forward speed of the upright envs {vx:.3f} m/s (command {a.speed if k >= settle else 0.0:.2f}), "
           f"mean trunk height {env.root_states[:, 2].mean().item():.3f} m, travelled {float((env.root_states[:, 0] - x_start).mean()):.3f} m", flush=True)
+    if att is not None:
+        qe, qs = att.quat[up], env.root_states[:, 3:7][up]
+
+        def zx(q):                                                                      # R^T z (the tilt) and the heading of R's x axis
+            x, y, z, w = q.unbind(-1)
+            return (torch.stack([2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=-1),
+                    torch.atan2(2 * (x * y + w * z), 1 - 2 * (y * y + z * z)))
+        (ze, he), (zs, hs) = zx(qe), zx(qs)
+        tilt = torch.acos((ze * zs).sum(-1).clamp(-1, 1))
+        head = torch.atan2(torch.sin(he - hs), torch.cos(he - hs)).abs()
+        berr = (att.bias[up] - a.gyro_bias).abs().max(dim=-1).values
+        stat = lambda t: f"mean {t.mean().item():.4f} max {t.max().item():.4f}" if t.numel() else "no upright env"
+        print(f"    attitude of the upright envs: tilt error {stat(tilt)} rad, heading error {stat(head)} rad, bias error {stat(berr)} rad/s", flush=True)
 
 
 planner = stand
@@ -84,12 +108,17 @@ for k in range(steps):
         if a.detector:
             dets[id(walk)].reset()
     c = cmd if k >= settle else zero
+    ekw = {}
+    if att is not None:
+        gyro, accel, heading = imu.read()
+        att.update(gyro=gyro, accel=accel, aux=(heading, imu.heading_world, 0.05))
+        ekw = dict(quat=att.quat, gyro=att.gyro, accel=accel)
     if a.detector:
         det = dets[id(planner)]
         det.update(torques=tau)                                                        # tau: what the last simulate calls applied (None at the start: env.torques)
-        est.update(contact=det.prob)
+        est.update(contact=det.prob, **ekw)
     else:
-        est.update(contact=planner.contact)
+        est.update(contact=planner.contact, **ekw)
     planner.update(c, wz, state=est)
     mpc.solve(planner.contact_schedule, c, wz, height=a.height, foot_positions=planner.foot_positions, state=est)
     if ctl is not None:
