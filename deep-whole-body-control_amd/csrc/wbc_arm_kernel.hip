@@ -18,6 +18,7 @@
 #include "wbc_contact.h"
 #include "wbc_legctl.h"
 #include "wbc_attitude.h"
+#include "wbc_ground.h"
 #include "wbc_mpc.h"
 
 #define ARM_N 6
@@ -4681,5 +4682,50 @@ extern "C" int wbc_sim_attitude_filter(wbc_sim* s, const wbc_attitude_cfg* cfg, 
   a.q = q; a.b = b; a.P = P; a.gyro_out = gyro_out; a.gravity_body = gravity_body; a.nis = nis; a.status = status;
   if (c.n <= 0) return 0;
   wbc_attitude_launch(*cfg, a, stream);
+  return c.launched();
+}
+
+// ---- ground plane from the footholds (include/wbc_sim.h: wbc_sim_ground_estimate) -----------------------------------------------------------
+// The host side; the kernel is in wbc_ground_kernel.hip, its argument struct in wbc_ground.h.
+extern "C" int wbc_sim_ground_estimate(wbc_sim* s, const wbc_ground_cfg* cfg, const float* quat, const float* dof, const float* base_pos,
+                                       const float* contact, const int32_t* reset_mask, const float* query_xy, int num_query, int flags,
+                                       float* state, float* normal, float* ground, float* residual, float* trunk, float* theta_ref,
+                                       float* query_z, int32_t* info, void* stream) {
+  WbCall c("wbc_sim_ground_estimate", s, stream);
+  // the arguments first, so that every refusal below can be met (and tested) without a sim; then the sim
+  if (!cfg) return c.fail(-1, "cfg is NULL");
+  if (!state || !contact) return c.fail(-1, "state or contact is NULL");
+  if (flags & ~WBC_GROUND_RESET) return c.fail(-1, "unknown flag bits");
+  auto finite = [](float v) { return fabsf(v) <= 3.4e38f; };
+  auto positive = [](float v) { return v > 0.f && v <= 3.4e38f; };
+  if (!positive(cfg->dt) || !positive(cfg->tau_age)) return c.fail(-1, "dt and tau_age must be finite and > 0");
+  if (!positive(cfg->lambda) || !positive(cfg->slope_max)) return c.fail(-1, "lambda and slope_max must be finite and > 0");
+  if (!finite(cfg->c_on)) return c.fail(-1, "c_on must be finite");
+  if (!(cfg->tilt_gain >= 0.f && cfg->tilt_gain <= 1.f)) return c.fail(-1, "tilt_gain must be in [0, 1]");
+  if (num_query < 0) return c.fail(-1, "num_query must be >= 0");
+  if (query_xy && num_query == 0) return c.fail(-1, "query_xy is given with num_query 0");
+  if (((uintptr_t)quat | (uintptr_t)dof | (uintptr_t)base_pos | (uintptr_t)contact | (uintptr_t)reset_mask | (uintptr_t)query_xy | (uintptr_t)state |
+       (uintptr_t)normal | (uintptr_t)ground | (uintptr_t)residual | (uintptr_t)trunk | (uintptr_t)theta_ref | (uintptr_t)query_z | (uintptr_t)info) & 3u)
+    return c.fail(-1, "every pointer must be 4-byte aligned");
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  const wbc_model& m = c.hc->model;
+  EstConst K;
+  if (tree_walk_fill(m, K) != 0 || !tree_rigid_ok(m)) return c.no_tree();
+  for (int f = 0; f < WBC_NFEET; ++f) {
+    const int rb = m.feet_rb[f];
+    if (rb < 0 || rb >= WBC_NRB) return c.no_tree();
+    K.foot_body[f] = m.rb_body[rb];
+    for (int j = 0; j < 3; ++j) K.foot_off[f][j] = m.rb_offset[rb][j];
+    const int32_t* path = K.path[K.foot_body[f]];                     // the kernel unrolls exactly GE_LEG_JOINTS joints per leg
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k)
+      if ((path[k] >= 0) != (k < GE_LEG_JOINTS)) return c.fail(-3, "a foot's leg does not have exactly three joints");
+  }
+  for (int j = 0; j < 3; ++j) K.gravity[j] = c.hc->cfg.gravity[j];
+  if (c.n <= 0) return 0;
+  const GeArgs a = {dof ? dof : c.dofs, quat ? quat : c.root + 3, base_pos ? base_pos : c.root, contact, query_xy, reset_mask,
+                    quat ? 4 : 26, base_pos ? 3 : 26, (flags & WBC_GROUND_RESET) ? 1 : 0, query_xy ? num_query : 0, c.n,
+                    state, normal, ground, residual, trunk, theta_ref, query_z, info};
+  wbc_ground_launch(K, *cfg, a, stream);
   return c.launched();
 }

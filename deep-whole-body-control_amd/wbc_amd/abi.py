@@ -190,6 +190,18 @@ class WbcAttitudeCfg(C.Structure):
 AttitudeCfg = WbcAttitudeCfg
 
 
+GROUND_NS = 32             # WBC_GROUND_NS: floats of ground-estimate state per env: (m, t, 0) per foot, the anchor at 20, the plane at 22
+GROUND_SERIES = 1e-4       # WBC_GROUND_SERIES
+GROUND_RESET = 1           # WBC_GROUND_RESET (wbc_sim_ground_estimate's own flags word)
+GROUND_INFO_RESET, GROUND_INFO_FAILED, GROUND_INFO_DEGENERATE, GROUND_INFO_CLAMPED = 1, 2, 4, 8   # WBC_GROUND_INFO_*
+GROUND_INFO_LATCHED = 16   # << foot
+
+
+class WbcGroundCfg(C.Structure):
+    """wbc_ground_cfg (include/wbc_sim.h): the host scalars of wbc_sim_ground_estimate."""
+    _fields_ = [(name, f32) for name in ("dt", "c_on", "tau_age", "lambda", "slope_max", "tilt_gain")]
+
+
 class WbcTaskQpLimits(C.Structure):
     """wbc_taskqp_limits (include/wbc_sim.h): the host scalars of wbc_sim_task_inverse_dynamics_qp; max_iter 0 = the default."""
     _fields_ = [("mu", f32), ("fn_min", f32), ("max_iter", i32)]

@@ -820,6 +820,12 @@ class WidowGo1(LeggedRobot):
         wbc_attitude_cfg; dt None: env.dt)."""
         return AttitudeEstimator(self, **cfg)
 
+    # ---- terrain estimation (no counterpart in the reference): include/wbc_sim.h: wbc_sim_ground_estimate ----
+    def ground_estimator(self, **cfg) -> "GroundEstimator":
+        """The blind terrain estimate: a plane through the most recent footholds, the estimate of what the other layers take as ground,
+        foot_height, normal and height: see GroundEstimator (cfg: the fields of wbc_ground_cfg; dt None: env.dt)."""
+        return GroundEstimator(self, **cfg)
+
     def imu(self, gyro_bias=0.0, gyro_noise: float = 0.0, accel_noise: float = 0.0, heading_noise: float = None, seed: int = 0) -> "ImuModel":
         """A small IMU model on the sim's state: gyro, accelerometer and (with heading_noise not None) a heading vector in trunk axes,
         with a constant gyro bias and seeded Gaussian noise: see ImuModel."""
@@ -1434,8 +1440,8 @@ class ContactDetector:
         det.update(torques=tau)                          # after the simulate calls that applied tau
         est.update(contact=det.prob)
         env.whole_body_controller(..., stance=det.stance)
-    Not covered: feeding the events back into the planner's clock, slip detection, terrain normals estimated rather than given, contacts
-    on links other than the feet."""
+    Not covered: feeding the events back into the planner's clock, slip detection, contacts on links other than the feet. ground and
+    normal can come from a GroundEstimator (det.update(ground=gnd.ground, normal=gnd.normal))."""
 
     DEFAULTS = dict(sigma_phase=0.05, mu_z=0.01, sigma_z=0.01, mu_f=15.0, sigma_f=8.0, var_phase=0.25, var_z=0.05, var_f=0.05, alpha=0.5,
                     p_on=0.6, p_off=0.4, t_dwell=0.04, early_min=0.5, late_min=0.2, damping=0.02)
@@ -1477,12 +1483,14 @@ class ContactDetector:
             env.sim.momentum_observer(self._tau, self.gain, dt, state=self._observer_fresh, reset=True)
             self.observer_state.copy_(torch.where((reset_mask != 0)[:, None, None], self._observer_fresh, self.observer_state))
 
-    def _launch(self, foot_force=None, ground=None, base_pos=None, reset_mask=None, reset=False) -> None:
+    def _launch(self, foot_force=None, ground=None, base_pos=None, reset_mask=None, reset=False, normal=None) -> None:
         phase = self.planner.state[:, 0] if self.planner is not None else None
         tau_ext = None if foot_force is not None else self.tau_ext
         self.last_inputs = dict(tau_ext=tau_ext, foot_force=foot_force, ground=ground, base_pos=base_pos, phase=phase, reset_mask=reset_mask, reset=reset)
-        self.env.sim.contact_detect(self.cfg, self.state, base_pos=base_pos, tau_ext=tau_ext, foot_force=foot_force, ground=ground, phase=phase,
-                                    reset_mask=reset_mask, reset=reset, prob=self.prob, contact=self.contact, stance=self.stance,
+        if normal is not None:
+            self.last_inputs["normal"] = normal
+        self.env.sim.contact_detect(self.cfg, self.state, base_pos=base_pos, tau_ext=tau_ext, foot_force=foot_force, normal=normal, ground=ground,
+                                    phase=phase, reset_mask=reset_mask, reset=reset, prob=self.prob, contact=self.contact, stance=self.stance,
                                     force=self.foot_forces, terms=self.terms, info=self.info)
 
     def reset(self, env_ids=None) -> None:
@@ -1503,19 +1511,21 @@ class ContactDetector:
         for t, k in zip(tensors, keep):
             t[rest] = k[rest]
 
-    def update(self, torques=None, foot_force=None, ground=None, base_pos=None) -> torch.Tensor:
+    def update(self, torques=None, foot_force=None, ground=None, base_pos=None, normal=None) -> torch.Tensor:
         """One observer update and one detector launch at the sim's current state, to be called once per control step after the simulate
         calls; returns prob [N, 4]. torques [N, 20]: the joint torques that were applied, what set_dof_forces takes (None: env.torques).
         foot_force [N, 4, 3] (world): a measured foot force, used instead of the observer's estimate. ground [N, 4]: the height of a
         resting foot's origin; None: the foot sphere's radius above z = 0 on the plane, no height term on other terrain. base_pos
-        [N, 3]: the trunk's position (a BaseStateEstimator's), None: the sim's. duty, offsets and phase are the planner's. Envs flagged
+        [N, 3]: the trunk's position (a BaseStateEstimator's), None: the sim's. normal [N, 4, 3]: the ground's normal under each foot (a
+        GroundEstimator's), None: world z. duty, offsets and phase are the planner's. Envs flagged
         in env.reset_buf are reset. Results: .prob, .contact, .stance, .foot_forces, .terms, .info; the tensors handed to the kernel are
         kept in last_inputs."""
         env = self.env
         mask = env.reset_buf.to(torch.int32)
         self._observe(torques, reset_mask=mask)
         f = lambda t: None if t is None else t.to(torch.float32).contiguous()
-        self._launch(foot_force=f(foot_force), ground=self._plane_ground if ground is None else f(ground), base_pos=f(base_pos), reset_mask=mask)
+        self._launch(foot_force=f(foot_force), ground=self._plane_ground if ground is None else f(ground), base_pos=f(base_pos), reset_mask=mask,
+                     normal=f(normal))
         return self.prob
 
 
@@ -1691,6 +1701,86 @@ class AttitudeEstimator:
         env = self.env
         self._launch(gyro=gyro, accel=accel, aux=aux, reset_mask=env.reset_buf.to(torch.int32), q_init=env.base_quat)
         return self.quat
+
+
+class GroundEstimator:
+    """The blind terrain estimate of wbc_sim_ground_estimate for every env (the terrain-slope estimate of Bledt et al., IROS 2018): a plane
+    through the most recent footholds, weighted by their age and regularised towards the previous slope. It owns the cfg, the state
+    [N, 32] (per foot the last contact point, its age and a 0; the anchor at 20, the plane (a0, a1, a2) at 22) and every output, and
+    advances them by one launch per update(). Keyword arguments are the fields of wbc_ground_cfg (include/wbc_sim.h), `lambda_` for
+    lambda; dt defaults to env.dt. The defaults are UNTUNED. The estimator starts reset with every contact point at its foot. Use it as
+        gnd.update(det.prob, base_pos=est.position)      # or a flag, or planner.contact
+        est.update(foot_height=gnd.ground)
+        det.update(ground=gnd.ground, normal=gnd.normal)
+        env.whole_body_controller(..., normal=gnd.normal[:, stance_idx])
+        mpc.solve(..., height=gnd.trunk[:, 0] + h_nominal)
+    Nothing takes it by default. Not covered: per-foot local patches, normals inside the MPC's cone or the leg controller's clip, slip
+    detection, the planner's foothold search (which keeps reading the heightfield)."""
+
+    DEFAULTS = dict(c_on=0.5, tau_age=0.5, lambda_=0.01, slope_max=0.7, tilt_gain=1.0)
+
+    def __init__(self, env, dt: float = None, **cfg):
+        unknown = set(cfg) - set(self.DEFAULTS)
+        assert not unknown, f"unknown ground-estimator parameters: {sorted(unknown)}"
+        v = dict(self.DEFAULTS, **cfg)
+        self.env = env
+        self.cfg = abi.WbcGroundCfg(float(env.dt if dt is None else dt), *[float(v[k]) for k in self.DEFAULTS])
+        n, dev = env.num_envs, env.device
+        z = lambda *sh, dtype=torch.float32: torch.zeros(sh, dtype=dtype, device=dev)
+        self.state = z(n, abi.GROUND_NS)
+        self.normal, self.ground, self.residual, self.trunk, self.theta_ref = z(n, 4, 3), z(n, 4), z(n, 4), z(n, 6), z(n, 3)
+        self.query_z, self.info = z(n, 0), z(n, dtype=torch.int32)
+        self._all = torch.ones((n, 4), dtype=torch.float32, device=dev)
+        self.last_inputs = None
+        self.reset()
+
+    @property
+    def plane(self) -> torch.Tensor:
+        """f32 [N, 5]: (c_x, c_y, a0, a1, a2) with z(x, y) = a0 + a1 (x - c_x) + a2 (y - c_y) (a view of the state)."""
+        return self.state[:, 20:25]
+
+    def _launch(self, contact, base_pos=None, quat=None, query_xy=None, reset_mask=None, reset=False) -> None:
+        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        n, dev = self.env.num_envs, self.env.device
+        q = f(query_xy)
+        if q is not None:
+            q = q.reshape(n, -1, 2)
+        nq = 0 if q is None else int(q.shape[1])
+        if tuple(self.query_z.shape) != (n, nq):
+            self.query_z = torch.zeros((n, nq), dtype=torch.float32, device=dev)
+        kw = dict(contact=f(contact), base_pos=f(base_pos), quat=f(quat), query_xy=q if nq > 0 else None, reset_mask=reset_mask, reset=reset)
+        self.last_inputs = dict(kw)
+        self.env.sim.ground_estimate(self.cfg, self.state, normal=self.normal, ground=self.ground, residual=self.residual, trunk=self.trunk,
+                                     theta_ref=self.theta_ref, query_z=self.query_z, info=self.info, **kw)
+
+    def reset(self, env_ids=None) -> None:
+        """Reset every env (env_ids None) or the listed ones: every contact point at its foot's current position, zero slope. One launch;
+        the other envs are left as they are."""
+        env = self.env
+        if env_ids is None:
+            self._launch(self._all, reset=True)
+            return
+        mask = torch.zeros((env.num_envs,), dtype=torch.int32, device=env.device)
+        mask[torch.as_tensor(env_ids, dtype=torch.long, device=env.device)] = 1
+        if tuple(self.query_z.shape) != (env.num_envs, 0):
+            self.query_z = torch.zeros((env.num_envs, 0), dtype=torch.float32, device=env.device)
+        tensors = (self.state, self.normal, self.ground, self.residual, self.trunk, self.theta_ref, self.info)
+        keep = [t.clone() for t in tensors]
+        self._launch(self._all, reset_mask=mask)
+        rest = mask == 0                                                            # the launch also advanced the others: put them back
+        for t, k in zip(tensors, keep):
+            t[rest] = k[rest]
+
+    def update(self, contact, base_pos=None, quat=None, query_xy=None) -> torch.Tensor:
+        """One launch at the sim's current joint state, to be called once per control step; returns ground [N, 4]. contact [N, 4]: a
+        ContactDetector's prob, a flag such as get_foot_contacts() or a FootstepPlanner's contact; a foot stands iff its entry is >=
+        c_on. base_pos [N, 3] and quat [N, 4] (xyzw): the trunk's estimated position and orientation (a BaseStateEstimator's, an
+        AttitudeEstimator's), None: the sim's. query_xy [N, Q, 2]: world points at which the plane is evaluated into .query_z [N, Q].
+        Envs flagged in env.reset_buf are reset. Results: .normal, .ground, .residual, .trunk, .theta_ref, .query_z, .info, .plane;
+        the tensors handed to the kernel are kept in last_inputs."""
+        env = self.env
+        self._launch(contact, base_pos=base_pos, quat=quat, query_xy=query_xy, reset_mask=env.reset_buf.to(torch.int32))
+        return self.ground
 
 
 class ImuModel:

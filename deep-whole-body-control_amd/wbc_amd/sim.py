@@ -807,6 +807,39 @@ class WbcSim:
                                              P.data_ptr(), *[ptr(outputs.get(name)) for name in self.ATTITUDE_OUTPUTS], self._stream()),
               "wbc_sim_attitude_filter")
 
+    # ---- ground plane from the footholds (include/wbc_sim.h: wbc_sim_ground_estimate) ------------------------------------------------------
+    GROUND_OUTPUTS = ("normal", "ground", "residual", "trunk", "theta_ref", "query_z", "info")
+
+    def ground_estimate(self, cfg: "abi.WbcGroundCfg", state: torch.Tensor, contact: torch.Tensor, quat: Optional[torch.Tensor] = None,
+                        dof: Optional[torch.Tensor] = None, base_pos: Optional[torch.Tensor] = None, reset_mask: Optional[torch.Tensor] = None,
+                        query_xy: Optional[torch.Tensor] = None, reset: bool = False, **outputs) -> None:
+        """One wbc_sim_ground_estimate launch on the current stream: one control step of the blind terrain estimate, a plane through the
+        most recent footholds, on the caller-owned state f32 [N, 32] (per foot the last contact point, its age and a 0; the anchor at 20,
+        the plane (a0, a1, a2) at 22), in place. contact f32 [N, 4]: a foot stands iff its entry is >= cfg.c_on. quat [N, 4] (xyzw), dof
+        [N, 20, 2] and base_pos [N, 3], None: the sim's current state. query_xy [N, Q, 2]: world points at which the plane is evaluated.
+        reset=True resets every env, reset_mask int32 [N] the envs whose entry is not 0. Outputs by keyword, each a caller-owned tensor
+        that is filled (GROUND_OUTPUTS): normal [N, 4, 3], ground [N, 4], residual [N, 4], trunk [N, 6], theta_ref [N, 3], query_z
+        [N, Q], info int32 [N]."""
+        n = self.num_envs
+        unknown = set(outputs) - set(self.GROUND_OUTPUTS)
+        assert not unknown, f"unknown outputs: {sorted(unknown)}"
+        f32, i32 = torch.float32, torch.int32
+        nq = 0 if query_xy is None else int(query_xy.shape[1])
+        assert query_xy is None or nq > 0, "query_xy needs at least one point per env"
+        shapes = dict(normal=((n, 4, 3), f32), ground=((n, 4), f32), residual=((n, 4), f32), trunk=((n, 6), f32), theta_ref=((n, 3), f32),
+                      query_z=((n, nq), f32), info=((n,), i32))
+        checks = [(state, (n, abi.GROUND_NS), f32), (contact, (n, 4), f32), (quat, (n, 4), f32), (dof, (n, abi.NDOF, 2), f32),
+                  (base_pos, (n, 3), f32), (reset_mask, (n,), i32), (query_xy, (n, nq, 2), f32)]
+        checks += [(outputs.get(k),) + shapes[k] for k in self.GROUND_OUTPUTS]
+        for t, sh, dt in checks:
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == sh, (tuple(t.shape), sh)
+        assert state is not None and contact is not None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None
+        check(self.L.wbc_sim_ground_estimate(self.h, C.byref(cfg), ptr(quat), ptr(dof), ptr(base_pos), ptr(contact), ptr(reset_mask), ptr(query_xy),
+                                             nq, abi.GROUND_RESET if reset else 0, state.data_ptr(),
+                                             *[ptr(outputs.get(k)) for k in self.GROUND_OUTPUTS], self._stream()), "wbc_sim_ground_estimate")
+
     def proximity_damper_rows(self, gap: torch.Tensor, jac: torch.Tensor, d_safe: float, d_influence: float, xi: float, dt: float,
                               nu: Optional[torch.Tensor] = None):
         """The velocity damper of the pairs inside the influence distance as rows on the accelerations, torch ops only: the gap rate

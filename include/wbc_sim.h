@@ -1235,8 +1235,8 @@ int wbc_sim_footstep_plan(wbc_sim* sim, const wbc_footstep_cfg* cfg, const float
  * not finite; alpha outside (0, 1]; p_on or p_off not finite, or p_on <= p_off; t_dwell or damping not finite or < 0; early_min or
  * late_min outside [0, 1]; no measurement source; both force inputs; tau_ext_stride < 26 or phase_stride < 1 where the pointer is given; a
  * misaligned pointer. Then NULL sim; -3 (also: a foot whose leg does not have exactly three joints) / -2 and stream handling as
- * wbc_sim_coriolis. Not covered: feeding the events back into the planner's clock, slip detection, terrain normals estimated rather than
- * given, contacts on links other than the feet. */
+ * wbc_sim_coriolis. Not covered: feeding the events back into the planner's clock, slip detection, contacts on links other
+ * than the feet. `ground` and `normal` can be estimated rather than given: wbc_sim_ground_estimate below writes both in this layout. */
 #define WBC_CONTACT_NS 16           /* floats of state per env */
 typedef struct {
   float dt;                         /* control step, s */
@@ -1425,6 +1425,89 @@ typedef struct {
 int wbc_sim_attitude_filter(wbc_sim* sim, const wbc_attitude_cfg* cfg, const float* gyro, const float* accel, const float* aux_body,
                             const float* aux_world, const float* aux_sigma, int num_aux, const int32_t* reset_mask, const float* q_init,
                             int flags, float* q, float* b, float* P, float* gyro_out, float* gravity_body, float* nis, int32_t* status,
+                            void* stream);
+
+/* One control step of the blind terrain estimate, the layer that gives wbc_sim_leg_odometry its foot_height, wbc_sim_contact_detect its
+ * ground and normal, wbc_sim_task_inverse_dynamics_qp its normal and the MPC's reference its height and tilt without the simulator's
+ * heightfield: a plane through the most recent footholds (Bledt et al., "MIT Cheetah 3: Design and Control of a Robust, Dynamic Quadruped
+ * Robot", IROS 2018, the terrain-slope estimate). OURS, not the paper's: the footholds are weighted by their age, the fit is regularised
+ * towards the previous slope (which is its only memory), and the plane is kept relative to an anchor at the footholds' weighted mean, so
+ * that nothing is squared in world coordinates. One launch (wbc_ground_estimate_kernel); the sim's state is read, never written. Per env
+ * the caller owns
+ * state  device f32 [N, WBC_GROUND_NS = 32], read and written. Per foot (feet_rb order FL, FR, RL, RR) five floats at 5 i: the last contact
+ *        point m_i (the foot ORIGIN, world axes), its age t_i in seconds, a reserved 0. At 20: the anchor (c_x, c_y). At 22: the plane
+ *        (a0, a1, a2), z(x, y) = a0 + a1 (x - c_x) + a2 (y - c_y): the height of a foot origin at rest on the ground at (x, y). 25 .. 31
+ *        are written as 0. Only m_i, t_i, a1 and a2 are ever read.
+ * INPUTS (device f32 unless said otherwise; each but contact may be NULL):
+ * quat [N, 4] xyzw, normalised in the call: R (world <- trunk). NULL: ROOT_STATES'.   dof [N, 20, 2] in the layout of DOF_STATE (the
+ *        velocities are not read). NULL: DOF_STATE.   base_pos [N, 3]: the trunk origin b, world axes. NULL: ROOT_STATES' (a
+ *        BaseStateEstimator's position fits here).
+ * contact [N, 4], required: wbc_sim_contact_detect's prob, a 0 / 1 flag or wbc_sim_footstep_plan's contact. Foot i counts as standing iff
+ *        contact_i >= c_on.
+ * reset_mask int32 [N].   query_xy [N, Q, 2], Q = num_query >= 0: world points at which the plane is evaluated (the planner's footholds,
+ *        the positions of x_ref's stages). NULL: no query, whatever Q.
+ * PER ENV, in this order. A sum over the four feet is taken pairwise, (s_0 + s_1) + (s_2 + s_3).
+ * 1 KINEMATICS  the leg walk of wbc_sim_leg_odometry: the foot origins p_i = b + R fk_i(q).
+ * 2 RESET (WBC_GROUND_RESET in flags: every env; otherwise the envs whose reset_mask entry is not 0; the env's state is then not read):
+ *   m_i = p_i and t_i = 0 for every foot, (a1, a2) = 0; info bit WBC_GROUND_INFO_RESET. The env then goes through steps 3 .. 6 of this very
+ *   call with that state.
+ * 3 LATCH  a standing foot: m_i <- p_i, t_i <- 0, info bit WBC_GROUND_INFO_LATCHED << i. Any other foot: t_i <- t_i + dt. Weights
+ *   w_i = exp(-(t_i - t_min) / tau_age) with t_min the smallest of the four ages, W = sum w_i. The fit below is homogeneous in the weights,
+ *   so this is the fit with w_i = exp(-t_i / tau_age), a foot that stays in the air loses weight against the others at that rate, and
+ *   W >= 1 however old the footholds are.
+ * 4 FIT  relative to foot 0's point, e_i = m_i - m_0: r = (sum w_i e_i) / W, the anchor cbar = m_0 + r (the weighted mean of the m_i, all
+ *   three coordinates) and d_i = e_i - r = m_i - cbar, formed without rounding cbar and before anything is squared. With lw = lambda W and
+ *   a_prev the stored slope (0 after a reset):
+ *     [Sxx + lw, Sxy; Sxy, Syy + lw] a = (Sxz + lw a_prev,1, Syz + lw a_prev,2),   Suv = sum_i (w_i d_i,u) d_i,v.
+ *   The lambda term is the only memory of the slope; it keeps the system regular when the weighted footholds are collinear (a long trot
+ *   stance on one diagonal): the slope along the line is fitted, the slope across it stays a_prev. The system is solved by the written-out
+ *   Cholesky factorisation of wbc_sim_contact_detect step 3 (l00 = sqrt(A00), l10 = A10 / l00, d1 = A11 - l10^2, l11 = sqrt(d1), forwards,
+ *   backwards). Where a pivot (A00, d1) is not a positive finite number, or a comes out not finite, a = a_prev: info bit
+ *   WBC_GROUND_INFO_DEGENERATE (anchor and a0 still move). Then, where |a| > slope_max, a <- a (slope_max / |a|): info bit
+ *   WBC_GROUND_INFO_CLAMPED. Stored: (c_x, c_y) = m_0,xy + r_xy, a0 = m_0,z + r_z, (a1, a2) = a. A point (x, y) enters the plane as
+ *   g = ((x, y) - m_0,xy) - r_xy, z = a0 + (a1 g_x + a2 g_y): relative to the anchor before it was rounded into the state.
+ * 5 OUTPUTS, each may be NULL and is then not written; what is written never depends on which are asked for:
+ *   normal f32 [N, 4, 3]: n = (-a1, -a2, 1) / sqrt(1 + a1^2 + a2^2), the same for every foot: the layout wbc_sim_contact_detect and
+ *          wbc_sim_task_inverse_dynamics_qp take.
+ *   ground f32 [N, 4] = z(p_i,xy) for every foot, standing or not: the foot-ORIGIN convention of wbc_sim_contact_detect's ground and
+ *          wbc_sim_leg_odometry's foot_height. A standing foot does not get its own height back (the detector's height term would be
+ *          circular).
+ *   residual f32 [N, 4] = m_i,z - z(m_i,xy) = d_i,z - (a1 d_i,x + a2 d_i,y): the fit's own roughness measure.
+ *   trunk f32 [N, 6]: z(b_xy); the clearance (b_z - z(b_xy)) n_z along the normal; the slopes along and across the heading,
+ *          s_f = a1 c + a2 s and s_l = -a1 s + a2 c with (c, s) wbc_sim_footstep_plan's heading rule on R; two reserved zeros.
+ *   theta_ref f32 [N, 3] = tilt_gain g(s) (a2, -a1, 0), s = |a|, g(s) = atan(s) / s, and for s < WBC_GROUND_SERIES the series 1 - s^2 / 3
+ *          (a = 0 gives exactly 0): the world-axes rotation vector of the shortest rotation from world z to n, scaled by tilt_gain: what
+ *          the theta block of the MPC's x_ref holds.
+ *   query_z f32 [N, Q]: the plane at the query points (nothing is written with Q = 0 or without query_xy).
+ *   info int32 [N]: the bits below.
+ * 6 FAILURE  an env that reads a value that is not finite (quat, or a zero quat; b; a leg joint's q; contact; its query points; and,
+ *   unless it is reset, its m_i, t_i, a1, a2) writes zeros to every float output, info = WBC_GROUND_INFO_FAILED alone, and leaves its state
+ *   as it was; no other env is affected.
+ * Every pointer needs 4-byte alignment only. Nothing is allocated and nothing synchronises: safe under stream capture. -1 with a message
+ * in wbc_last_error() that names the entry point, nothing written, checked BEFORE the sim: NULL cfg, state or contact; unknown flag bits;
+ * dt, tau_age, lambda or slope_max not finite and > 0; c_on not finite; tilt_gain outside [0, 1]; num_query < 0, or query_xy given with
+ * num_query = 0; a misaligned pointer. Then NULL sim; -3 (also: a foot whose leg does not have exactly three joints) / -2 and stream
+ * handling as wbc_sim_coriolis. Not covered: per-foot local patches, normals inside the MPC's cone or the leg controller's clip, slip
+ * detection, feeding the plane to wbc_sim_footstep_plan (which keeps reading the heightfield). */
+#define WBC_GROUND_NS 32            /* floats of state per env */
+#define WBC_GROUND_SERIES 1e-4f     /* below this |a|, atan(s) / s is taken from its series */
+typedef struct {
+  float dt;                         /* control step, s */
+  float c_on;                       /* a foot stands iff contact >= c_on */
+  float tau_age;                    /* time constant of a foothold's weight, s */
+  float lambda;                     /* weight of the previous slope in the fit, m^2 */
+  float slope_max;                  /* largest |a| */
+  float tilt_gain;                  /* share of the plane's tilt that theta_ref asks of the trunk, [0, 1] */
+} wbc_ground_cfg;
+#define WBC_GROUND_RESET 1
+#define WBC_GROUND_INFO_RESET 1
+#define WBC_GROUND_INFO_FAILED 2
+#define WBC_GROUND_INFO_DEGENERATE 4
+#define WBC_GROUND_INFO_CLAMPED 8
+#define WBC_GROUND_INFO_LATCHED 16               /* << foot */
+int wbc_sim_ground_estimate(wbc_sim* sim, const wbc_ground_cfg* cfg, const float* quat, const float* dof, const float* base_pos,
+                            const float* contact, const int32_t* reset_mask, const float* query_xy, int num_query, int flags, float* state,
+                            float* normal, float* ground, float* residual, float* trunk, float* theta_ref, float* query_z, int32_t* info,
                             void* stream);
 
 /* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and

@@ -3,7 +3,7 @@
 defaults of BaseStateEstimator, FootstepPlanner, CentroidalMPC and whole_body_controller.
 
   python tools/classical_trot.py [--envs 64] [--seconds 4] [--speed 0.3] [--gait trot] [--detector] [--controller qp|leg] [--height H]
-                                 [--attitude [--gyro-bias B]]
+                                 [--attitude [--gyro-bias B]] [--ground]
 
 Prints, once per simulated second and at the end: the share of envs still upright (trunk z axis within 0.5 rad of vertical and the trunk
 above 0.15 m), the mean forward speed of the upright envs against the command, and the MPC / QP / planner status counts.
@@ -23,7 +23,15 @@ height of the centre of mass (default: the current one, so that nothing pulls a 
 (env.imu: gyro noise 0.002 rad/s, accelerometer noise 0.05 m/s^2, a heading vector with noise 0.01, and --gyro-bias B rad/s on every
 axis): the leg-odometry estimator takes att.quat, att.gyro and the IMU's accelerometer instead of the sim's true orientation and angular
 velocity. The planner, the detector and the controllers keep reading the sim's quaternion. It then also prints, once per simulated
-second, the tilt and heading errors of att.quat against the sim's quaternion and the bias error."""
+second, the tilt and heading errors of att.quat against the sim's quaternion and the bias error.
+
+--ground (default off) puts the blind terrain estimate (env.ground_estimator: wbc_sim_ground_estimate) into the loop, on the planner's
+contact (det.prob with --detector) and the estimator's position: the leg odometry takes gnd.ground as foot_height, the detector
+gnd.ground and gnd.normal, the task QP gnd.normal, and with --height H the MPC's reference height is gnd.trunk[:, 0] + H, H above the
+estimated plane under the trunk (without --height the MPC keeps the current height as before). It then also prints, once per simulated
+second, the estimated slope and the error of the feet's clearance gnd.ground - est z against the truth (the plane: the foot sphere's
+radius above z = 0, less the trunk's true height); the loop of estimator and plane has no absolute height, so only that difference means
+anything."""
 import argparse
 import os
 import sys
@@ -40,6 +48,7 @@ ap.add_argument("--controller", choices=("qp", "leg"), default="qp", help="whole
 ap.add_argument("--height", type=float, default=None, help="reference height of the centre of mass for the MPC (default: the current one)")
 ap.add_argument("--attitude", action="store_true", help="orientation and gyro for the leg odometry from the attitude filter on an IMU model")
 ap.add_argument("--gyro-bias", type=float, default=0.0, help="constant gyro bias of the IMU model, rad/s on every axis (with --attitude)")
+ap.add_argument("--ground", action="store_true", help="foot heights, normals and the MPC's reference height from the blind terrain estimate")
 a = ap.parse_args()
 
 sys.path.insert(0, os.path.join(ROOT, "deep-whole-body-control_amd"))
@@ -48,6 +57,7 @@ from collections import Counter  # noqa: E402
 
 import torch  # noqa: E402
 
+from wbc_amd import abi  # noqa: E402
 from wbc_amd.config import WidowGo1RoughCfg  # noqa: E402
 from wbc_amd.envs import WidowGo1  # noqa: E402
 
@@ -71,6 +81,8 @@ dets = {id(stand): env.contact_detector(planner=stand), id(walk): env.contact_de
 agree, events, tau = [0, 0], dict(early=0, late=0, touchdown=0, liftoff=0), None
 att = env.attitude_estimator() if a.attitude else None
 imu = env.imu(gyro_bias=a.gyro_bias, gyro_noise=0.002, accel_noise=0.05, heading_noise=0.01, seed=2) if a.attitude else None
+gnd = env.ground_estimator() if a.ground else None
+h_nominal = None
 x_start = env.root_states[:, 0].clone()
 
 
@@ -98,6 +110,13 @@ def report(label, k):
         berr = (att.bias[up] - a.gyro_bias).abs().max(dim=-1).values
         stat = lambda t: f"mean {t.mean().item():.4f} max {t.max().item():.4f}" if t.numel() else "no upright env"
         print(f"    attitude of the upright envs: tilt error {stat(tilt)} rad, heading error {stat(head)} rad, bias error {stat(berr)} rad/s", flush=True)
+    if gnd is not None and bool(up.any()):
+        slope = gnd.plane[up][:, 3:5].norm(dim=1)
+        gerr = ((gnd.ground - est.position[:, 2:3]) - (abi.FOOT_RADIUS - env.root_states[:, 2:3]))[up].abs()
+        print(f"    ground estimate of the upright envs: slope mean {slope.mean().item():.4f} max {slope.max().item():.4f} (truth 0), error of the feet's "
+              f"clearance below the trunk mean {gerr.mean().item() * 1e3:.2f} max {gerr.max().item() * 1e3:.2f} mm, |residual| max "
+              f"{gnd.residual[up].abs().max().item() * 1e3:.2f} mm, estimator z - true z mean "
+              f"{(est.position[:, 2] - env.root_states[:, 2])[up].mean().item() * 1e3:.2f} mm", flush=True)
 
 
 planner = stand
@@ -107,25 +126,35 @@ for k in range(steps):
         planner.reset()
         if a.detector:
             dets[id(walk)].reset()
+        if gnd is not None and a.height is not None:
+            h_nominal = a.height
     c = cmd if k >= settle else zero
     ekw = {}
     if att is not None:
         gyro, accel, heading = imu.read()
         att.update(gyro=gyro, accel=accel, aux=(heading, imu.heading_world, 0.05))
         ekw = dict(quat=att.quat, gyro=att.gyro, accel=accel)
+    gkw, height = {}, a.height
+    if gnd is not None:                                                                # on the contact and the position of the step before
+        gnd.update(dets[id(planner)].prob if a.detector else planner.contact, base_pos=est.position)
+        ekw["foot_height"] = gnd.ground
+        gkw = dict(ground=gnd.ground, normal=gnd.normal)
+        if h_nominal is not None:
+            height = gnd.trunk[:, 0] + h_nominal
     if a.detector:
         det = dets[id(planner)]
-        det.update(torques=tau)                                                        # tau: what the last simulate calls applied (None at the start: env.torques)
+        det.update(torques=tau, **gkw)                                                 # tau: what the last simulate calls applied (None at the start: env.torques)
         est.update(contact=det.prob, **ekw)
     else:
         est.update(contact=planner.contact, **ekw)
     planner.update(c, wz, state=est)
-    mpc.solve(planner.contact_schedule, c, wz, height=a.height, foot_positions=planner.foot_positions, state=est)
+    mpc.solve(planner.contact_schedule, c, wz, height=height, foot_positions=planner.foot_positions, state=est)
     if ctl is not None:
         tau = ctl.update(forces=mpc.forces, swing_ref=planner.swing_ref, stance=det.prob if a.detector else planner.contact, state=est)
     else:
         tau, nudot, lam, info = env.whole_body_controller(base_acc=mpc.base_acc, swing_acc=planner.swing_acc,
-                                                          stance=det.stance if a.detector else planner.stance)
+                                                          stance=det.stance if a.detector else planner.stance,
+                                                          normal=gnd.normal if gnd is not None else None)
     env.sim.set_dof_forces(tau.contiguous())
     for _ in range(decimation):
         env.sim.simulate()
