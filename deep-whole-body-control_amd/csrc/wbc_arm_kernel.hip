@@ -19,6 +19,7 @@
 #include "wbc_legctl.h"
 #include "wbc_attitude.h"
 #include "wbc_ground.h"
+#include "wbc_slip.h"
 #include "wbc_mpc.h"
 
 #define ARM_N 6
@@ -4727,5 +4728,57 @@ extern "C" int wbc_sim_ground_estimate(wbc_sim* s, const wbc_ground_cfg* cfg, co
                     quat ? 4 : 26, base_pos ? 3 : 26, (flags & WBC_GROUND_RESET) ? 1 : 0, query_xy ? num_query : 0, c.n,
                     state, normal, ground, residual, trunk, theta_ref, query_z, info};
   wbc_ground_launch(K, *cfg, a, stream);
+  return c.launched();
+}
+
+// ---- foot slip detection and friction estimate (include/wbc_sim.h: wbc_sim_slip_detect) ----------------------------------------------------
+// The host side; the kernel is in wbc_slip_kernel.hip, its argument struct in wbc_slip.h.
+extern "C" int wbc_sim_slip_detect(wbc_sim* s, const wbc_slip_cfg* cfg, const float* quat, const float* dof, const float* base_vel,
+                                   const float* ang_vel, const float* contact, const float* foot_force, const float* normal,
+                                   const int32_t* reset_mask, const float* mu_init, int flags, float* state, float* prob, uint8_t* slip,
+                                   float* weight, float* foot_vel, float* speed, float* distance, float* mu, float* mu_lower, float* mu_env,
+                                   int32_t* info, void* stream) {
+  WbCall c("wbc_sim_slip_detect", s, stream);
+  // the arguments first, so that every refusal below can be met (and tested) without a sim; then the sim
+  if (!cfg) return c.fail(-1, "cfg is NULL");
+  if (!state || !contact) return c.fail(-1, "state or contact is NULL");
+  if (flags & ~WBC_SLIP_RESET) return c.fail(-1, "unknown flag bits");
+  auto finite = [](float v) { return fabsf(v) <= 3.4e38f; };
+  auto positive = [](float v) { return v > 0.f && v <= 3.4e38f; };
+  auto nonneg = [](float v) { return v >= 0.f && v <= 3.4e38f; };
+  if (!positive(cfg->dt) || !positive(cfg->sigma_v)) return c.fail(-1, "dt and sigma_v must be finite and > 0");
+  if (!positive(cfg->fn_min) || !positive(cfg->w_min) || !positive(cfg->mu_scale)) return c.fail(-1, "fn_min, w_min and mu_scale must be finite and > 0");
+  if (!finite(cfg->c_on)) return c.fail(-1, "c_on must be finite");
+  if (!nonneg(cfg->v_slip) || !nonneg(cfg->t_dwell)) return c.fail(-1, "v_slip and t_dwell must be finite and >= 0");
+  if (!nonneg(cfg->mu_prior) || !nonneg(cfg->mu_min)) return c.fail(-1, "mu_prior and mu_min must be finite and >= 0");
+  if (!(cfg->alpha > 0.f && cfg->alpha <= 1.f) || !(cfg->gamma > 0.f && cfg->gamma <= 1.f)) return c.fail(-1, "alpha and gamma must be in (0, 1]");
+  if (!finite(cfg->p_on) || !finite(cfg->p_off)) return c.fail(-1, "p_on and p_off must be finite");
+  if (!(cfg->p_on > cfg->p_off)) return c.fail(-1, "p_on must be above p_off");
+  if (!(cfg->common_mode >= 0.f && cfg->common_mode <= 1.f)) return c.fail(-1, "common_mode must be in [0, 1]");
+  if (!(cfg->mu_max >= cfg->mu_min && cfg->mu_max <= 3.4e38f)) return c.fail(-1, "mu_max must be finite and >= mu_min");
+  if (((uintptr_t)quat | (uintptr_t)dof | (uintptr_t)base_vel | (uintptr_t)ang_vel | (uintptr_t)contact | (uintptr_t)foot_force | (uintptr_t)normal |
+       (uintptr_t)reset_mask | (uintptr_t)mu_init | (uintptr_t)state | (uintptr_t)prob | (uintptr_t)weight | (uintptr_t)foot_vel | (uintptr_t)speed |
+       (uintptr_t)distance | (uintptr_t)mu | (uintptr_t)mu_lower | (uintptr_t)mu_env | (uintptr_t)info) & 3u)
+    return c.fail(-1, "every float or int32 pointer must be 4-byte aligned");
+  if (!s) return c.no_sim();
+  if (!c.have) return c.no_state();
+  const wbc_model& m = c.hc->model;
+  EstConst K;
+  if (tree_walk_fill(m, K) != 0 || !tree_rigid_ok(m)) return c.no_tree();
+  for (int f = 0; f < WBC_NFEET; ++f) {
+    const int rb = m.feet_rb[f];
+    if (rb < 0 || rb >= WBC_NRB) return c.no_tree();
+    K.foot_body[f] = m.rb_body[rb];
+    for (int j = 0; j < 3; ++j) K.foot_off[f][j] = m.rb_offset[rb][j];
+    const int32_t* path = K.path[K.foot_body[f]];                     // the kernel unrolls exactly SL_LEG_JOINTS joints per leg
+    for (int k = 0; k < WBC_MAX_DEPTH; ++k)
+      if ((path[k] >= 0) != (k < SL_LEG_JOINTS)) return c.fail(-3, "a foot's leg does not have exactly three joints");
+  }
+  for (int j = 0; j < 3; ++j) K.gravity[j] = c.hc->cfg.gravity[j];
+  if (c.n <= 0) return 0;
+  const SlArgs a = {dof ? dof : c.dofs, quat ? quat : c.root + 3, base_vel ? base_vel : c.root + 7, ang_vel ? ang_vel : c.root + 10, contact,
+                    foot_force, normal, mu_init, reset_mask, quat ? 4 : 26, base_vel ? 3 : 26, ang_vel ? 3 : 26, ang_vel ? 0 : 1,
+                    (flags & WBC_SLIP_RESET) ? 1 : 0, c.n, state, prob, slip, weight, foot_vel, speed, distance, mu, mu_lower, mu_env, info};
+  wbc_slip_launch(K, *cfg, a, stream);
   return c.launched();
 }

@@ -202,6 +202,18 @@ class WbcGroundCfg(C.Structure):
     _fields_ = [(name, f32) for name in ("dt", "c_on", "tau_age", "lambda", "slope_max", "tilt_gain")]
 
 
+SLIP_NS = 8                # WBC_SLIP_NS: floats of slip-detector state per foot: p, s, t, c_prev, d, mu_i, w_i, m_i
+SLIP_RESET = 1             # WBC_SLIP_RESET (wbc_sim_slip_detect's own flags word)
+SLIP_INFO_RESET, SLIP_INFO_FAILED, SLIP_INFO_NO_FORCE = 1, 2, 4                          # WBC_SLIP_INFO_*
+SLIP_INFO_START, SLIP_INFO_END, SLIP_INFO_SLIPPING, SLIP_INFO_MU_VALID = 16, 256, 4096, 65536   # << foot
+
+
+class WbcSlipCfg(C.Structure):
+    """wbc_slip_cfg (include/wbc_sim.h): the host scalars of wbc_sim_slip_detect."""
+    _fields_ = [(name, f32) for name in ("dt", "c_on", "v_slip", "sigma_v", "alpha", "p_on", "p_off", "t_dwell", "common_mode", "fn_min",
+                                         "gamma", "w_min", "mu_prior", "mu_min", "mu_max", "mu_scale")]
+
+
 class WbcTaskQpLimits(C.Structure):
     """wbc_taskqp_limits (include/wbc_sim.h): the host scalars of wbc_sim_task_inverse_dynamics_qp; max_iter 0 = the default."""
     _fields_ = [("mu", f32), ("fn_min", f32), ("max_iter", i32)]

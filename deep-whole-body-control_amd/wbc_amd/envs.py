@@ -826,6 +826,12 @@ class WidowGo1(LeggedRobot):
         foot_height, normal and height: see GroundEstimator (cfg: the fields of wbc_ground_cfg; dt None: env.dt)."""
         return GroundEstimator(self, **cfg)
 
+    # ---- slip detection and friction estimate (no counterpart in the reference): include/wbc_sim.h: wbc_sim_slip_detect ----
+    def slip_detector(self, **cfg) -> "SlipDetector":
+        """The foot slip detector and friction estimate: which standing feet slide, how far a standing foot can be trusted, and the
+        friction coefficient from the force ratio while sliding: see SlipDetector (cfg: the fields of wbc_slip_cfg; dt None: env.dt)."""
+        return SlipDetector(self, **cfg)
+
     def imu(self, gyro_bias=0.0, gyro_noise: float = 0.0, accel_noise: float = 0.0, heading_noise: float = None, seed: int = 0) -> "ImuModel":
         """A small IMU model on the sim's state: gyro, accelerometer and (with heading_noise not None) a heading vector in trunk axes,
         with a constant gyro bias and seeded Gaussian noise: see ImuModel."""
@@ -1440,7 +1446,7 @@ class ContactDetector:
         det.update(torques=tau)                          # after the simulate calls that applied tau
         est.update(contact=det.prob)
         env.whole_body_controller(..., stance=det.stance)
-    Not covered: feeding the events back into the planner's clock, slip detection, contacts on links other than the feet. ground and
+    Not covered: feeding the events back into the planner's clock, contacts on links other than the feet. ground and
     normal can come from a GroundEstimator (det.update(ground=gnd.ground, normal=gnd.normal))."""
 
     DEFAULTS = dict(sigma_phase=0.05, mu_z=0.01, sigma_z=0.01, mu_f=15.0, sigma_f=8.0, var_phase=0.25, var_z=0.05, var_f=0.05, alpha=0.5,
@@ -1714,8 +1720,8 @@ class GroundEstimator:
         det.update(ground=gnd.ground, normal=gnd.normal)
         env.whole_body_controller(..., normal=gnd.normal[:, stance_idx])
         mpc.solve(..., height=gnd.trunk[:, 0] + h_nominal)
-    Nothing takes it by default. Not covered: per-foot local patches, normals inside the MPC's cone or the leg controller's clip, slip
-    detection, the planner's foothold search (which keeps reading the heightfield)."""
+    Nothing takes it by default. Not covered: per-foot local patches, normals inside the MPC's cone or the leg controller's clip,
+    the planner's foothold search (which keeps reading the heightfield)."""
 
     DEFAULTS = dict(c_on=0.5, tau_age=0.5, lambda_=0.01, slope_max=0.7, tilt_gain=1.0)
 
@@ -1781,6 +1787,82 @@ class GroundEstimator:
         env = self.env
         self._launch(contact, base_pos=base_pos, quat=quat, query_xy=query_xy, reset_mask=env.reset_buf.to(torch.int32))
         return self.ground
+
+
+class SlipDetector:
+    """The foot slip detector and friction estimate of wbc_sim_slip_detect for every env (after Focchi et al., "Slip Detection and
+    Recovery for Quadruped Robots"): per foot a test of the foot origin's tangential world velocity with hysteresis and a dwell time,
+    and a friction coefficient from the ratio of tangential to normal force while the foot slides, fused per env, next to a lower bound
+    from the feet that stick. It owns the cfg, the state [N, 4, 8] (per foot p, s, t, c_prev, d, mu_i, w_i, m_i) and every output, and
+    advances them by one launch per update(). Keyword arguments are the fields of wbc_slip_cfg (include/wbc_sim.h); dt defaults to
+    env.dt. The defaults are UNTUNED. The detector starts reset. Use it as
+        slip.update(det.prob, foot_force=det.foot_forces, state=est, gyro=att.gyro)     # or a flag, or planner.contact
+        est.update(contact=slip.weight)
+        gnd.update(contact=slip.weight)
+        env.whole_body_controller(..., mu=slip.mu)
+    Nothing takes it by default. Not covered: slip recovery (re-planning the force or the foothold), a friction coefficient per env
+    inside the MPC, estimating the normal from the slip direction, tuning of any default."""
+
+    DEFAULTS = dict(c_on=0.5, v_slip=0.15, sigma_v=0.05, alpha=0.5, p_on=0.6, p_off=0.3, t_dwell=0.02, common_mode=0.0, fn_min=10.0,
+                    gamma=0.995, w_min=1.0, mu_prior=0.5, mu_min=0.1, mu_max=1.5, mu_scale=0.9)
+
+    def __init__(self, env, dt: float = None, **cfg):
+        unknown = set(cfg) - set(self.DEFAULTS)
+        assert not unknown, f"unknown slip-detector parameters: {sorted(unknown)}"
+        v = dict(self.DEFAULTS, **cfg)
+        self.env = env
+        self.cfg = abi.WbcSlipCfg(float(env.dt if dt is None else dt), *[float(v[k]) for k in self.DEFAULTS])
+        n, dev = env.num_envs, env.device
+        z = lambda *sh, dtype=torch.float32: torch.zeros(sh, dtype=dtype, device=dev)
+        self.state = z(n, 4, abi.SLIP_NS)
+        self.prob, self.slip, self.weight, self.foot_vel = z(n, 4), z(n, 4, dtype=torch.uint8), z(n, 4), z(n, 4, 3)
+        self.speed, self.distance, self.mu, self.mu_lower, self.mu_env = z(n, 4), z(n, 4), z(n, 4), z(n, 4), z(n, 2)
+        self.info = z(n, dtype=torch.int32)
+        self._none = z(n, 4)
+        self.last_inputs = None
+        self.reset()
+
+    def _outputs(self):
+        return (self.state, self.prob, self.slip, self.weight, self.foot_vel, self.speed, self.distance, self.mu, self.mu_lower, self.mu_env,
+                self.info)
+
+    def _launch(self, contact, foot_force=None, normal=None, base_vel=None, ang_vel=None, reset_mask=None, reset=False) -> None:
+        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        kw = dict(contact=f(contact), foot_force=f(foot_force), normal=f(normal), base_vel=f(base_vel), ang_vel=f(ang_vel), reset_mask=reset_mask,
+                  reset=reset)
+        self.last_inputs = dict(kw)
+        self.env.sim.slip_detect(self.cfg, self.state, prob=self.prob, slip=self.slip, weight=self.weight, foot_vel=self.foot_vel,
+                                 speed=self.speed, distance=self.distance, mu=self.mu, mu_lower=self.mu_lower, mu_env=self.mu_env,
+                                 info=self.info, **kw)
+
+    def reset(self, env_ids=None) -> None:
+        """Reset every env (env_ids None) or the listed ones: no slip, zero distance, mu_i = mu_prior with no weight. One launch with no
+        foot standing; the other envs are left as they are."""
+        env = self.env
+        if env_ids is None:
+            self._launch(self._none, reset=True)
+            return
+        mask = torch.zeros((env.num_envs,), dtype=torch.int32, device=env.device)
+        mask[torch.as_tensor(env_ids, dtype=torch.long, device=env.device)] = 1
+        tensors = self._outputs()
+        keep = [t.clone() for t in tensors]
+        self._launch(self._none, reset_mask=mask)
+        rest = mask == 0                                                            # the launch also advanced the others: put them back
+        for t, k in zip(tensors, keep):
+            t[rest] = k[rest]
+
+    def update(self, contact, foot_force=None, normal=None, state=None, gyro=None) -> torch.Tensor:
+        """One launch at the sim's current joint state, to be called once per control step; returns slip u8 [N, 4]. contact [N, 4]: a
+        ContactDetector's prob, a flag such as get_foot_contacts() or a FootstepPlanner's contact. foot_force [N, 4, 3] (world): the
+        force of the ground on each foot (a ContactDetector's foot_forces), None: no friction update. normal [N, 4, 3]: the ground's
+        normal under each foot (a GroundEstimator's), None: world z. state: a BaseStateEstimator, whose velocity is taken as the
+        trunk's, None: the sim's. gyro [N, 3]: the angular velocity in trunk axes (an AttitudeEstimator's gyro), None: the sim's. Envs
+        flagged in env.reset_buf are reset. Results: .slip, .prob, .weight, .foot_vel, .speed, .distance, .mu, .mu_lower, .mu_env,
+        .info; the tensors handed to the kernel are kept in last_inputs."""
+        env = self.env
+        base_vel = None if state is None else state.velocity
+        self._launch(contact, foot_force=foot_force, normal=normal, base_vel=base_vel, ang_vel=gyro, reset_mask=env.reset_buf.to(torch.int32))
+        return self.slip
 
 
 class ImuModel:

@@ -81,6 +81,7 @@ def lib():
                                           [c_void] * 2 + [c_int] + [c_void] * 5)
         L.wbc_sim_attitude_filter.argtypes = [c_void, C.POINTER(abi.WbcAttitudeCfg)] + [c_void] * 5 + [c_int] + [c_void] * 2 + [c_int] + [c_void] * 8
         L.wbc_sim_ground_estimate.argtypes = [c_void, C.POINTER(abi.WbcGroundCfg)] + [c_void] * 6 + [c_int] * 2 + [c_void] * 9
+        L.wbc_sim_slip_detect.argtypes = [c_void, C.POINTER(abi.WbcSlipCfg)] + [c_void] * 9 + [c_int] + [c_void] * 12
         L.wbc_sim_centroidal_mpc.argtypes = [c_void, C.POINTER(abi.WbcMpcCfg)] + [c_void] * 4 + [c_int] + [c_void] * 3 + [c_int] + [c_void] * 8
         L.wbc_sim_centroidal_mpc_workspace_floats.argtypes = [c_int]
         L.wbc_sim_centroidal_mpc_workspace_floats.restype = C.c_size_t
@@ -167,7 +168,7 @@ EXPORTED_SYMBOLS = [
     "wbc_sim_set_root_state_indexed", "wbc_sim_set_dof_state_indexed", "wbc_sim_refresh_dof_state",
     "wbc_sim_refresh_root_state", "wbc_sim_refresh_net_contact_force", "wbc_sim_refresh_force_sensor",
     "wbc_sim_refresh_rigid_body_state", "wbc_sim_get_step_counter", "wbc_sim_set_step_counter", "wbc_gae_compute",
-    "wbc_gae_normalize", "wbc_gae_workspace_doubles", "wbc_abi_sizes", "wbc_sim_episode_stats", "wbc_rollout_store", "wbc_hist_latent", "wbc_sim_arm_dynamics", "wbc_sim_body_dynamics", "wbc_sim_inverse_dynamics", "wbc_sim_mass_solve", "wbc_sim_forward_dynamics", "wbc_sim_body_accelerations", "wbc_sim_constrained_dynamics", "wbc_sim_constrained_dynamics_workspace_floats", "wbc_sim_constrained_dynamics_derivatives", "wbc_sim_constrained_dynamics_derivatives_workspace_floats", "wbc_sim_impulse_dynamics", "wbc_sim_impulse_dynamics_workspace_floats", "wbc_sim_inverse_kinematics", "wbc_sim_task_inverse_dynamics", "wbc_sim_task_inverse_dynamics_workspace_floats", "wbc_sim_task_inverse_dynamics_qp", "wbc_sim_task_inverse_dynamics_qp_workspace_floats", "wbc_sim_centroidal", "wbc_sim_inverse_dynamics_derivatives", "wbc_sim_forward_dynamics_derivatives", "wbc_sim_forward_dynamics_derivatives_workspace_floats", "wbc_sim_inverse_dynamics_regressor", "wbc_sim_forward_dynamics_sensitivity", "wbc_sim_identification_accumulate", "wbc_sim_identification_solve", "wbc_sim_proximity_pair_count", "wbc_sim_proximity_pairs", "wbc_sim_proximity", "wbc_sim_leg_odometry", "wbc_sim_footstep_plan", "wbc_sim_contact_detect", "wbc_sim_leg_control", "wbc_sim_attitude_filter", "wbc_sim_ground_estimate", "wbc_sim_centroidal_mpc", "wbc_sim_centroidal_mpc_workspace_floats", "wbc_policy_act", "wbc_policy_pack", "wbc_policy_pack_floats", "wbc_ppo_minibatch_grad", "wbc_ppo_minibatch_grad_packed", "wbc_ppo_pack_invalidate", "wbc_ppo_clip_adam", "wbc_ppo_clip_adam_packed", "wbc_ppo_clip_adam_workspace_floats", "wbc_ppo_grad_floats",
+    "wbc_gae_normalize", "wbc_gae_workspace_doubles", "wbc_abi_sizes", "wbc_sim_episode_stats", "wbc_rollout_store", "wbc_hist_latent", "wbc_sim_arm_dynamics", "wbc_sim_body_dynamics", "wbc_sim_inverse_dynamics", "wbc_sim_mass_solve", "wbc_sim_forward_dynamics", "wbc_sim_body_accelerations", "wbc_sim_constrained_dynamics", "wbc_sim_constrained_dynamics_workspace_floats", "wbc_sim_constrained_dynamics_derivatives", "wbc_sim_constrained_dynamics_derivatives_workspace_floats", "wbc_sim_impulse_dynamics", "wbc_sim_impulse_dynamics_workspace_floats", "wbc_sim_inverse_kinematics", "wbc_sim_task_inverse_dynamics", "wbc_sim_task_inverse_dynamics_workspace_floats", "wbc_sim_task_inverse_dynamics_qp", "wbc_sim_task_inverse_dynamics_qp_workspace_floats", "wbc_sim_centroidal", "wbc_sim_inverse_dynamics_derivatives", "wbc_sim_forward_dynamics_derivatives", "wbc_sim_forward_dynamics_derivatives_workspace_floats", "wbc_sim_inverse_dynamics_regressor", "wbc_sim_forward_dynamics_sensitivity", "wbc_sim_identification_accumulate", "wbc_sim_identification_solve", "wbc_sim_proximity_pair_count", "wbc_sim_proximity_pairs", "wbc_sim_proximity", "wbc_sim_leg_odometry", "wbc_sim_footstep_plan", "wbc_sim_contact_detect", "wbc_sim_leg_control", "wbc_sim_attitude_filter", "wbc_sim_ground_estimate", "wbc_sim_slip_detect", "wbc_sim_centroidal_mpc", "wbc_sim_centroidal_mpc_workspace_floats", "wbc_policy_act", "wbc_policy_pack", "wbc_policy_pack_floats", "wbc_ppo_minibatch_grad", "wbc_ppo_minibatch_grad_packed", "wbc_ppo_pack_invalidate", "wbc_ppo_clip_adam", "wbc_ppo_clip_adam_packed", "wbc_ppo_clip_adam_workspace_floats", "wbc_ppo_grad_floats",
     "wbc_ppo_num_splits", "wbc_ppo_workspace_floats", "wbc_ppo_sq_partials_offset", "wbc_hist_train_grad", "wbc_hist_train_grad_floats",
     "wbc_hist_train_workspace_floats", "wbc_hist_clip_adam", "wbc_priv_latent", "wbc_runner_track_episodes", "wbc_sim_episode_stats_track", "wbc_tensor_spec", "wbc_policy_act_job", "wbc_sim_episode_stats_job", "wbc_side_job_run",
     "wbc_runner_track_state_floats", "wbc_asset_load", "wbc_asset_free", "wbc_asset_dof_count", "wbc_asset_rigid_body_count", "wbc_asset_dof_name",

@@ -840,6 +840,39 @@ class WbcSim:
                                              nq, abi.GROUND_RESET if reset else 0, state.data_ptr(),
                                              *[ptr(outputs.get(k)) for k in self.GROUND_OUTPUTS], self._stream()), "wbc_sim_ground_estimate")
 
+    # ---- foot slip detection and friction estimate (include/wbc_sim.h: wbc_sim_slip_detect) -------------------------------------------------
+    SLIP_OUTPUTS = ("prob", "slip", "weight", "foot_vel", "speed", "distance", "mu", "mu_lower", "mu_env", "info")
+
+    def slip_detect(self, cfg: "abi.WbcSlipCfg", state: torch.Tensor, contact: torch.Tensor, quat: Optional[torch.Tensor] = None,
+                    dof: Optional[torch.Tensor] = None, base_vel: Optional[torch.Tensor] = None, ang_vel: Optional[torch.Tensor] = None,
+                    foot_force: Optional[torch.Tensor] = None, normal: Optional[torch.Tensor] = None,
+                    reset_mask: Optional[torch.Tensor] = None, mu_init: Optional[torch.Tensor] = None, reset: bool = False, **outputs) -> None:
+        """One wbc_sim_slip_detect launch on the current stream: one control step of the foot slip detector and friction estimate on the
+        caller-owned state f32 [N, 4, 8] (per foot p, s, t, c_prev, d, mu_i, w_i, m_i), in place. contact f32 [N, 4]: a foot stands iff
+        its entry, clamped to [0, 1], is >= cfg.c_on. quat [N, 4] (xyzw), dof [N, 20, 2], base_vel [N, 3] (world) and ang_vel [N, 3]
+        (trunk axes), None: the sim's current state. foot_force [N, 4, 3] (world), None: no friction update. normal [N, 4, 3], None:
+        world z. reset=True resets every env, reset_mask int32 [N] the envs whose entry is not 0, to mu_init [N, 4] (None: cfg.mu_prior).
+        Outputs by keyword, each a caller-owned tensor that is filled (SLIP_OUTPUTS): prob, weight, speed, distance, mu, mu_lower
+        [N, 4], slip u8 [N, 4], foot_vel [N, 4, 3], mu_env [N, 2], info int32 [N]."""
+        n = self.num_envs
+        unknown = set(outputs) - set(self.SLIP_OUTPUTS)
+        assert not unknown, f"unknown outputs: {sorted(unknown)}"
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        shapes = dict(prob=((n, 4), f32), slip=((n, 4), u8), weight=((n, 4), f32), foot_vel=((n, 4, 3), f32), speed=((n, 4), f32),
+                      distance=((n, 4), f32), mu=((n, 4), f32), mu_lower=((n, 4), f32), mu_env=((n, 2), f32), info=((n,), i32))
+        checks = [(state, (n, 4, abi.SLIP_NS), f32), (contact, (n, 4), f32), (quat, (n, 4), f32), (dof, (n, abi.NDOF, 2), f32),
+                  (base_vel, (n, 3), f32), (ang_vel, (n, 3), f32), (foot_force, (n, 4, 3), f32), (normal, (n, 4, 3), f32),
+                  (reset_mask, (n,), i32), (mu_init, (n, 4), f32)]
+        checks += [(outputs.get(k),) + shapes[k] for k in self.SLIP_OUTPUTS]
+        for t, sh, dt in checks:
+            if t is not None:
+                assert t.device == self.arena.device and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == sh, (tuple(t.shape), sh)
+        assert state is not None and contact is not None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None
+        check(self.L.wbc_sim_slip_detect(self.h, C.byref(cfg), ptr(quat), ptr(dof), ptr(base_vel), ptr(ang_vel), ptr(contact), ptr(foot_force),
+                                         ptr(normal), ptr(reset_mask), ptr(mu_init), abi.SLIP_RESET if reset else 0, state.data_ptr(),
+                                         *[ptr(outputs.get(k)) for k in self.SLIP_OUTPUTS], self._stream()), "wbc_sim_slip_detect")
+
     def proximity_damper_rows(self, gap: torch.Tensor, jac: torch.Tensor, d_safe: float, d_influence: float, xi: float, dt: float,
                               nu: Optional[torch.Tensor] = None):
         """The velocity damper of the pairs inside the influence distance as rows on the accelerations, torch ops only: the gap rate

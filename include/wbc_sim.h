@@ -1235,7 +1235,7 @@ int wbc_sim_footstep_plan(wbc_sim* sim, const wbc_footstep_cfg* cfg, const float
  * not finite; alpha outside (0, 1]; p_on or p_off not finite, or p_on <= p_off; t_dwell or damping not finite or < 0; early_min or
  * late_min outside [0, 1]; no measurement source; both force inputs; tau_ext_stride < 26 or phase_stride < 1 where the pointer is given; a
  * misaligned pointer. Then NULL sim; -3 (also: a foot whose leg does not have exactly three joints) / -2 and stream handling as
- * wbc_sim_coriolis. Not covered: feeding the events back into the planner's clock, slip detection, contacts on links other
+ * wbc_sim_coriolis. Not covered: feeding the events back into the planner's clock, contacts on links other
  * than the feet. `ground` and `normal` can be estimated rather than given: wbc_sim_ground_estimate below writes both in this layout. */
 #define WBC_CONTACT_NS 16           /* floats of state per env */
 typedef struct {
@@ -1487,8 +1487,8 @@ int wbc_sim_attitude_filter(wbc_sim* sim, const wbc_attitude_cfg* cfg, const flo
  * in wbc_last_error() that names the entry point, nothing written, checked BEFORE the sim: NULL cfg, state or contact; unknown flag bits;
  * dt, tau_age, lambda or slope_max not finite and > 0; c_on not finite; tilt_gain outside [0, 1]; num_query < 0, or query_xy given with
  * num_query = 0; a misaligned pointer. Then NULL sim; -3 (also: a foot whose leg does not have exactly three joints) / -2 and stream
- * handling as wbc_sim_coriolis. Not covered: per-foot local patches, normals inside the MPC's cone or the leg controller's clip, slip
- * detection, feeding the plane to wbc_sim_footstep_plan (which keeps reading the heightfield). */
+ * handling as wbc_sim_coriolis. Not covered: per-foot local patches, normals inside the MPC's cone or the leg controller's clip,
+ * feeding the plane to wbc_sim_footstep_plan (which keeps reading the heightfield). */
 #define WBC_GROUND_NS 32            /* floats of state per env */
 #define WBC_GROUND_SERIES 1e-4f     /* below this |a|, atan(s) / s is taken from its series */
 typedef struct {
@@ -1509,6 +1509,99 @@ int wbc_sim_ground_estimate(wbc_sim* sim, const wbc_ground_cfg* cfg, const float
                             const float* contact, const int32_t* reset_mask, const float* query_xy, int num_query, int flags, float* state,
                             float* normal, float* ground, float* residual, float* trunk, float* theta_ref, float* query_z, int32_t* info,
                             void* stream);
+
+/* One control step of the foot slip detector and friction estimate, the layer that tells wbc_sim_leg_odometry and
+ * wbc_sim_ground_estimate how far a standing foot can be trusted to stand still, and wbc_sim_task_inverse_dynamics_qp which friction
+ * coefficient its pyramid should take: a per-foot velocity test with hysteresis, and a friction estimate from the force ratio while the
+ * foot slides (Focchi, Barasuol, Frigerio, Caldwell, Semini, "Slip Detection and Recovery for Quadruped Robots", ISRR 2015). OURS, not
+ * the paper's: the evidence is a probability Phi of the tangential speed, low-passed, with hysteresis and a dwell time (the paper
+ * compares each foot's speed with the median of the feet's); the common mode is a contact-weighted mean with a gain; the estimate is a
+ * weighted running mean with forgetting per foot, fused per env, next to a lower bound from the feet that stick; a foot in the air cannot
+ * start slipping. One launch (wbc_slip_detect_kernel); the sim's state is read, never written. The base POSITION is never read (there is
+ * no such argument): every output is bit-identical under a translation of the robot. Per env the caller owns
+ * state  device f32 [N, 4, WBC_SLIP_NS = 8], read and written; per foot (feet_rb order FL, FR, RL, RR): 0 p the filtered slip
+ *        probability; 1 s the slip flag (0.0 or 1.0; read as != 0); 2 t the dwell timer, s; 3 c_prev, whether the foot stood in the last
+ *        call (0.0 or 1.0; read as != 0); 4 d the distance slid in this stance, m; 5 mu_i this foot's friction estimate; 6 w_i the weight
+ *        of mu_i; 7 m_i the sticking bound: the largest force ratio seen while not slipping, forgotten at rate gamma.
+ * INPUTS (device f32 unless said otherwise; each but contact may be NULL):
+ * quat [N, 4] xyzw, normalised in the call: R (world <- trunk). NULL: ROOT_STATES'.   dof [N, 20, 2] in the layout of DOF_STATE; the
+ *        positions q and the velocities qd of the leg joints are read. NULL: DOF_STATE.
+ * base_vel [N, 3]: the world linear velocity v of the trunk origin (a BaseStateEstimator's v fits). NULL: ROOT_STATES'.
+ * ang_vel [N, 3]: the trunk's angular velocity w in TRUNK axes (wbc_sim_attitude_filter's gyro_out fits). NULL: R^T times ROOT_STATES'
+ *        (which is in world axes).
+ * contact [N, 4], required: wbc_sim_contact_detect's prob, a 0 / 1 flag or wbc_sim_footstep_plan's contact.
+ * foot_force [N, 4, 3], world axes: the force of the ground on the foot (wbc_sim_contact_detect's force). NULL: step 7 is left out, slots
+ *        5 .. 7 of the state keep their values, info bit WBC_SLIP_INFO_NO_FORCE.
+ * normal [N, 4, 3]: the ground's normal under each foot, normalised in the call: n_i = normal_i / |normal_i|. NULL: world z.
+ * reset_mask int32 [N].   mu_init [N, 4], NULL: mu_prior.
+ * PER ENV AND FOOT i, in this order (Phi(x) = (1/2) (1 + erf(x / sqrt 2)), wbc_sim_contact_detect's). A sum over the four feet is taken
+ * pairwise, (x_0 + x_1) + (x_2 + x_3).
+ * 1 KINEMATICS  the leg walk of wbc_sim_contact_detect step 2: fk_i(q) in trunk axes, a_k the axis and o_k the origin of the leg's k-th
+ *   actuated joint (k = 0, 1, 2 from the trunk down), c_k = a_k x (fk_i - o_k). The foot origin's world velocity is
+ *     u_i = v + R (w x fk_i + ((qd_0 c_0 + qd_1 c_1) + qd_2 c_2)).
+ * 2 RESET (WBC_SLIP_RESET in flags: every env; otherwise the envs whose reset_mask entry is not 0; the env's state is then not read):
+ *   p = 0, s = 0, t = t_dwell, c_prev = 0, d = 0, w_i = 0, m_i = 0, mu_i = mu_init_i (NULL: mu_prior); info bit WBC_SLIP_INFO_RESET. The
+ *   env then goes through steps 3 .. 9 of this very call with that state.
+ * 3 STANDING  c_i = min(max(contact_i, 0), 1), stand_i = c_i >= c_on. A touchdown (stand_i and c_prev = 0) sets d = 0.
+ * 4 COMMON MODE  a wrong base_vel moves every foot alike, so it can be taken out. With cw_j = c_j where foot j stands and 0 elsewhere,
+ *   S = sum_j cw_j: where at least two feet stand and S > 0, ubar = (sum_j cw_j u_j) / S per coordinate, otherwise ubar = 0.
+ *   g_i = u_i - common_mode ubar, its tangential part gt_i = g_i - n_i (n_i . g_i), the slip speed s_i = |gt_i|.
+ * 5 EVIDENCE  P_i = c_i Phi((s_i - v_slip) / sigma_v) where foot i stands, 0 elsewhere;  p <- p + alpha (P_i - p).
+ * 6 FLAG  t <- t + dt. If the foot does not stand and s = 1: s <- 0, t <- 0, info bit WBC_SLIP_INFO_END << i. Else if it stands, s = 0,
+ *   p >= p_on and t >= t_dwell: s <- 1, t <- 0, info bit WBC_SLIP_INFO_START << i. Else if s = 1, p <= p_off and t >= t_dwell: s <- 0,
+ *   t <- 0, info bit WBC_SLIP_INFO_END << i. Then d <- d + s_i dt where s = 1, c_prev <- stand_i, and info bit
+ *   WBC_SLIP_INFO_SLIPPING << i where s = 1.
+ * 7 FRICTION (with foot_force only)  fn = n_i . f_i, ft = |f_i - n_i fn|, valid = stand_i and fn >= fn_min, rho = ft / fn.
+ *   m_i <- gamma m_i, and where valid and s = 0: m_i <- max(m_i, rho). w_i <- gamma w_i, and where valid, s = 1 and p > 0:
+ *   w_i <- w_i + p, then mu_i <- mu_i + (p / w_i) (rho - mu_i). A sticking foot bounds the coefficient from below; a sliding foot measures
+ *   it. Info bit WBC_SLIP_INFO_MU_VALID << i where w_i >= w_min (with or without foot_force).
+ * 8 FUSE, per env: W = sum_i w_i; mu_env = (sum_i w_i mu_i) / W where W >= w_min, mu_prior elsewhere. Per foot mu_raw = mu_i where
+ *   w_i >= w_min, mu_env elsewhere.
+ * 9 OUTPUTS, each may be NULL and is then not written; what is written never depends on which are asked for:
+ *   prob f32 [N, 4] = p;   slip u8 [N, 4] = s;   weight f32 [N, 4] = c_i (1 - p): what wbc_sim_leg_odometry and wbc_sim_ground_estimate
+ *   should take as contact;   foot_vel f32 [N, 4, 3] = u_i;   speed f32 [N, 4] = s_i;   distance f32 [N, 4] = d;
+ *   mu f32 [N, 4] = min(max(mu_scale mu_raw, mu_min), mu_max): the layout wbc_sim_task_inverse_dynamics_qp takes;
+ *   mu_lower f32 [N, 4] = m_i;   mu_env f32 [N, 2] = (mu_env, W);   info int32 [N]: the bits below.
+ * 10 FAILURE  an env that reads a value that is not finite (quat, or a zero quat; v; w; a leg joint's q or qd; contact; foot_force; normal,
+ *   or a zero normal; mu_init where it is reset; unless it is reset, the eight floats of state of any foot), or whose u_i or new p, t, d,
+ *   mu_i, w_i or m_i comes out not finite, writes zeros to every float and byte output, info = WBC_SLIP_INFO_FAILED alone, and leaves its
+ *   state as it was; no other env is affected.
+ * Every pointer needs 4-byte alignment only (the u8 output none). No workspace; nothing is allocated and nothing synchronises: safe under
+ * stream capture. -1 with a message in wbc_last_error() that names the entry point, nothing written, checked BEFORE the sim: NULL cfg,
+ * state or contact; unknown flag bits; dt, sigma_v, fn_min, w_min or mu_scale not finite and > 0; c_on not finite; v_slip, t_dwell,
+ * mu_prior or mu_min not finite or < 0; alpha or gamma outside (0, 1]; p_on or p_off not finite, or p_on <= p_off; common_mode outside
+ * [0, 1]; mu_max not finite or < mu_min; a misaligned pointer. Then NULL sim; -3 (also: a foot whose leg does not have exactly three
+ * joints) / -2 and stream handling as wbc_sim_coriolis. Not covered: slip recovery (re-planning the force or the foothold), a friction
+ * coefficient per env inside the MPC, estimating the normal from the slip direction, tuning of any default. */
+#define WBC_SLIP_NS 8               /* floats of state per foot */
+typedef struct {
+  float dt;                         /* control step, s */
+  float c_on;                       /* a foot stands iff its clamped contact >= c_on */
+  float v_slip, sigma_v;            /* mean and width of the slip speed's evidence, m/s */
+  float alpha;                      /* low-pass weight of the filtered probability, (0, 1] */
+  float p_on, p_off;                /* hysteresis thresholds, p_on > p_off */
+  float t_dwell;                    /* minimum seconds between flag switches, >= 0 */
+  float common_mode;                /* share of the standing feet's mean velocity that is taken out, [0, 1] */
+  float fn_min;                     /* smallest normal force at which the force ratio is used, N, > 0 */
+  float gamma;                      /* forgetting factor per call of w_i and m_i, (0, 1] */
+  float w_min;                      /* weight from which an estimate counts, > 0 */
+  float mu_prior;                   /* the coefficient where nothing has been measured */
+  float mu_min, mu_max;             /* clamp of the mu output */
+  float mu_scale;                   /* safety factor of the mu output, > 0 */
+} wbc_slip_cfg;
+#define WBC_SLIP_RESET 1
+#define WBC_SLIP_INFO_RESET 1
+#define WBC_SLIP_INFO_FAILED 2
+#define WBC_SLIP_INFO_NO_FORCE 4
+#define WBC_SLIP_INFO_START 16                /* << foot */
+#define WBC_SLIP_INFO_END 256                 /* << foot */
+#define WBC_SLIP_INFO_SLIPPING 4096           /* << foot */
+#define WBC_SLIP_INFO_MU_VALID 65536          /* << foot */
+int wbc_sim_slip_detect(wbc_sim* sim, const wbc_slip_cfg* cfg, const float* quat, const float* dof, const float* base_vel,
+                        const float* ang_vel, const float* contact, const float* foot_force, const float* normal,
+                        const int32_t* reset_mask, const float* mu_init, int flags, float* state, float* prob, uint8_t* slip, float* weight,
+                        float* foot_vel, float* speed, float* distance, float* mu, float* mu_lower, float* mu_env, int32_t* info,
+                        void* stream);
 
 /* First-order layer of wbc_sim_inverse_dynamics / wbc_sim_forward_dynamics: the analytic partial derivatives of tau(q, nu, nudot) and
  * of nudot(q, nu, tau) in the coordinates of wbc_sim_body_dynamics, from the sim's current root / DoF state, WBC_T_BODY_PARAMS and all

@@ -3,7 +3,7 @@
 defaults of BaseStateEstimator, FootstepPlanner, CentroidalMPC and whole_body_controller.
 
   python tools/classical_trot.py [--envs 64] [--seconds 4] [--speed 0.3] [--gait trot] [--detector] [--controller qp|leg] [--height H]
-                                 [--attitude [--gyro-bias B]] [--ground]
+                                 [--attitude [--gyro-bias B]] [--ground] [--slip] [--friction MU]
 
 Prints, once per simulated second and at the end: the share of envs still upright (trunk z axis within 0.5 rad of vertical and the trunk
 above 0.15 m), the mean forward speed of the upright envs against the command, and the MPC / QP / planner status counts.
@@ -31,7 +31,18 @@ gnd.ground and gnd.normal, the task QP gnd.normal, and with --height H the MPC's
 estimated plane under the trunk (without --height the MPC keeps the current height as before). It then also prints, once per simulated
 second, the estimated slope and the error of the feet's clearance gnd.ground - est z against the truth (the plane: the foot sphere's
 radius above z = 0, less the trunk's true height); the loop of estimator and plane has no absolute height, so only that difference means
-anything."""
+anything.
+
+--friction MU (default: the env's randomised draws) makes MU the coefficient that the step kernel's contact law applies between every
+env's feet and the terrain: the law combines the env's WBC_T_FRICTION with the cfg's terrain_friction by their mean (DESIGN.md section
+3), so every env's WBC_T_FRICTION is set to 2 MU - terrain_friction, through set_env_params.
+
+--slip (default off) puts the slip detector and friction estimate (env.slip_detector: wbc_sim_slip_detect) into the loop, on the
+planner's contact (det.prob with --detector), the estimator's velocity, att.gyro with --attitude, gnd.normal with --ground and the foot
+forces (det.foot_forces with --detector, otherwise the sim's net contact forces on the feet): the leg odometry and the ground estimator
+take slip.weight as contact and the task QP slip.mu as its friction coefficient. It then also prints, once per simulated second, the
+share of stance foot-steps flagged as slipping so far and, over the upright envs with a MU_VALID foot, the median and the 90th
+percentile of |mu_env - mu_true| / mu_true, mu_true the coefficient the contact law applies (MU with --friction)."""
 import argparse
 import os
 import sys
@@ -49,6 +60,8 @@ ap.add_argument("--height", type=float, default=None, help="reference height of 
 ap.add_argument("--attitude", action="store_true", help="orientation and gyro for the leg odometry from the attitude filter on an IMU model")
 ap.add_argument("--gyro-bias", type=float, default=0.0, help="constant gyro bias of the IMU model, rad/s on every axis (with --attitude)")
 ap.add_argument("--ground", action="store_true", help="foot heights, normals and the MPC's reference height from the blind terrain estimate")
+ap.add_argument("--slip", action="store_true", help="slip detector in the loop: its weight for the estimators, its mu for the task QP")
+ap.add_argument("--friction", type=float, default=None, help="the foot-terrain friction coefficient of every env (default: the randomised draws)")
 a = ap.parse_args()
 
 sys.path.insert(0, os.path.join(ROOT, "deep-whole-body-control_amd"))
@@ -82,6 +95,12 @@ agree, events, tau = [0, 0], dict(early=0, late=0, touchdown=0, liftoff=0), None
 att = env.attitude_estimator() if a.attitude else None
 imu = env.imu(gyro_bias=a.gyro_bias, gyro_noise=0.002, accel_noise=0.05, heading_noise=0.01, seed=2) if a.attitude else None
 gnd = env.ground_estimator() if a.ground else None
+terrain_mu = float(env.cfg.terrain.static_friction)
+if a.friction is not None:
+    env.sim.set_env_params(friction=[2.0 * a.friction - terrain_mu] * n)
+mu_true = ((env.friction_coeffs_tensor.reshape(n).to(torch.float32) + terrain_mu) / 2).clamp(min=0.0)   # the contact law's coefficient
+slip = env.slip_detector() if a.slip else None
+slipped = [0, 0]
 h_nominal = None
 x_start = env.root_states[:, 0].clone()
 
@@ -117,6 +136,13 @@ def report(label, k):
               f"clearance below the trunk mean {gerr.mean().item() * 1e3:.2f} max {gerr.max().item() * 1e3:.2f} mm, |residual| max "
               f"{gnd.residual[up].abs().max().item() * 1e3:.2f} mm, estimator z - true z mean "
               f"{(est.position[:, 2] - env.root_states[:, 2])[up].mean().item() * 1e3:.2f} mm", flush=True)
+    if slip is not None:
+        have = up & (((slip.info >> 16) & 15) != 0)
+        err = ((slip.mu_env[:, 0] - mu_true).abs() / mu_true.clamp(min=1e-6))[have]
+        q = lambda p: f"{torch.quantile(err, p).item():.3f}" if err.numel() else "none"
+        print(f"    slip: {slipped[0] / max(slipped[1], 1):.4f} of the stance foot-steps flagged ({slipped[0]} of {slipped[1]}); {int(have.sum())} upright envs "
+              f"with MU_VALID, |mu_env - mu_true| / mu_true median {q(0.5)} 90 % {q(0.9)} (mu_true mean {mu_true.mean().item():.3f}, mu_env mean "
+              f"{slip.mu_env[:, 0].mean().item():.3f})", flush=True)
 
 
 planner = stand
@@ -135,8 +161,17 @@ for k in range(steps):
         att.update(gyro=gyro, accel=accel, aux=(heading, imu.heading_world, 0.05))
         ekw = dict(quat=att.quat, gyro=att.gyro, accel=accel)
     gkw, height = {}, a.height
+    contact_in = dets[id(planner)].prob if a.detector else planner.contact            # of the step before
+    if slip is not None:
+        force = dets[id(planner)].foot_forces if a.detector else env.contact_forces[:, env.feet_indices, :]
+        slip.update(contact_in, foot_force=force, normal=gnd.normal if gnd is not None and k > 0 else None, state=est,
+                    gyro=att.gyro if att is not None else None)
+        contact_in = slip.weight
+        if k >= settle:
+            stance_now = slip.last_inputs["contact"] >= slip.cfg.c_on
+            slipped[0] += int((slip.slip.bool() & stance_now).sum()); slipped[1] += int(stance_now.sum())
     if gnd is not None:                                                                # on the contact and the position of the step before
-        gnd.update(dets[id(planner)].prob if a.detector else planner.contact, base_pos=est.position)
+        gnd.update(contact_in, base_pos=est.position)
         ekw["foot_height"] = gnd.ground
         gkw = dict(ground=gnd.ground, normal=gnd.normal)
         if h_nominal is not None:
@@ -144,9 +179,9 @@ for k in range(steps):
     if a.detector:
         det = dets[id(planner)]
         det.update(torques=tau, **gkw)                                                 # tau: what the last simulate calls applied (None at the start: env.torques)
-        est.update(contact=det.prob, **ekw)
+        est.update(contact=slip.weight if slip is not None else det.prob, **ekw)
     else:
-        est.update(contact=planner.contact, **ekw)
+        est.update(contact=slip.weight if slip is not None else planner.contact, **ekw)
     planner.update(c, wz, state=est)
     mpc.solve(planner.contact_schedule, c, wz, height=height, foot_positions=planner.foot_positions, state=est)
     if ctl is not None:
@@ -154,7 +189,8 @@ for k in range(steps):
     else:
         tau, nudot, lam, info = env.whole_body_controller(base_acc=mpc.base_acc, swing_acc=planner.swing_acc,
                                                           stance=det.stance if a.detector else planner.stance,
-                                                          normal=gnd.normal if gnd is not None else None)
+                                                          normal=gnd.normal if gnd is not None else None,
+                                                          **(dict(mu=slip.mu) if slip is not None else {}))
     env.sim.set_dof_forces(tau.contiguous())
     for _ in range(decimation):
         env.sim.simulate()
