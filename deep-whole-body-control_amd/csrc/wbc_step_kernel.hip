@@ -1045,6 +1045,8 @@ __device__ void physics_substep(Smem& s, CP C, const ChainRegs& cr, const int ch
   }
   if (lane < WBC_NB) s.qddD[lane] = 0.f;
   if (lane < 6) { AD(s)[0][lane] = 0.f; s.bxa[lane] = 0.f; }
+  float bfx = 0.f, bfy = 0.f, bfz = 0.f;        // lanes 32..47 keep their scan values of the last sweep; only lane 47's is the complete sum
+  //                                               (the net contact force on the box), and only that one is read
   // the per-body contact wrenches pD (every active contact ADDS its own; zeroed again by the sweep that consumed them)
   for (int t = lane; t < WBC_NB * 6; t += LANES) (&PD(s)[0][0])[t] = 0.f;
   WSYNC();
@@ -1172,6 +1174,7 @@ __device__ void physics_substep(Smem& s, CP C, const ChainRegs& cr, const int ch
         const float nx = row_scan16(mom.x), ny = row_scan16(mom.y), nz = row_scan16(mom.z);
         const float fx = row_scan16(f.x), fy = row_scan16(f.y), fz = row_scan16(f.z);
         if (lane == 47) { st3(&s.bxa[0], mk3(nx, ny, nz) * s.bxiI); st3(&s.bxa[3], mk3(fx, fy, fz) * s.bxim); }
+        bfx = fx; bfy = fy; bfz = fz;
       }
       if (any_tree) {
         if (it == 0) STAMP(21);
@@ -1305,8 +1308,10 @@ __device__ void physics_substep(Smem& s, CP C, const ChainRegs& cr, const int ch
     const f3 n1 = mk3(__shfl(cn.x, kc1), __shfl(cn.y, kc1), __shfl(cn.z, kc1));
     const f3 n2 = mk3(__shfl(cn.x, src2), __shfl(cn.y, src2), __shfl(cn.z, src2));
     // lanes 0..27: net force on rigid body `lane` (+ as the sphere's body, - as the partner of a pair); row 27 is the box actor
-    if (lane == WBC_BOX_RB) {                     // the box actor's row: the net force the last sweep's row reduction left (F = m a)
-      st3(s.out_contact[lane], mat_mul(s.R, ld3(&s.bxa[3]) * (1.f / s.bxim)));
+    const f3 bxF = mk3(__shfl(bfx, 47), __shfl(bfy, 47), __shfl(bfz, 47));
+    if (lane == WBC_BOX_RB) {                     // the box actor's row: the net force the last sweep's row reduction left, itself (not m a:
+      //                                             a lone pair's two rows are minus each other bit for bit, as the spec's are)
+      st3(s.out_contact[lane], mat_mul(s.R, bxF));
     } else if (lane < WBC_NRB) {
       const uint64_t m1 = Cc->out_cp_mask[lane], m2 = Cc->out_cp2_mask[lane];
       f3 acc = mk3(0.f, 0.f, 0.f);

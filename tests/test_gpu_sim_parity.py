@@ -359,45 +359,21 @@ def test_self_collision_candidates_match_oracle(robot):
     g.reset_all()
     torch.cuda.synchronize()
     rng = np.random.default_rng(72)
-    model = robot["model"]
-    names = model.rb_names
-    root = _t(g, "ROOT_STATES").astype(np.float32)
-    dof = _t(g, "DOF_STATE").astype(np.float32)
-    lo, hi = np.array(model.dof_lower, dtype=np.float64), np.array(model.dof_upper, dtype=np.float64)
-    free = ~(lo < hi)
-    lo[free], hi[free] = -np.pi, np.pi
-    lo[18:], hi[18:] = 0.0, 0.0
-    half = n // 2
-    root[:, 0, 2] = 1.2                                                        # in the air for the five steps: no terrain contact
-    root[:, 0, 7:] = 0
-    dof[:, :, 1] = 0
-    dof[:half, :, 0] = rng.uniform(lo, hi, (half, 20))                          # every joint anywhere
-    q = np.array(tc.default_dof_pos, dtype=np.float64)[None] + rng.uniform(-0.3, 0.3, (n - half, 20))
-    leg = rng.integers(0, 4, n - half)
-    for e in range(n - half):                                                  # one hip rolled inward, that leg swung at its neighbour
-        q[e, 3 * leg[e]] = (-1 if leg[e] % 2 == 0 else 1) * rng.uniform(0.6, 1.04)
-        q[e, 3 * leg[e] + 1] = rng.uniform(-0.6, 2.9)
-    dof[half:, :, 0] = np.clip(q, lo, hi)
-    dof[:, 18:, 0] = 0
-    # boxes: at a knee / a shin / under the trunk of every third robot (else far away), at rest
-    g.tensor("ROOT_STATES").copy_(torch.from_numpy(root)); g.tensor("DOF_STATE").copy_(torch.from_numpy(dof))
-    g.refresh_rigid_body_state()
-    torch.cuda.synchronize()
-    rb = _t(g, "RIGID_BODY_STATE")
-    root[:, 1, :3] = root[:, 0, :3] + np.array([3.0, 0.0, -1.15])
-    root[:, 1, 3:7] = [0, 0, 0, 1]; root[:, 1, 7:] = 0
-    targets = [names.index(k) for k in ("FL_calf", "FR_calf", "RL_calf", "RR_calf", "trunk")]
-    for e in range(0, n, 3):
-        t = targets[(e // 3) % 5]
-        off = rng.uniform(-0.03, 0.03, 3) + (np.array([0, 0, -0.11]) if names[t] == "trunk" else np.array([0.05, 0, rng.choice([0.0, -0.1])]))
-        root[e, 1, :3] = rb[e, t, :3] + off
-        root[e, 1, 3:7] = helpers.random_quat(rng)
-    g.tensor("ROOT_STATES").copy_(torch.from_numpy(root))
+    names = robot["model"].rb_names
+
+    def put(root, dof):
+        g.tensor("ROOT_STATES").copy_(torch.from_numpy(root)); g.tensor("DOF_STATE").copy_(torch.from_numpy(dof))
+
+    def refresh():
+        g.refresh_rigid_body_state()
+        torch.cuda.synchronize()
+    helpers.stage_self_collision(robot, tc, n, rng, lambda name: _t(g, name), put, refresh)
     seen = np.zeros(28, dtype=np.int64)
     legleg = boxhits = 0
     legs_rb = [i for i, nm in enumerate(names) if any(k in nm for k in ("thigh", "calf", "foot"))]
     for step in range(4):
         helpers.sync_oracle_from_gpu(o, g)
+        root_before = _t(g, "ROOT_STATES").astype(np.float64)
         a = (0.3 * rng.normal(size=(n, 18))).astype(np.float32)
         g.step(torch.from_numpy(a).cuda()); o.step(a)
         tag = f"self-collision candidates, step {step}"
@@ -406,9 +382,38 @@ def test_self_collision_candidates_match_oracle(robot):
         fo, fg = o.get("NET_CONTACT_FORCE"), _t(g, "NET_CONTACT_FORCE")
         strong = np.abs(fo).sum(-1) > 0.5
         assert ((np.abs(fg).sum(-1) > 0) == (np.abs(fo).sum(-1) > 0))[strong | (np.abs(fo).sum(-1) == 0)].mean() > 0.998, tag
-        _assert_close_bulk(fg, fo, 0.08, 5e-3, f"{tag} NET_CONTACT_FORCE", frac=4e-3, slack=1e3)
-        _assert_close_bulk(_t(g, "FORCE_SENSOR"), o.get("FORCE_SENSOR"), 0.08, 5e-3, f"{tag} FORCE_SENSOR", frac=4e-3, slack=1e3)
-        for name, atol, rtol in (("DOF_STATE", 6e-4, 1e-3), ("ROOT_STATES", 4e-4, 5e-4), ("TORQUES", 4e-4, 5e-4), ("OBS_BUF", 3e-3, 1e-3)):
+        # Rows are split by whether kernel and oracle ended the step with the SAME set of rigid bodies in contact (the split of the
+        # box-actor test below). Same set: every entry within 10 x its tolerance, all but `frac` within it. Different set -- a limb pair
+        # or a box pair that touches one substep apart in fp32 and in fp64 --: a capped share of the envs (SELF_COLLISION_MAX_SHARE), and
+        # a physical bound on the difference: one of the two has applied impacts the other has not, each at most the largest force
+        # either of them reports in the batch (twice that: one contact more on one side, one fewer on the other; + 50 N for the
+        # depenetration of a contact that only one side has), and the box (at rest before the first step, 1 kg against a robot limb)
+        # moves by at most its closing speed over one policy step.
+        ro, rg = o.get("ROOT_STATES"), _t(g, "ROOT_STATES")
+        same = ((np.abs(fg).sum(-1) > 0) == (np.abs(fo).sum(-1) > 0)).all(1)
+        ndiff = int((~same).sum())
+        assert ndiff <= helpers.SELF_COLLISION_MAX_SHARE * n, f"{tag}: contact sets differ in {ndiff} of {n} envs"
+        wmax = float(max(np.abs(fo).max(initial=1.0), np.abs(fg).max(initial=1.0)))
+        vclose = (np.linalg.norm(root_before[:, 1, 7:10], axis=1) + 0.0866 * np.linalg.norm(root_before[:, 1, 10:13], axis=1)
+                  + np.linalg.norm(root_before[:, 0, 7:10], axis=1) + float(tc.max_depenetration_vel) + 9.81 * 0.02)
+
+        def split(name, got, want, atol, rtol, frac, dbound):
+            got, want = np.asarray(got, np.float64).reshape(n, -1), np.asarray(want, np.float64).reshape(n, -1)
+            if same.any():
+                _assert_close_bulk(got[same], want[same], atol, rtol, f"{tag} {name} (same contact set)", frac=frac, slack=10.0)
+            if ndiff:
+                err = np.abs(got[~same] - want[~same]).max(1)
+                lim = np.broadcast_to(np.asarray(dbound, np.float64), (n,))[~same] if np.ndim(dbound) else np.full(ndiff, float(dbound))
+                assert (err <= lim).all(), f"{tag} {name} (different contact set): {err.max():.3e} against the bound {lim[err.argmax()]:.3e}"
+        split("NET_CONTACT_FORCE", fg, fo, 0.08, 5e-3, 4e-3, 2.0 * wmax + 50.0)
+        split("FORCE_SENSOR", _t(g, "FORCE_SENSOR"), o.get("FORCE_SENSOR"), 0.08, 5e-3, 4e-3, 2.0 * wmax + 50.0)
+        _assert_close_bulk(rg[:, 0], ro[:, 0], 4e-4, 5e-4, f"{tag} ROOT_STATES (robot)", frac=4e-3)
+        split("box pose", rg[:, 1, :7], ro[:, 1, :7], 2e-3, 2e-3, 3e-3, 0.02 * vclose + 0.05)
+        split("box velocity", rg[:, 1, 7:10], ro[:, 1, 7:10], 2e-3, 2e-3, 3e-3, vclose)
+        split("box spin", rg[:, 1, 10:], ro[:, 1, 10:], 2e-3, 2e-3, 3e-3, vclose / 0.05 + 1.0)
+        if ndiff:
+            print(f"{tag}: {ndiff} envs with different contact sets")
+        for name, atol, rtol in (("DOF_STATE", 6e-4, 1e-3), ("TORQUES", 4e-4, 5e-4), ("OBS_BUF", 3e-3, 1e-3)):
             _close(name, _t(g, name), o.get(name), atol, rtol, f"{tag} {name}", frac=4e-3)
         hit = np.abs(fo).sum(-1) > 0
         seen += hit.sum(0)
