@@ -621,15 +621,16 @@ def case_states(robot, name):
     return _STATES[name]
 
 
-def step_states(robot, name):
+def step_states(robot, name, case=None, **cfg):
     """Tier E: (tcfg, terrain, root, dof, actions) -- the staged states of A-256 (plane) or C-256 (grid) tiled over the envs;
-    decimation = 1, the attitude and height terminations out of reach (the staged poses are random attitudes a few cm above the ground)."""
-    case = STEP_CASES[name]
+    decimation = 1, the attitude and height terminations out of reach (the staged poses are random attitudes a few cm above the ground).
+    case: dict(n, seed, source[, sigma]) instead of STEP_CASES[name]; cfg: further fields of the task cfg (tests/decimation_reference.py)."""
+    case = STEP_CASES[name] if case is None else case
     tc, ter, root, dof, _ = case_states(robot, case["source"])
-    tc = case_cfg(tc, decimation=1, term_rp_threshold=100.0, term_z_threshold=-100.0)
+    tc = case_cfg(tc, **dict(dict(decimation=1, term_rp_threshold=100.0, term_z_threshold=-100.0), **cfg))
     idx = np.arange(case["n"]) % len(root)
     rng = np.random.default_rng(case["seed"])
-    act = (STEP_SIGMA * rng.normal(size=(case["n"], 18))).astype(np.float32)
+    act = (case.get("sigma", STEP_SIGMA) * rng.normal(size=(case["n"], 18))).astype(np.float32)
     root, dof = root[idx].copy(), dof[idx].copy()
     dof[:, 12:18, 1] *= 0.25          # the arm slower: the PD torques of the step would otherwise take its light joints into the velocity clamp
     return tc, ter, root, dof, act

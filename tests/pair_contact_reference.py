@@ -380,7 +380,8 @@ def box_integrator(dt, b0, b1):
 def check_env(model, wmodel, tcfg, ter, root0, dof0, root1, dof1, ncf, fs, body_params, friction, box_mass, dropped, tau, timer0=0.0,
               timer1=None, spec=DEFAULT_SPEC, tangled=False):
     """Steps 1 to 7 for one env. Returns dict(left_out (None or "clamp", "margin", "feature"), exact [...], ratio {tier: ...},
-    kind ("pair" / "corner" / None: what the one active contact is), cls, near, branch, mu, sphere, region, static, asleep)."""
+    kind ("pair" / "corner" / None: what the one active contact is), cls, near, branch, mu, sphere, region, static, asleep, dyn (the
+    dynamic slots within the margin: ("limbs", lane) / ("box", sphere)), feet (the foot spheres within the margin of the terrain))."""
     key = (bytes(wmodel), bytes(tcfg))
     if key not in _TABLES:
         _TABLES[key] = (clr.table_model(model, wmodel), clr.spheres(wmodel), fdr.tables(wmodel, tcfg), box_tables(wmodel), limb_tables(wmodel))
@@ -403,7 +404,11 @@ def check_env(model, wmodel, tcfg, ter, root0, dof0, root1, dof1, ncf, fs, body_
     G = box_geometry(tm, sph, bt, ter, cfg, root0, dof0[:, 0], spec)
     g = G["robot"]
     internal = internal_geometry(lt, sph, g, cfg)
-    gaps = [(p["gap"], p["mag_gap"]) for p in internal] + [(p["gap"], p["mag_gap"]) for p in G["pairs"]] + [(cn["gap"], cn["mag_gap"]) for cn in G["corners"]] + list(zip(g["gap"], g["mag_gap"]))
+    # the dynamic slots in contact (limb pairs by lane, promoted box spheres) and the feet on the terrain: tests/decimation_reference.py
+    out["dyn"] = frozenset([("limbs", p["lane"]) for p in internal if p["kind"] == "limbs" and p["active"]]
+                           + [("box", p["sphere"]) for p in G["pairs"] if p["active"] and p["sphere"] in PROMOTED_BOX_SPHERES])
+    out["feet"] = frozenset(int(k) for k in np.flatnonzero(g["active"][:4]))
+    gaps =[(p["gap"], p["mag_gap"]) for p in internal] + [(p["gap"], p["mag_gap"]) for p in G["pairs"]] + [(cn["gap"], cn["mag_gap"]) for cn in G["corners"]] + list(zip(g["gap"], g["mag_gap"]))
     if out["left_out"] is None and any(abs(gp - cfg["margin"]) <= MARGIN_GUARD * EPS * mg for gp, mg in gaps):
         out["left_out"] = "margin"
     if out["left_out"] is None:
@@ -1460,12 +1465,13 @@ def case_states(robot, name):
     return _STATES[name]
 
 
-def step_states(robot, name):
+def step_states(robot, name, case=None, **cfg):
     """Tier E: (tcfg, terrain, root, dof, actions) -- the staged states of B-255 tiled over the envs; decimation = 1, the attitude and
-    height terminations out of reach, the arm slower (as contact_law_reference.step_states)."""
-    case = STEP_CASES[name]
+    height terminations out of reach, the arm slower (as contact_law_reference.step_states). case: dict(n, seed, source[, sigma]) instead
+    of STEP_CASES[name]; cfg: further fields of the task cfg (tests/decimation_reference.py)."""
+    case = STEP_CASES[name] if case is None else case
     tc, ter, root, dof = case_states(robot, case["source"])[:4]
-    tc = case_cfg(tc, decimation=1, term_rp_threshold=100.0, term_z_threshold=-100.0)
+    tc = case_cfg(tc, **dict(dict(decimation=1, term_rp_threshold=100.0, term_z_threshold=-100.0), **cfg))
     if CASES[case["source"]]["kind"] == "tree":
         # the staged limb pairs are poses anywhere inside the joint limits, far from the default pose the actions are offsets of: with
         # the shipped gains the PD torques alone take 60 % of them into the velocity clamp within the substep. A twentieth of the
@@ -1475,7 +1481,7 @@ def step_states(robot, name):
             tc.d_gains[i] *= 0.25
     idx = np.arange(case["n"]) % len(root)
     rng = np.random.default_rng(case["seed"])
-    act = (STEP_SIGMA * rng.normal(size=(case["n"], 18))).astype(np.float32)
+    act = (case.get("sigma", STEP_SIGMA) * rng.normal(size=(case["n"], 18))).astype(np.float32)
     root, dof = root[idx].copy(), dof[idx].copy()
     dof[:, 12:18, 1] *= 0.25
     return tc, ter, root, dof, act

@@ -31,6 +31,7 @@ C-256 54 / 86 / 106 / 1, 23, 99 / 108 / 40 (triangles 121 / 126, 28 clipped indi
 cell border). The step tier, the same on all three: E-2560 82 / 63 / 104 / 0 of 249 checked (8 left out for a velocity clamp),
 E-2560-grid 72 / 41 / 121 / 1 of 235 (22 left out). No env of any case sits in a decision band or at the margin. The frictionless
 fallback is produced once per grid case by the fp64 oracle and by the kernel alike (reported, not asserted as a count).
+Case E runs decimation = 1; the step kernel's decimation loop (substeps 2 to 4 of a launch) is held by tests/test_gpu_step_decimation.py.
 """
 import numpy as np
 import pytest

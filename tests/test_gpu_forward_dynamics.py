@@ -16,6 +16,7 @@ asserted on the CPU by tests/test_forward_dynamics.py, never taken from the kern
 
 The kernel's maxima all sit on row 21 (the forearm roll, the lightest joint of the tree): airborne-256 env 84; contact-256 third
 substep env 167; limit-128 env 88; step-2560 fourth step env 1770. No row comes closer to its C than a factor of 3.8.
+The step kernel runs decimation = 1 here; its decimation loop (substeps 2 to 4 of a launch) is held by tests/test_gpu_step_decimation.py.
 """
 import numpy as np
 import pytest

@@ -29,6 +29,7 @@ K_ref sits on E-2560 env 2550 (velocity), T-96 env 73 (cone), K-128-grid env 123
 (root rows), E-2560-box env 790 (joint rows), S-64 env 62 (box). Counts and classes: DESIGN.md section 3. Largest contraction
 |1 - W_t W_u^-1|: 1.00.
 The box row of NET_CONTACT_FORCE is the row reduction's sum itself, so a lone pair's two rows are exact negatives.
+Case E runs decimation = 1; the step kernel's decimation loop (substeps 2 to 4 of a launch) is held by tests/test_gpu_step_decimation.py.
 """
 import numpy as np
 import pytest
